@@ -3,7 +3,7 @@
 bench.py -- AR-training samples/sec on the synthetic 512x512x60 grid, 3-step rollout
 (BASELINE.json metric; SURVEY.md section 8(d) workload).
 
-    python bench.py --gpus N --steps K --warmup W [--model HalfUNet] [--dtype bf16|f32]
+    python bench.py --gpus N --steps K --warmup W [--model HalfUNet] [--dtype bf16|f32] [--dump-outputs DIR] [--full]
 
 One "step" = one micro-batch of B samples per GPU through: 3 AR steps (build x -> model forward
 -> scaled residual update + border forcing -> weighted MSE) -> backward through the rollout
@@ -12,6 +12,11 @@ the device and resident in HBM before the timed region.  Rank 0 prints ONE JSON 
 
 For N>1 launch with torch.distributed.run (one rank per GPU); samples are independent, each rank
 draws its own B samples (weak scaling) and the only collective is the gradient all-reduce.
+
+A plain run does only what the headline figure needs: setup, W warm-up steps, the K timed steps, the result line.  Everything
+else it can measure -- the roofline object and per-kernel times, the native share of kernel time, the fp32 flavour and the larger
+batch, the CPU baseline, BASELINE configurations 3 / 4 / 5 -- runs with --full only.  --dump-outputs DIR writes what the last
+timed step handed its caller (loss, trained parameters) as .npy files, so that two builds can be compared output for output.
 """
 
 import argparse
@@ -85,9 +90,14 @@ def parse_args():
     ap.add_argument("--no-larger-batch", action="store_true", help="skip the short `larger_batch` measurement (bf16, --larger-batch samples per GPU)")
     ap.add_argument("--larger-batch", type=int, default=8)
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default HalfUNet run on one GPU: do not also time BASELINE configurations 3 / 4 / 5 (SwinUNetR, HiLAM, UNetRPP 6-step "
+                    help="--full HalfUNet run on one GPU: do not also time BASELINE configurations 3 / 4 / 5 (SwinUNetR, HiLAM, UNetRPP 6-step "
                          "diff_ar; 5 steps each in child processes of their own) into `other_configs`")
     ap.add_argument("--other-configs-launcher", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure: roofline and per-kernel times, native share, fp32 flavour, "
+                         "larger batch, CPU baseline, other BASELINE configurations (each can still be switched off by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, trained parameters) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -100,7 +110,7 @@ OTHER_CONFIGS = {
 
 
 def other_configs_launcher():
-    """Runs in a child process that the default run starts BEFORE its own first GPU call and that never touches the GPU itself: waits
+    """Runs in a child process that the --full run starts BEFORE its own first GPU call and that never touches the GPU itself: waits
     for a line on stdin (the headline legs are done), then runs one `bench.py --model X` per configuration as a child of its own -- a
     fresh process each, nothing re-executed from a process that has initialised the GPU -- and prints ONE JSON object with their
     ms_per_step / native_share / roofline.step.frac."""
@@ -113,7 +123,7 @@ def other_configs_launcher():
             str(args.forcings), "--hidden", str(args.hidden)]      # (the bench size unless the caller shrank it: tests)
     res = {}
     for name, extra in OTHER_CONFIGS.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--model", name, "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--model", name, "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
                "--no-other-configs"] + size + extra
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
@@ -130,6 +140,24 @@ def other_configs_launcher():
         except Exception as exc:  # noqa: BLE001  (a configuration that fails is reported as such, the headline line stays valid)
             res[name] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
     print(json.dumps(res), flush=True)
+
+
+DUMP_MAX_ELEMENTS = 15_000_000   # 60 MB of float32: --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the timed path hands its caller after its last step -- that step's loss (loss.npy, float64) and the
+    trained parameters (params.npy: every trainable tensor in named_parameters order, flattened into one float32 vector; above
+    DUMP_MAX_ELEMENTS a seeded sample of it, the same positions in every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters() if p.requires_grad])
+    if flat.numel() > DUMP_MAX_ELEMENTS:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMENTS].sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, "loss.npy"), np.asarray([loss], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), flat.cpu().numpy().astype(np.float32))
 
 
 def synthetic_case(seed, B, T, T_in, H, W, F, Ff, Fs, border, device):
@@ -413,9 +441,9 @@ def main():
     # (never under a profiler: its preloaded library initialises the GPU before this program starts, and a child started from such a
     # process is exactly the re-exec the GPU boxes forbid)
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.model == "HalfUNet" and not args.no_other_configs and not args.kernel_times
-            and args.dtype == "bf16" and not profiled):
-        # the default run also reports configurations 3 / 4 / 5: their launcher is started HERE, before this process touches the GPU
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.model == "HalfUNet" and not args.no_other_configs
+            and not args.kernel_times and args.dtype == "bf16" and not profiled):
+        # the --full run also reports configurations 3 / 4 / 5: their launcher is started HERE, before this process touches the GPU
         import subprocess
 
         others = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--other-configs-launcher", "--grid", str(args.grid[0]),
@@ -590,11 +618,13 @@ def _main(args, others=None):
     timed = getattr(lm.model, "timed_entry_points", None) or (
         "p4c_build_x", "p4c_ar_update_fwd", "p4c_weighted_loss_fwd", "p4c_weighted_loss_bwd", "p4c_ar_update_bwd")
     has_roofline = hasattr(lm.model, "roofline")
-    if args.kernel_times or not has_roofline or getattr(lm.model, "roofline_from_entry_points", False):
+    # kernel times and the roofline object: --full (or --kernel-times) only; a plain run's timed steps carry no event markers
+    kernel_legs = args.full or args.kernel_times
+    if kernel_legs and (args.kernel_times or not has_roofline or getattr(lm.model, "roofline_from_entry_points", False)):
         L.enable_kernel_timing(timed)
     if args.kernel_times:
         L.lib().p4c_prof_enable(7, 4096)
-    elif has_roofline and not getattr(lm.model, "roofline_from_entry_points", False):
+    elif kernel_legs and has_roofline and not getattr(lm.model, "roofline_from_entry_points", False):
         # roofline leg: only the dominant kernel's forward-plan launches at full resolution get event markers, and only those of
         # the first four timed steps (3 per AR step): an event record costs the stream a bubble of several microseconds, so
         # marking all of them (90 launches at the defaults) lowered the measured throughput by ~2 %
@@ -604,18 +634,22 @@ def _main(args, others=None):
     roof_model = None
     graph_note = None
     work = None
+    ktimes = {}
     if use_graph:
         # kernel timings for the roofline object come from two eager steps (a replayed graph has no per-call host hooks);
-        # then the micro-batch is captured and the warm-up + timed steps replay it
+        # then the micro-batch is captured and the warm-up + timed steps replay it.  The two steps run without --full too, so that
+        # the timed steps train the same weights in either mode
         from py4cast_amd.trainer import GraphedTrainingStep
 
-        L.WORK[0] = {"bytes": 0.0, "flops": 0.0, "calls": 0, "unstated": 0}
+        if kernel_legs:
+            L.WORK[0] = {"bytes": 0.0, "flops": 0.0, "calls": 0, "unstated": 0}
         for i in range(2):
             step(args.warmup + i)
-        work, L.WORK[0] = L.WORK[0], None
-        work = {k: v / 2 for k, v in work.items()}        # per step
-        ktimes = L.kernel_times()
-        roof_model = lm.model.roofline(ktimes, B=B, H=H, W=W) if (rank == 0 and hasattr(lm.model, "roofline")) else None
+        if kernel_legs:
+            work, L.WORK[0] = L.WORK[0], None
+            work = {k: v / 2 for k, v in work.items()}        # per step
+            ktimes = L.kernel_times()
+            roof_model = lm.model.roofline(ktimes, B=B, H=H, W=W) if (rank == 0 and hasattr(lm.model, "roofline")) else None
         L.enable_kernel_timing(None)
         L.lib().p4c_prof_enable(0, 0)   # no event markers inside a capture
         ddp.zero_grad()
@@ -659,13 +693,16 @@ def _main(args, others=None):
         gc.enable()
     gc.unfreeze()
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    if not use_graph:
+    last_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:   # (before any un-timed step below trains the parameters further)
+        dump_outputs(args.dump_outputs, last_loss, lm.model)
+    if not use_graph and kernel_legs:
         ktimes = L.kernel_times()
         roof_model = lm.model.roofline(ktimes, B=B, H=H, W=W) if (rank == 0 and hasattr(lm.model, "roofline")) else None
-        L.enable_kernel_timing(None)
+    L.enable_kernel_timing(None)
     L.lib().p4c_prof_enable(0, 0)
     extra = None
-    if has_roofline and not use_graph and not getattr(lm.model, "roofline_from_entry_points", False) \
+    if args.full and has_roofline and not use_graph and not getattr(lm.model, "roofline_from_entry_points", False) \
             and hasattr(lm.model, "launch_times"):   # (every rank: the step contains the gradient exchange)
         # ONE extra un-timed step with every tagged launch bracketed by events: data-gradient and weight-gradient launch times
         # of the roofline kernel's siblings (they overlap each other in the backward plan, hence reported apart)
@@ -676,7 +713,7 @@ def _main(args, others=None):
         L.lib().p4c_prof_enable(0, 0)
     affinity_all = None
     share = None
-    if rank == 0 and world == 1 and not args.no_native_share:
+    if args.full and rank == 0 and world == 1 and not args.no_native_share:
         saved_graph, graphed[0] = graphed[0], None          # one EAGER step under the profiler (a replay has the same kernels)
         if work is None:
             L.WORK[0] = {"bytes": 0.0, "flops": 0.0, "calls": 0, "unstated": 0}
@@ -792,14 +829,15 @@ def _main(args, others=None):
                 "host_affinity_policy": __import__("py4cast_amd.trainer", fromlist=["AFFINITY_POLICY"]).AFFINITY_POLICY[0],
                 "environment_settings": L.environment_settings(),
                 "launch_mode_probe": probe,
+                "full": bool(args.full),
             },
-            "loss": float(loss.detach()),
+            "loss": last_loss,
             "native_share": None if share is None else {"of_gpu_kernel_time": round(share[0], 4), "ms_by_origin": share[1], "kernels": share[2],
                                                         "note": "one eager step under torch.profiler: kernels named p4c:: are this repository's"},
             "roofline": roof,
             "kernel_ms": {k: {"calls": v[0], "avg_ms": round(v[1], 4)} for k, v in ktimes.items()},
         }
-        if (world == 1 and not args.no_fp32_flavour and args.dtype == "bf16" and args.model == "HalfUNet"
+        if (args.full and world == 1 and not args.no_fp32_flavour and args.dtype == "bf16" and args.model == "HalfUNet"
                 and hasattr(lm.model, "native_rollout")):
             # the parity flavour (exact fp32 matrix cores, fp32 storage; <= 1e-4 vs the oracle) of the SAME workload, measured by
             # the same process after the headline run: a short run of its own (2 setup + 2 warm-up + 6 timed steps)
@@ -814,7 +852,7 @@ def _main(args, others=None):
                 out["larger_batch"] = fp32_flavour(args, big, info, device, steps=8, warmup=4, dtype="bf16", batch=args.larger_batch)
                 out["larger_batch"]["note"] = ("same rollout / loss / optimizer and model at a per-GPU batch the 288 GB of HBM invite; not the "
                                                "headline `value` (BASELINE.md fixes B=2 per GPU)")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         if others is not None:
             # BASELINE configurations 3 / 4 / 5, each in a fresh process (this one's GPU work is done; its memory is released first)

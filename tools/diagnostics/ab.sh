@@ -2,7 +2,7 @@
 # same-box A/B: runs bench.py alternately with the libraries given as arguments
 for rep in 1 2; do
 for lib in "$@"; do
-  P4C_LIB_PATH=$GRAFT_REPO_ROOT/tools/diagnostics/libs/$lib python bench.py --dtype bf16 --no-cpu-baseline --steps 15 2>/dev/null | python -c "
+  P4C_LIB_PATH=$PWD/tools/diagnostics/libs/$lib python bench.py --full --dtype bf16 --no-cpu-baseline --steps 15 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 k = d['kernel_ms']

@@ -2,7 +2,7 @@
 # same-box A/B of an environment switch: scratch/ab_env.sh VAR valA valB
 for rep in 1 2; do
 for v in "$2" "$3"; do
-  env $1=$v python bench.py --no-cpu-baseline --steps 15 2>/dev/null | python -c "
+  env $1=$v python bench.py --full --no-cpu-baseline --steps 15 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 k = d['kernel_ms']
