@@ -106,6 +106,13 @@ int p4c_build_x(const float* prev, int64_t prev_bs, int64_t prev_ts, const float
 int p4c_build_x_bwd(const void* dx, int dx_dtype, int c_pad, float* dprev, int B, int T_in, int64_t N, int F,
                     p4c_stream_t stream);
 
+/* Gradient of one state slot in the reverse sweep of a rollout with num_input_steps >= 2: out[b,n,f] (batch stride out_bs, rows of F
+ * floats) = sum over k = 0 .. n_src-1, in that order, of src[k][b * src_bs[k] + n * src_cs[k] + src_off[k] + f], src_dtype[k] P4C_F32 or
+ * P4C_BF16 (n_src <= 8; src_off[k] + F <= src_cs[k]).  Sources: the prediction's gradient, the residual path of the next AR step, the
+ * F-channel block of the input gradient of every later step whose window holds the state. */
+int p4c_sum_state_grads(float* out, int64_t out_bs, int n_src, const void* const* src, const int64_t* src_bs, const int* src_cs,
+                        const int* src_off, const int* src_dtype, int B, int64_t N, int F, p4c_stream_t stream);
+
 /* K1 with the masked-auto-encoder block mask of mask_tensor (lightning.py:769-785, applied at :580-581) fused in:
  * x[b, (yy,xx), c] *= 0 for every grid point whose block index (yy / block_h) * W + (xx / block_w) is set in
  * block_selected (H*W bytes, 1 = drawn by the caller's randperm; the draw itself stays with torch's CPU generator,
@@ -323,7 +330,8 @@ int p4c_prep_weights(const float* w, int CO, int CI, int ks, int transpose_flip,
  * with act(v) = relu?(v*in_scale[b,k] + in_shift[b,k]) applied while the input tile is staged
  * (in_scale/in_shift: (B,CI) or NULL).  stat_partial (or NULL): per-tile channel sums,
  * [B*tiles][2][64] floats with tiles = p4c_conv_stat_tiles(compute, storage, CI, B, H, W) -- the BatchNorm/GroupNorm statistics of
- * the output, produced in the epilogue.  in: (B,H,W,CI), CI in {32,64,96}; out: (B,H,W,out_cs),
+ * the output, produced in the epilogue.  in: (B,H,W,CI), CI in {32,64,96} (ks = 1 or 3) or, for ks = 3 and no bias, any multiple of
+ * 32 up to 256 (beyond 96: K in 32-channel chunks, the first convolution of a multi-step input); out: (B,H,W,out_cs),
  * m_blocks*64 channels written. */
 int p4c_conv_fwd(const void* in, int compute, int storage, int CI, const void* wprep, int ks, const float* in_scale,
                  const float* in_shift, int in_relu, const float* bias, void* out, int out_cs, float* stat_partial,
@@ -397,9 +405,11 @@ int p4c_conv_wgrad_compact(const void* in, int in_c, int ks, const void* dout, i
 typedef struct p4c_halfunet_desc {
     int32_t B, H, W;      /* H, W multiples of 16 */
     int32_t cin;          /* real input channels */
-    int32_t cin_pad;      /* x is (B,H,W,cin_pad), cin_pad in {32,64,96}; channels >= cin must be zero */
+    int32_t cin_pad;      /* x is (B,H,W,cin_pad), cin_pad a multiple of 32 up to 256 (beyond 96: num_input_steps >= 2, the first
+                             convolution runs K in 32-channel chunks); channels >= cin must be zero */
     int32_t cout;         /* real output channels (<= 64); y is (B,H,W,64), channels >= cout are zero */
-    int32_t dx_channels;  /* leading input channels whose gradient is returned (<= 64, 0 = none) */
+    int32_t dx_channels;  /* leading input channels whose gradient is returned (<= cin, 0 = none); dx rows are
+                             64 * ceil(dx_channels / 64) channels wide (64 when dx_channels <= 64) */
     int32_t dtype;        /* storage of x, y, dy, dx and of the saved activations: P4C_F32, or P4C_BF16 (needs compute = P4C_BF16) */
     int32_t norm;         /* 0 = BatchNorm2d, 1 = GroupNorm */
     int32_t groups;       /* GroupNorm groups (divides 64) */
@@ -468,7 +478,7 @@ int p4c_halfunet_forward(const p4c_halfunet_desc* d, const void* x, const float*
 int p4c_halfunet_tail(const p4c_halfunet_desc* d, const float* params, void* saved, const void** a, const float** a_scale,
                       const float** a_shift, const float** wout);
 /* dy: (B,H,W,64), channels >= cout must be ZERO (the fused backward of the output convolution feeds all 64 to the matrix cores
- * against zero weight rows: NaN / Inf garbage there would reach every upstream gradient; the in-tree rollout zero-fills them); dx: (B,H,W,64) or NULL (first dx_channels channels valid);
+ * against zero weight rows: NaN / Inf garbage there would reach every upstream gradient; the in-tree rollout zero-fills them); dx: (B,H,W,64 * ceil(dx_channels / 64)) -- (B,H,W,64) up to 64 -- or NULL (first dx_channels channels valid);
  * grads: flat, same layout as params, ACCUMULATED into (+=). */
 int p4c_halfunet_backward(const p4c_halfunet_desc* d, const void* x, const float* params, const void* dy, void* dx,
                           float* grads, void* saved, void* scratch, int training, p4c_stream_t stream);

@@ -1952,6 +1952,219 @@ static int launch_conv3x3_wgrad_bf16_ws(const __bf16* in, const float* in_scale,
 }
 
 // ---------------------------------------------------------------------------------------------
+// conv_fwd_bf16_wide: the 3x3 convolution from CI = 128 .. 256 input channels (multiple of 32) to 64 outputs -- the first
+// convolution of a HalfUNet fed num_input_steps >= 2 past states.  The 9*CI*64 bf16 weight image (up to 288 KB) no longer fits
+// the LDS, so K runs in chunks of WCC = 32 input channels: every chunk stages its 36 KB of weights and the 32-channel slice of the
+// halo tile, double buffered, while the fp32 accumulators stay in registers across all of K and are rounded once on store.
+// Persistent: grid = min(tiles, CUs) x M_pad/64, 256 threads; tile 8 x 32 pixels, wave w owns tile rows 2w, 2w+1 (two 32-pixel
+// N-tiles) x both 32-channel tiles.  The (tile, chunk) pairs of a workgroup form ONE pipeline with one barrier per chunk:
+//   MFMA(chunk i from buf[i&1]) ; [last chunk of a tile: epilogue] ; registers(chunk i+1) -> buf[~i&1] ; issue loads(chunk i+2)
+// LDS: 2 x (36 KB weights + 27 KB tile) + statistics scratch = 147 KB: one workgroup per CU.
+// Statistics: one slot [2][64] per tile (sample-major: slot = b * tiles_per_sample + ty * tiles_x + tx), sums of the STORED
+// values (rounded when T is bf16) -- the per-tile slot format norm_finalize reads.
+constexpr int WCC = 32;        // input channels per K chunk
+constexpr int WIDE_TH = 8;     // tile rows
+static inline int conv_wide_stat_slots(int H, int W) { return ((H + WIDE_TH - 1) / WIDE_TH) * ((W + BTW - 1) / BTW); }
+
+template <typename T>
+__global__ void __launch_bounds__(256, 1)
+    conv_fwd_bf16_wide_kernel(const T* __restrict__ in, int CI, const __bf16* __restrict__ wp, const float* __restrict__ in_scale,
+                              const float* __restrict__ in_shift, int in_relu, T* __restrict__ out, int out_cs,
+                              float* __restrict__ stat_partial, int B, int H, int W) {
+    constexpr int KS = 3, HALO = 1, NTAPS = 9;
+    constexpr int TH = WIDE_TH;
+    constexpr int LH = TH + 2 * HALO, LW = BTW + 2 * HALO;
+    constexpr int ROWB = WCC * 2 + 16;                      // 5 x 16-byte slots per pixel row: odd, conflict-free b128 reads
+    constexpr int WCB = NTAPS * (WCC / 16) * 2048;          // weight bytes per chunk: [tap][kstep(2)][h][64][8] bf16
+    constexpr int TILEB = (LH * LW * ROWB + 15) / 16 * 16;
+    constexpr int BUFB = WCB + TILEB;
+    constexpr int WITERS = WCB / (256 * 16);                // 16-byte weight loads per thread and chunk (9)
+    static_assert(WCB % (256 * 16) == 0, "weight chunk must split evenly over the workgroup");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* tw = reinterpret_cast<float*>(smem + 2 * BUFB) + (threadIdx.x >> 6) * (32 * 33);   // per-wave transpose scratch
+    float* red = reinterpret_cast<float*>(smem + 2 * BUFB) + 4 * 32 * 33;                    // [wave][2][64]
+
+    const int NC = CI / WCC;
+    const int NKST = CI / 16;                               // k-steps of the whole weight image per tap
+    const int mb = blockIdx.y;
+    const __bf16* wimg = wp + (int64_t)mb * NTAPS * CI * 64;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int tiles_x = (W + BTW - 1) / BTW, tiles_y = (H + TH - 1) / TH;
+    const int ntiles = tiles_x * tiles_y * B;
+    const int t_begin = (int)((int64_t)ntiles * blockIdx.x / gridDim.x);
+    const int t_end = (int)((int64_t)ntiles * (blockIdx.x + 1) / gridDim.x);
+    if (t_begin >= t_end) return;
+    const int n_it = (t_end - t_begin) * NC;
+    // tiles ordered down a 32-pixel-wide strip (ty fastest): halo rows shared with the previous tile are L2 hits
+    auto coords = [&](int t, int& b, int& y0, int& x0, int& canon) {
+        const int ty = t % tiles_y;
+        const int rest = t / tiles_y;
+        const int tx = rest % tiles_x;
+        b = rest / tiles_x;
+        y0 = ty * TH;
+        x0 = tx * BTW;
+        canon = (b * tiles_y + ty) * tiles_x + tx;
+    };
+
+    BTile<T, WCC, LH, LW> tr;
+    f32x4 wr[WITERS];
+    auto load = [&](int it) {
+        const int t = t_begin + it / NC, c = it % NC;
+        int b, y0, x0, cn;
+        coords(t, b, y0, x0, cn);
+        btile_load<T, WCC, LH, LW, HALO>(tr, in + c * WCC, b, y0, x0, H, W, CI);
+        // chunk c of tap `tap` = k-steps 2c, 2c+1 of that tap: 4096 contiguous bytes of the image
+        const char* src = reinterpret_cast<const char*>(wimg) + (int64_t)c * 2 * 2048 + threadIdx.x * 16;
+#pragma unroll
+        for (int tap = 0; tap < WITERS; ++tap) wr[tap] = *reinterpret_cast<const f32x4*>(src + (int64_t)tap * NKST * 2048);
+    };
+    auto store = [&](int it, char* buf) {
+        const int t = t_begin + it / NC, c = it % NC;
+        int b, y0, x0, cn;
+        coords(t, b, y0, x0, cn);
+#pragma unroll
+        for (int tap = 0; tap < WITERS; ++tap) *reinterpret_cast<f32x4*>(buf + tap * 4096 + threadIdx.x * 16) = wr[tap];
+        btile_store<T, WCC, LH, LW, HALO, ROWB>(tr, in_scale ? in_scale + c * WCC : nullptr, in_shift ? in_shift + c * WCC : nullptr,
+                                                in_relu, buf + WCB, b, y0, x0, H, W, CI);
+    };
+
+    load(0);
+    store(0, smem);
+    if (n_it > 1) load(1);
+    __syncthreads();
+
+    f32x16 acc[2][2];   // [pixel row pt][channel tile ct]
+    int done_canon = -1, done_b = 0;
+    for (int it = 0; it < n_it; ++it) {
+        const int c = it % NC;
+        if (done_canon >= 0) {   // the previous tile's statistics: every wave's slot is in `red` since the last barrier
+            if (threadIdx.x < 128) {
+                const int t = threadIdx.x;
+                stat_partial[((int64_t)done_b * tiles_x * tiles_y + done_canon) * 128 + t] =
+                    (red[t] + red[128 + t]) + (red[256 + t] + red[384 + t]);
+            }
+            done_canon = -1;
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) acc[pt][ct][i] = 0.f;
+        }
+        const char* cur = smem + (it & 1) * BUFB;
+        {
+            // operand double buffering at tap granularity: the 8 LDS reads of tap t+1 are issued before the 8 MFMAs of tap t
+            const char* wl = cur + (h * 64 + r) * 16;
+            const char* pl0 = cur + WCB + (2 * wv * LW + r) * ROWB + 16 * h;
+            bf16x8 fa[2][2][2], fb[2][2][2];   // [buffer][ct | pt][kstep]
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) fa[0][ct][ks] = *reinterpret_cast<const bf16x8*>(wl + ks * 2048 + ct * 512);
+#pragma unroll
+                for (int pt = 0; pt < 2; ++pt) fb[0][pt][ks] = *reinterpret_cast<const bf16x8*>(pl0 + pt * LW * ROWB + 32 * ks);
+            }
+#pragma unroll
+            for (int tap = 0; tap < NTAPS; ++tap) {
+                const int cb = tap & 1, nb = cb ^ 1;
+                if (tap + 1 < NTAPS) {
+                    const int ky = (tap + 1) / KS, kx = (tap + 1) % KS;
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct)
+                            fa[nb][ct][ks] = *reinterpret_cast<const bf16x8*>(wl + ((tap + 1) * 2 + ks) * 2048 + ct * 512);
+#pragma unroll
+                        for (int pt = 0; pt < 2; ++pt)
+                            fb[nb][pt][ks] = *reinterpret_cast<const bf16x8*>(pl0 + ((pt + ky) * LW + kx) * ROWB + 32 * ks);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                    for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct)
+                            acc[pt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cb][ct][ks], fb[cb][pt][ks], acc[pt][ct], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+
+        if (c == NC - 1) {
+            // ---- epilogue: C[co][px]; lane = pixel r (+ half h), register i -> co = ct*32 + (i&3) + 8*(i>>2) + 4*h
+            int b, y0, x0, canon;
+            coords(t_begin + it / NC, b, y0, x0, canon);
+            const int gx = x0 + r;
+            float s1[2][16], s2[2][16];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) s1[ct][i] = s2[ct][i] = 0.f;
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt) {
+                const int gy = y0 + 2 * wv + pt;
+                const bool valid = (gy < H) && (gx < W);
+                T* orow = out + (((int64_t)b * H + gy) * W + gx) * out_cs + mb * 64 + 4 * h;
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        f32x4 v = {acc[pt][ct][4 * g], acc[pt][ct][4 * g + 1], acc[pt][ct][4 * g + 2], acc[pt][ct][4 * g + 3]};
+                        if (std::is_same<T, __bf16>::value) {   // statistics of what is stored
+                            v.x = (float)(__bf16)v.x; v.y = (float)(__bf16)v.y; v.z = (float)(__bf16)v.z; v.w = (float)(__bf16)v.w;
+                        }
+                        if (valid) store4(orow + ct * 32 + 8 * g, v);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float o = valid ? v[j] : 0.f;
+                            s1[ct][4 * g + j] += o;
+                            s2[ct][4 * g + j] = __builtin_fmaf(o, o, s2[ct][4 * g + j]);
+                        }
+                    }
+            }
+            if (stat_partial) {
+                flush_stats(s1, s2, tw, red + wv * 128, lane);
+                done_canon = canon - b * tiles_x * tiles_y;
+                done_b = b;
+            }
+        }
+
+        // the other buffer was last read by MFMA(it-1), which every wave finished before the previous barrier
+        if (it + 1 < n_it) store(it + 1, smem + ((it + 1) & 1) * BUFB);
+        if (it + 2 < n_it) load(it + 2);
+        __syncthreads();
+    }
+    if (done_canon >= 0 && threadIdx.x < 128) {
+        const int t = threadIdx.x;
+        stat_partial[((int64_t)done_b * tiles_x * tiles_y + done_canon) * 128 + t] = (red[t] + red[128 + t]) + (red[256 + t] + red[384 + t]);
+    }
+}
+
+template <typename T>
+static int launch_conv_fwd_bf16_wide(const T* in, int CI, const __bf16* wp, const float* in_scale, const float* in_shift, int in_relu,
+                                     T* out, int out_cs, float* stat_partial, int B, int H, int W, int m_blocks, hipStream_t stream) {
+    if (CI % WCC || CI <= 96 || CI > 256) return fail(P4C_ERR_UNSUPPORTED, "conv_fwd_bf16_wide: CI=%d (multiple of 32 in 128..256)", CI);
+    if (stat_partial && m_blocks != 1) return fail(P4C_ERR_UNSUPPORTED, "conv_fwd_bf16_wide: statistics need m_blocks = 1");
+    if (out_cs % 4 || out_cs < 64 * m_blocks) return fail(P4C_ERR_INVALID, "conv_fwd_bf16_wide: out_cs=%d", out_cs);
+    constexpr int LH = WIDE_TH + 2, LW = BTW + 2;
+    constexpr size_t BUFB = (size_t)9 * 2 * 2048 + (LH * LW * (WCC * 2 + 16) + 15) / 16 * 16;
+    const size_t smem = 2 * BUFB + (4 * 32 * 33 + 4 * 128) * sizeof(float);
+    auto kern = conv_fwd_bf16_wide_kernel<T>;
+    P4C_TRY(ensure_dyn_smem((const void*)kern, (int)smem));
+    const int64_t ntiles = (int64_t)conv_wide_stat_slots(H, W) * B;
+    int G = num_cus();
+    if (ntiles < G) G = (int)ntiles;
+    hipLaunchKernelGGL(kern, dim3(G, m_blocks), dim3(256), smem, stream, in, CI, wp, in_scale, in_shift, in_relu, out, out_cs,
+                       stat_partial, B, H, W);
+    P4C_CHECK_LAUNCH("conv_fwd_bf16_wide");
+    return P4C_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 template <typename T, int CI, int KS, int NBUF>
 static int launch_conv_fwd_bf16(const T* in, const __bf16* wp, const float* in_scale, const float* in_shift, int in_relu,
                                 T* out, int out_cs, float* stat_partial, int B, int H, int W, int m_blocks,
@@ -2004,6 +2217,7 @@ static int launch_conv_wgrad_bf16(const T* in, const float* in_scale, const floa
 
 // rows per sample of the statistics partial buffer written by conv_fwd_bf16
 int conv_bf16_stat_slots(int CI, int storage, int B, int H, int W, int ks) {
+    if (CI > 96 && ks == 3) return conv_wide_stat_slots(H, W);   // K-chunked kernel: one slot per 8 x 32 tile
     if (conv_bf16_is_rows(storage, CI, ks, 1, 64, B, H, W)) return conv_rows_stat_slots(B, H, W);   // per (workgroup, loader wave)
     const int tiles = ((H + 3) / 4) * ((W + BTW - 1) / BTW);
     if (CI > 64 && storage != P4C_BF16) return tiles;  // per-tile partials (single-buffer kernel, fp32 storage)
@@ -2017,6 +2231,8 @@ static int conv_fwd_bf16_t(const T* in, int CI, const void* wp, int ks, const fl
                            int in_relu, T* out, int out_cs, float* stat_partial, int B, int H, int W, int m_blocks,
                            hipStream_t stream) {
     const __bf16* w = (const __bf16*)wp;
+    if (CI > 96 && ks == 3)   // (the first convolution of a multi-step input: 128 .. 256 channels, K in 32-channel chunks)
+        return launch_conv_fwd_bf16_wide<T>(in, CI, w, in_scale, in_shift, in_relu, out, out_cs, stat_partial, B, H, W, m_blocks, stream);
 #define P4C_CASE(ci, k, nb)                                                                                          \
     if (CI == ci && ks == k)                                                                                         \
         return launch_conv_fwd_bf16<T, ci, k, nb>(in, w, in_scale, in_shift, in_relu, out, out_cs, stat_partial, B, H, \

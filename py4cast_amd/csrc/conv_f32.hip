@@ -392,6 +392,136 @@ __global__ void __launch_bounds__(256) wgrad_reduce_batch_kernel(WgradBatchArgs 
     wgrad_reduce_block<16>(J.partial, J.nslots, J.ntaps, J.CI_pad, J.ci_lo, J.ci_hi, J.CO, J.CI, J.grad, (int)blockIdx.x - a.first[j]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// conv_fwd_f32_wide: the 3x3 convolution from CI = 128 .. 256 input channels (multiple of 32) -- the first convolution of a
+// HalfUNet fed num_input_steps >= 2 past states -- for the exact-fp32 flavour.  conv_fwd_f32_kernel stages the whole halo tile
+// (LH*LW*(CI+4) floats: 212 KB at CI = 256, more than the LDS); here K runs in chunks of 32 input channels: the chunk's slice of
+// the tile is staged (29 KB), the next chunk's global loads are in flight during the current chunk's MFMAs, and the accumulators
+// stay in registers across all of K.  Weights stream from global / L2 exactly as in conv_fwd_f32_kernel (same prepared image).
+// Grid (tiles_x, tiles_y*B, M_pad/64), tile 4 x 32 pixels, same statistics epilogue and slot format (one slot per tile).
+template <int KS>
+__global__ void __launch_bounds__(256)
+    conv_fwd_f32_wide_kernel(const float* __restrict__ in, int CI, const float* __restrict__ wp, const float* __restrict__ in_scale,
+                             const float* __restrict__ in_shift, int in_relu, float* __restrict__ out, int out_cs,
+                             float* __restrict__ stat_partial, int H, int W) {
+    constexpr int CC = 32;          // input channels per K chunk
+    constexpr int TH = 4;
+    constexpr int HALO = KS / 2;
+    constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
+    constexpr int CIS = CC + 4;
+    constexpr int NTAPS = KS * KS;
+    constexpr int NQ = CC / 8;      // k groups of 8 channels per chunk
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+
+    const int NC = CI / CC, NQT = CI / 8;
+    const int tiles_y = (H + TH - 1) / TH;
+    const int b = blockIdx.y / tiles_y, ty = blockIdx.y - b * tiles_y;
+    const int y0 = ty * TH, x0 = blockIdx.x * TW;
+    const int mb = blockIdx.z;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[ct][i] = 0.f;
+
+    const float* wbase = wp + (int64_t)mb * NTAPS * CI * 64 + (h * 64 + r) * 4;
+    TileRegs<CC, LH, LW> tr;
+    tile_load<CC, LH, LW, HALO>(tr, in, b, y0, x0, H, W, CI);
+#pragma unroll 1
+    for (int c = 0; c < NC; ++c) {
+        __syncthreads();   // every wave is done with chunk c-1's tile slice
+        tile_store<CC, LH, LW, HALO>(tr, in_scale ? in_scale + c * CC : nullptr, in_shift ? in_shift + c * CC : nullptr, in_relu, lds, b,
+                                     y0, x0, H, W, CI);
+        __syncthreads();
+        if (c + 1 < NC) tile_load<CC, LH, LW, HALO>(tr, in + (c + 1) * CC, b, y0, x0, H, W, CI);   // in flight during the MFMAs
+        // weight group (tap, q) of this chunk: [tap][4c + q] of the prepared image; the next group's loads are issued first
+        f32x4 a0 = *reinterpret_cast<const f32x4*>(wbase + (int64_t)(4 * c) * 512);
+        f32x4 a1 = *reinterpret_cast<const f32x4*>(wbase + (int64_t)(4 * c) * 512 + 128);
+#pragma unroll 1
+        for (int tap = 0; tap < NTAPS; ++tap) {
+            const int ky = tap / KS, kx = tap - ky * KS;
+            const float* lt = lds + ((wv + ky) * LW + (r + kx)) * CIS + 4 * h;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int tn = q + 1 < NQ ? tap : (tap + 1 < NTAPS ? tap + 1 : tap);
+                const int qn = q + 1 < NQ ? q + 1 : 0;
+                const int64_t jn = (int64_t)tn * NQT + 4 * c + qn;
+                const f32x4 n0 = *reinterpret_cast<const f32x4*>(wbase + jn * 512);
+                const f32x4 n1 = *reinterpret_cast<const f32x4*>(wbase + jn * 512 + 128);
+                const f32x4 bb = *reinterpret_cast<const f32x4*>(lt + 8 * q);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], bb[s], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], bb[s], acc[1], 0, 0, 0);
+                }
+                a0 = n0;
+                a1 = n1;
+            }
+        }
+    }
+
+    // ---- epilogue (as conv_fwd_f32_kernel): C[co][px]; lane = pixel r (+ half h), register i -> co = (i&3) + 8*(i>>2) + 4*h
+    const int gx = x0 + r;
+    const int gy = y0 + wv;
+    const bool valid = (gy < H) && (gx < W);
+    __syncthreads();   // all waves are done reading the tile slice: LDS is reused below
+    float* tw = lds + wv * (64 * 33);
+    float* orow = out + (((int64_t)b * H + gy) * W + gx) * out_cs + mb * 64 + 4 * h;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 v = {acc[ct][4 * g], acc[ct][4 * g + 1], acc[ct][4 * g + 2], acc[ct][4 * g + 3]};
+            if (valid) *reinterpret_cast<f32x4*>(orow + ct * 32 + 8 * g) = v;
+            if (stat_partial) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) tw[(ct * 32 + 8 * g + 4 * h + j) * 33 + r] = valid ? v[j] : 0.f;
+            }
+        }
+    }
+    if (stat_partial) {
+        __syncthreads();
+        float s1 = 0.f, s2 = 0.f;
+        const float* row = tw + lane * 33;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            const float o = row[k];
+            s1 += o;
+            s2 += o * o;
+        }
+        float* red = lds + 4 * 64 * 33;  // [wave][stat][64]
+        red[(wv * 2 + 0) * 64 + lane] = s1;
+        red[(wv * 2 + 1) * 64 + lane] = s2;
+        __syncthreads();
+        if (threadIdx.x < 128) {
+            const int t = threadIdx.x;
+            const int64_t tile = ((int64_t)blockIdx.y) * gridDim.x + blockIdx.x;
+            stat_partial[tile * 128 + t] = (red[t] + red[128 + t]) + (red[256 + t] + red[384 + t]);
+        }
+    }
+}
+
+static int launch_conv_fwd_f32_wide(const float* in, int CI, const float* wp, const float* in_scale, const float* in_shift, int in_relu,
+                                    float* out, int out_cs, float* stat_partial, int B, int H, int W, int m_blocks, hipStream_t stream) {
+    if (CI % 32 || CI <= 96 || CI > 256) return fail(P4C_ERR_UNSUPPORTED, "conv_fwd_f32_wide: CI=%d (multiple of 32 in 128..256)", CI);
+    if (stat_partial && m_blocks != 1) return fail(P4C_ERR_UNSUPPORTED, "conv_fwd_f32_wide: statistics need m_blocks = 1");
+    if (out_cs % 4 || out_cs < 64 * m_blocks) return fail(P4C_ERR_INVALID, "conv_fwd_f32_wide: out_cs=%d", out_cs);
+    constexpr int LH = 4 + 2, LW = TW + 2;
+    size_t smem = (size_t)LH * LW * (32 + 4) * sizeof(float);
+    const size_t stat_smem = (4 * 64 * 33 + 4 * 2 * 64) * sizeof(float);
+    if (smem < stat_smem) smem = stat_smem;
+    auto kern = conv_fwd_f32_wide_kernel<3>;
+    P4C_TRY(ensure_dyn_smem((const void*)kern, (int)smem));
+    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + 3) / 4;
+    hipLaunchKernelGGL(kern, dim3(tiles_x, tiles_y * B, m_blocks), dim3(256), smem, stream, in, CI, wp, in_scale, in_shift, in_relu, out,
+                       out_cs, stat_partial, H, W);
+    P4C_CHECK_LAUNCH("conv_fwd_f32_wide");
+    return P4C_OK;
+}
+
 template <int CI, int KS, int TH>
 static int launch_conv_fwd(const float* in, const float* wp, const float* in_scale, const float* in_shift, int in_relu,
                            const float* bias, float* out, int out_cs, float* stat_partial, int B, int H, int W,
@@ -436,6 +566,8 @@ static int launch_conv_wgrad(const float* in, const float* in_scale, const float
 int conv_fwd_f32(const float* in, int CI, const float* wp, int ks, const float* in_scale, const float* in_shift,
                  int in_relu, const float* bias, float* out, int out_cs, float* stat_partial, int B, int H, int W,
                  int m_blocks, hipStream_t stream) {
+    if (CI > 96 && ks == 3 && !bias)   // (the first convolution of a multi-step input: 128 .. 256 channels, K in 32-channel chunks)
+        return launch_conv_fwd_f32_wide(in, CI, wp, in_scale, in_shift, in_relu, out, out_cs, stat_partial, B, H, W, m_blocks, stream);
 #define P4C_CASE(ci, k)                                                                                              \
     if (CI == ci && ks == k)                                                                                         \
         return launch_conv_fwd<ci, k, 4>(in, wp, in_scale, in_shift, in_relu, bias, out, out_cs, stat_partial, B, H, \

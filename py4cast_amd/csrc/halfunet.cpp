@@ -24,7 +24,6 @@ constexpr int NCONV = 12;    // 3x3 convs: enc k conv j -> 2(k-1)+j-1 ; decoder 
 // prepared-weight cache in the scratch workspace: slot i = conv i forward, NCONV + i = conv i data gradient,
 // 2*NCONV / 2*NCONV + 1 = 1x1 output conv forward / data gradient
 constexpr int NWSLOT = 2 * NCONV + 3;   // forward + data-gradient images of the 3x3 blocks, the two of the 1x1 output conv, the first conv's 64-channel row image
-constexpr int64_t WSLOT_FLOATS = 9 * 96 * 64;
 
 struct Layout {
     int esz;                  // bytes per activation element
@@ -35,6 +34,7 @@ struct Layout {
     // saved workspace: activations (element offsets) then normalisation arrays (float offsets from norm_base bytes)
     int64_t Y[NCONV], P[NLEV], S, act_elems, norm_base, norm[NCONV], saved_bytes;
     // scratch: fp32 region (float offsets) then gradient buffers (element offsets from g_base bytes)
+    int64_t wslot_floats;     // floats per prepared-weight slot: the largest image of the descriptor (9 x 64 x 96 at least)
     int64_t wprep, statp, wgradp[NCONV + 1], ocbp[2], nbwdp, k1i[2][NCONV], k2i[2][NCONV], tickets, f_floats, g_base, G0, G1, G2, TB, DY[2][NCONV], scratch_bytes;
     int G;  // workgroups of the weight-gradient kernels
 };
@@ -43,6 +43,8 @@ inline int conv_level(int i) { return i < 10 ? i / 2 : 0; }
 inline int conv_cin(const p4c_halfunet_desc& d, int i) { return i == 0 ? d.cin : NF; }
 inline int conv_cin_pad(const p4c_halfunet_desc& d, int i) { return i == 0 ? d.cin_pad : NF; }
 inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
+// 64-channel output blocks of the first convolution's data gradient; dx rows are 64 * dx_blocks wide
+inline int dx_blocks(const p4c_halfunet_desc& d) { return d.dx_channels > 64 ? (d.dx_channels + 63) / 64 : 1; }
 
 inline int stat_tiles(int compute, int storage, int CI, int B, int H, int W, int ks = 3) {
     if (compute == P4C_BF16) return conv_bf16_stat_slots(CI, storage, B, H, W, ks);
@@ -75,11 +77,11 @@ int check_desc(const p4c_halfunet_desc* d) {
     P4C_CHECK_ARG(d, "halfunet: null descriptor");
     P4C_CHECK_ARG(d->B > 0 && d->H > 0 && d->W > 0, "halfunet: bad shape");
     P4C_CHECK_ARG(d->H % 16 == 0 && d->W % 16 == 0, "halfunet: H and W must be multiples of 16 (got %dx%d)", d->H, d->W);
-    P4C_CHECK_ARG(d->cin_pad == 32 || d->cin_pad == 64 || d->cin_pad == 96,
-                  "halfunet: cin_pad must be 32, 64 or 96 (got %d)", d->cin_pad);
+    P4C_CHECK_ARG(d->cin_pad > 0 && d->cin_pad <= 256 && d->cin_pad % 32 == 0,
+                  "halfunet: cin_pad must be a multiple of 32 up to 256 (got %d)", d->cin_pad);
     P4C_CHECK_ARG(d->cin > 0 && d->cin <= d->cin_pad, "halfunet: cin out of range");
     P4C_CHECK_ARG(d->cout > 0 && d->cout <= 64, "halfunet: cout must be in 1..64 (got %d)", d->cout);
-    P4C_CHECK_ARG(d->dx_channels >= 0 && d->dx_channels <= 64 && d->dx_channels <= d->cin, "halfunet: bad dx_channels");
+    P4C_CHECK_ARG(d->dx_channels >= 0 && d->dx_channels <= d->cin, "halfunet: bad dx_channels (%d, cin %d)", d->dx_channels, d->cin);
     P4C_CHECK_ARG(d->norm == 0 || (d->norm == 1 && d->groups > 0 && 64 % d->groups == 0), "halfunet: bad norm/groups");
     P4C_CHECK_ARG(d->compute == P4C_F32 || d->compute == P4C_BF16, "halfunet: compute must be P4C_F32 or P4C_BF16");
     P4C_CHECK_ARG(d->dtype == P4C_F32 || d->dtype == P4C_BF16, "halfunet: dtype must be P4C_F32 or P4C_BF16");
@@ -127,13 +129,28 @@ void make_layout(const p4c_halfunet_desc& d, Layout& L) {
     L.G = d.compute == P4C_BF16 ? num_cus() / 2 : num_cus();   // (fp32 matrix cores: the kernel is MFMA-bound, all CUs)
     if (const char* e = diag_env("P4C_WGRAD_G")) { const int g = atoi(e); if (g > 0 && g <= num_cus()) L.G = g; }
     off = 0;
-    L.wprep = off; off += (int64_t)NWSLOT * WSLOT_FLOATS;
+    {   // the first convolution's forward image (9 x 64 x cin_pad) and data-gradient image (9 x 64 dx_blocks x 64) may be the largest.
+        // Sized from cin alone (dx_channels <= cin): descriptors of one network that differ in dx_channels only -- a rollout's step 0
+        // runs with dx_channels = 0 on weights prepared under the other steps' descriptor -- must share one slot layout.
+        int64_t m = 96;
+        if (d.cin_pad > m) m = d.cin_pad;
+        if (64 * ((d.cin + 63) / 64) > m) m = 64 * ((d.cin + 63) / 64);
+        L.wslot_floats = 9 * 64 * m;
+    }
+    L.wprep = off; off += (int64_t)NWSLOT * L.wslot_floats;
     const int64_t tps = conv_tiles_per_sample(d.H, d.W);
     {
         int64_t slots = tps > 4 * (int64_t)num_cus() ? tps : 4 * (int64_t)num_cus();
         for (int k = 0; k < NLEV; ++k) {   // (the row-streaming kernel's slot count depends on the level's shape)
             const int64_t s = d.compute == P4C_BF16 ? conv_bf16_stat_slots(NF, d.dtype, d.B, L.Hk[k], L.Wk[k], 3) : 0;
             if (s > slots) slots = s;
+        }
+        // the first convolution: its own kernel's slots (the K-chunked kernel beyond 96 channels), or the 65..72-channel tail's
+        const int64_t s0 = stat_tiles(d.compute, d.dtype, d.cin_pad, d.B, d.H, d.W);
+        if (s0 > slots) slots = s0;
+        if (first_conv_split_ok(d.compute, d.dtype, d.cin, d.cin_pad, d.B, d.H, d.W)) {
+            const int64_t st = first_conv_tail_slots(d.B, d.H, d.W);
+            if (st > slots) slots = st;
         }
         L.statp = off; off += (int64_t)d.B * slots * 128;
     }
@@ -195,7 +212,7 @@ inline Norm norm_at(const WS& ws, int i, int B) {
     return {p, p + (int64_t)B * NF, p + 2 * (int64_t)B * NF, p + 3 * (int64_t)B * NF};
 }
 
-inline void* wslot(const WS& ws, int slot) { return ws.f(ws.L.wprep + (int64_t)slot * WSLOT_FLOATS); }
+inline void* wslot(const WS& ws, int slot) { return ws.f(ws.L.wprep + (int64_t)slot * ws.L.wslot_floats); }
 
 // (re)prepares the weight operand streams: which = 1 forward orientation, 2 data-gradient orientation, 3 both
 int prepare_weights(const p4c_halfunet_desc& d, const WS& ws, const float* params, int which, hipStream_t st) {
@@ -205,8 +222,8 @@ int prepare_weights(const p4c_halfunet_desc& d, const WS& ws, const float* param
     pb.bf16 = d.compute == P4C_BF16;
     for (int i = 0; i < NCONV; ++i) {
         if (which & 1) pb.job[pb.n++] = {params + L.w[i], wslot(ws, i), NF, conv_cin(d, i), 9, 0, 64, conv_cin_pad(d, i)};
-        // data gradient: M = input channel (the first 64 at most: dx_channels <= 64), K = output channel, taps flipped
-        if (which & 2) pb.job[pb.n++] = {params + L.w[i], wslot(ws, NCONV + i), NF, conv_cin(d, i), 9, 1, 64, NF};
+        // data gradient: M = input channel (the first 64 * dx_blocks of the first convolution's), K = output channel, taps flipped
+        if (which & 2) pb.job[pb.n++] = {params + L.w[i], wslot(ws, NCONV + i), NF, conv_cin(d, i), 9, 1, i == 0 ? 64 * dx_blocks(d) : 64, NF};
     }
     if (which & 1) pb.job[pb.n++] = {params + L.wout, wslot(ws, 2 * NCONV), d.cout, NF, 1, 0, 64, NF};
     // the first convolution as a 64-channel row launch + tail (conv_thin.hip): the row kernel's image of input channels 0..63
@@ -410,8 +427,11 @@ int conv_block_bwd(const p4c_halfunet_desc& d, const WS& ws, int i, const void* 
     static const bool nb_all = [] { const char* e = diag_env("P4C_NB_ALL"); return !(e && e[0] == '0'); }();
     // (the first convolution's 96-channel input: its weight gradient runs as a 64-channel chunk + a half-empty one, both on the
     // role-split kernel -- conv_wgrad_bf16_takes_nb -- and its data gradient, state channels only, is a 64 -> 64 launch)
+    // (beyond 96 input channels -- num_input_steps >= 2 -- the first block's pass 2 stays a norm_bwd_apply launch: its weight gradient
+    // runs in up to four chunks and its data gradient in up to four output blocks, all reading the one dY map)
     const bool nbf = (!dgrad_takes_pass1 || nb_all) && d.compute == P4C_BF16 && conv_bf16_norm_bwd_fused_ok(d.dtype, NF, d.B, H, W) &&
-                     (cip == NF || (nb_all && diag_env("P4C_NO_NB0") == nullptr && conv_wgrad_bf16_takes_nb(d.dtype, cip, 3, d.B)));
+                     (i > 0 || dx_blocks(d) == 1) &&
+                     (cip == NF || (cip <= 96 && nb_all && diag_env("P4C_NO_NB0") == nullptr && conv_wgrad_bf16_takes_nb(d.dtype, cip, 3, d.B)));
     P4C_TRY(norm_bwd(d.dtype, g, ws.act(L.Y[i]), nm.scale, nm.shift, nm.mean, nm.rstd, params + L.gamma[i], 1, d.B,
                      (int64_t)H * W, d.norm, d.groups, stats_training, ws.f(L.nbwdp), ws.f(L.k1i[g_side.calls & 1][i]), ws.f(L.k2i[g_side.calls & 1][i]),
                      grads + L.gamma[i], grads + L.beta[i], nbf ? nullptr : g, st, pre_nblk, bwd_ticket(d, ws), pre_finalized));
@@ -460,8 +480,22 @@ int conv_block_bwd(const p4c_halfunet_desc& d, const WS& ws, int i, const void* 
                           conv_bf16_bwd_stats_ok(d.dtype, d.B, H, W);
         const RingBwdStats bst{in, in_norm ? in_norm->scale : nullptr, in_norm ? in_norm->shift : nullptr,
                                in_norm ? in_norm->mean : nullptr, in_norm ? in_norm->rstd : nullptr};
-        P4C_TRY(conv_fwd(d.compute, d.dtype, g, NF, wslot(ws, NCONV + i), 3, nullptr, nullptr, 0, din, 64, fuse ? ws.f(L.nbwdp) : nullptr,
-                         d.B, H, W, 1, st, nullptr, fuse ? &bst : nullptr, fuse ? next_nblk : nullptr, nbf ? &nb : nullptr));
+        const int nblk = i == 0 ? dx_blocks(d) : 1;
+        if (nblk == 1) {
+            P4C_TRY(conv_fwd(d.compute, d.dtype, g, NF, wslot(ws, NCONV + i), 3, nullptr, nullptr, 0, din, 64, fuse ? ws.f(L.nbwdp) : nullptr,
+                             d.B, H, W, 1, st, nullptr, fuse ? &bst : nullptr, fuse ? next_nblk : nullptr, nbf ? &nb : nullptr));
+        } else if (d.compute == P4C_BF16 && conv_bf16_is_rows(d.dtype, NF, 3, 1, 64 * nblk, d.B, H, W)) {
+            // the first convolution's data gradient for more than 64 input channels (num_input_steps >= 2): one row-kernel launch per
+            // 64-channel output block, each writing its columns of the 64 * nblk wide dx rows (block m's image is rows 64m .. 64m+63
+            // of the M_pad = 64 * nblk data-gradient image)
+            const int64_t wblk = (int64_t)9 * 64 * 64 * (d.compute == P4C_BF16 ? 2 : 4);
+            for (int m = 0; m < nblk; ++m)
+                P4C_TRY(conv_fwd(d.compute, d.dtype, g, NF, (char*)wslot(ws, NCONV + i) + m * wblk, 3, nullptr, nullptr, 0,
+                                 (char*)din + (int64_t)m * 64 * L.esz, 64 * nblk, nullptr, d.B, H, W, 1, st));
+        } else {
+            P4C_TRY(conv_fwd(d.compute, d.dtype, g, NF, wslot(ws, NCONV + i), 3, nullptr, nullptr, 0, din, 64 * nblk, nullptr, d.B, H, W,
+                             nblk, st));
+        }
     }
     return P4C_OK;
 }

@@ -668,6 +668,52 @@ extern "C" int p4c_build_x_bwd_masked(const void* dx, int dx_dtype, int c_pad, f
     return build_x_bwd_impl(dx, dx_dtype, c_pad, dprev, B, T_in, N, F, BlockMask{block_selected, W, block_h, block_w}, stream);
 }
 
+// ------------------------------------------------------------------------------ state gradients of a rollout with num_input_steps >= 2
+// out[b,n,f] = sum_k src_k[b * bs_k + n * cs_k + off_k + f], sources in the given (fixed) order: the gradient of one state slot of the
+// reverse sweep -- the prediction's own gradient, the residual path of the next AR step, and the matching F-channel block of the input
+// gradient (dx) of every later step whose input window holds the state.
+constexpr int SUM_MAX_SRC = 8;
+struct SumSrcs {
+    const void* p[SUM_MAX_SRC];
+    int64_t bs[SUM_MAX_SRC];
+    int cs[SUM_MAX_SRC], off[SUM_MAX_SRC], bf16[SUM_MAX_SRC];
+    int n;
+};
+
+__global__ void __launch_bounds__(256) sum_state_grads_kernel(float* __restrict__ out, int64_t out_bs, SumSrcs s, int B, int64_t N, int F) {
+    const int64_t rows = (int64_t)B * N;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows * F; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / F;
+        const int f = (int)(i - r * F);
+        const int64_t b = r / N, n = r - b * N;
+        float acc = 0.f;
+        for (int k = 0; k < s.n; ++k) {
+            const int64_t idx = b * s.bs[k] + n * s.cs[k] + s.off[k] + f;
+            acc += s.bf16[k] ? (float)reinterpret_cast<const __bf16*>(s.p[k])[idx] : reinterpret_cast<const float*>(s.p[k])[idx];
+        }
+        out[b * out_bs + n * F + f] = acc;
+    }
+}
+
+extern "C" int p4c_sum_state_grads(float* out, int64_t out_bs, int n_src, const void* const* src, const int64_t* src_bs, const int* src_cs,
+                                   const int* src_off, const int* src_dtype, int B, int64_t N, int F, p4c_stream_t stream) {
+    P4C_CHECK_ARG(out && B > 0 && N > 0 && F > 0 && out_bs >= N * F, "p4c_sum_state_grads: bad output");
+    P4C_CHECK_ARG(n_src >= 1 && n_src <= SUM_MAX_SRC && src && src_bs && src_cs && src_off && src_dtype,
+                  "p4c_sum_state_grads: 1..%d sources", SUM_MAX_SRC);
+    SumSrcs s{};
+    s.n = n_src;
+    for (int k = 0; k < n_src; ++k) {
+        P4C_CHECK_ARG(src[k] && src_off[k] >= 0 && src_cs[k] >= src_off[k] + F && src_bs[k] >= N * src_cs[k] &&
+                          (src_dtype[k] == P4C_F32 || src_dtype[k] == P4C_BF16),
+                      "p4c_sum_state_grads: bad source %d", k);
+        s.p[k] = src[k]; s.bs[k] = src_bs[k]; s.cs[k] = src_cs[k]; s.off[k] = src_off[k]; s.bf16[k] = src_dtype[k] == P4C_BF16;
+    }
+    const int grid = stream_grid((int64_t)B * N * F, 64);   // (one element per lane)
+    hipLaunchKernelGGL(sum_state_grads_kernel, dim3(grid), dim3(256), 0, as_stream(stream), out, out_bs, s, B, N, F);
+    P4C_CHECK_LAUNCH("p4c_sum_state_grads");
+    return P4C_OK;
+}
+
 extern "C" int p4c_ar_update_fwd(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs,
                                  const float* border_state, int64_t border_bs, const float* std, const float* mean,
                                  const float* border_mask, const float* interior_mask, float* new_state,

@@ -29,6 +29,7 @@ from ._lib_model import HalfUNetDesc
 from .base import ModelABC, ModelType
 
 NF = 64
+MAX_CIN = 256   # input channels of the fused plan (cin_pad: a multiple of 32 up to 256)
 BLOCKS = ("enc1", "enc2", "enc3", "enc4", "enc5", "decoder")
 BLOCK_ATTR = ("encoder1", "encoder2", "encoder3", "encoder4", "encoder5", "decoder")
 
@@ -84,7 +85,7 @@ class _HalfUNetFn(torch.autograd.Function):
         flat = model._flat_params()
         _, scratch = model._workspaces(desc, x.device)
         gflat = torch.zeros_like(flat)
-        dx = torch.empty_like(dy) if desc.dx_channels > 0 else None
+        dx = torch.empty(dy.shape[:-1] + (model.dx_width,), dtype=dy.dtype, device=dy.device) if desc.dx_channels > 0 else None
         L.call("p4c_halfunet_backward", ctypes.byref(desc), L.ptr(x), L.ptr(flat), L.ptr(dy), L.ptr(dx), L.ptr(gflat),
                L.ptr(saved), L.ptr(scratch), int(ctx.training), L.stream(x.device))
         dxp = None
@@ -133,16 +134,19 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         if not self.module_path:
             if out_channels > NF:
                 unsupported.append(f"out_channels={out_channels} > 64")
-            if pad32(in_channels) > 96:
-                unsupported.append(f"in_channels={in_channels} > 96")
+            if pad32(in_channels) > MAX_CIN:
+                unsupported.append(f"in_channels={in_channels} > {MAX_CIN}")
         if unsupported:
             raise NotImplementedError("HalfUNetMI355X: unsupported settings: " + ", ".join(unsupported))
         self.cin_pad = pad32(in_channels)
-        self.dx_channels = min(in_channels, NF)  # gradient wrt the leading (previous-state) channels
+        # gradient wrt the leading (previous-state) channels: all of them beyond 96 input channels (num_input_steps >= 2 at the
+        # benchmark's widths); AutoRegressiveLightning raises it to num_input_steps * weather_dim (grad_input_channels)
+        self.dx_channels = min(in_channels, NF) if self.cin_pad <= 96 else in_channels
         self.compute_dtype = torch.float32 if settings.compute_dtype == "f32" else torch.bfloat16
         self.act_dtype = torch.float32 if act == "f32" else torch.bfloat16  # dtype of x / y / dy / dx handed to the plan
         self.timed_entry_points = ("p4c_halfunet_forward", "p4c_halfunet_backward", "p4c_build_x",
-                                   "p4c_ar_update_loss_fwd", "p4c_ar_update_loss_fwd_next", "p4c_ar_update_loss_bwd")
+                                   "p4c_ar_update_loss_fwd", "p4c_ar_update_loss_fwd_next", "p4c_ar_update_loss_bwd",
+                                   "p4c_sum_state_grads")
 
         self.use_ghost = bool(settings.use_ghost)
         if self.module_path:
@@ -316,6 +320,25 @@ class HalfUNetMI355X(ModelABC, nn.Module):
     def settings(self):
         return self._settings
 
+    @property
+    def grad_input_channels(self) -> int:
+        """Leading input channels whose gradient the backward returns (the past states a rollout differentiates through); the
+        gradient of the channels beyond them (statics, forcings, padding) is returned as zeros."""
+        return self.in_channels if self.module_path else self.dx_channels
+
+    @grad_input_channels.setter
+    def grad_input_channels(self, n: int):
+        if self.module_path:
+            return   # (the module path differentiates every input channel)
+        if not 0 <= n <= self.in_channels:
+            raise ValueError(f"HalfUNetMI355X: grad_input_channels={n} outside 0..{self.in_channels}")
+        self.dx_channels = int(n)
+
+    @property
+    def dx_width(self) -> int:
+        """Channels of the plan's dx rows: 64 per started block of 64 gradient channels (64 up to 64)."""
+        return NF * max(1, (self.dx_channels + NF - 1) // NF)
+
     # ---------------------------------------------------------------- flat views
     def _ordered_params(self):
         out = []
@@ -406,7 +429,7 @@ class HalfUNetMI355X(ModelABC, nn.Module):
                             L.F32 if s.compute_dtype == "f32" else L.BF16, 0)
 
     def _workspaces(self, desc, device):
-        key = (desc.B, desc.H, desc.W, str(device))
+        key = (desc.B, desc.H, desc.W, desc.dx_channels, str(device))
         hit = self._scratch.get(key)
         if hit is None:
             sb, cb = ctypes.c_size_t(), ctypes.c_size_t()
@@ -456,13 +479,19 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         Whole training/validation rollout of AutoRegressiveLightning._common_step (lightning.py:565-662) as ONE
         autograd node: per AR step K1 (build x, padded layout) -> HalfUNet plan -> fused state update + border
         forcing + weighted loss, and the matching reverse sweep (BPTT) enqueued back to back from Python with no
-        autograd bookkeeping in between.  Returns the (B,T,*S,F) prediction, with ``fused_loss`` (B,T) attached
+        autograd bookkeeping in between.  num_input_steps = T_in >= 2: step i's input is the window of states i .. i+T_in-1 of a
+        (T_in + T)-slot state buffer, and the reverse sweep sums each state's gradient (its prediction's, the next step's residual
+        path, the matching block of the input gradient of the next T_in steps) in HIP.  Returns the (B,T,*S,F) prediction, with ``fused_loss`` (B,T) attached
         when the configured loss is a single WeightedLoss.  Returns None when the configuration is not covered
         (the caller then takes the generic per-op path).
         """
         from .losses import WeightedLoss
 
-        if batch.num_input_steps != 1 or batch.inputs.tensor.dim() != 5:
+        if batch.inputs.tensor.dim() != 5:
+            return None
+        T_in, F = batch.inputs.tensor.shape[1], batch.inputs.tensor.shape[-1]
+        if T_in > 1 and (T_in * F + lm.grid_static_features.shape[-1] + batch.forcing.tensor.shape[-1] + int(lm.mask_on_nan)
+                         != self.in_channels):
             return None
         if any(self.padding_for(batch.inputs.tensor.shape[2], batch.inputs.tensor.shape[3])):
             return None   # auto-padded grids take the generic per-step path (forward pads and crops around the plan)
@@ -597,7 +626,7 @@ class _NativeRolloutFn(torch.autograd.Function):
         L.require_cuda(inputs, forcing, outputs)
         dev = inputs.device
         B, T = outputs.shape[0], outputs.shape[1]
-        H, W, F = inputs.shape[2], inputs.shape[3], inputs.shape[4]
+        T_in, H, W, F = inputs.shape[1], inputs.shape[2], inputs.shape[3], inputs.shape[4]
         N = H * W
         Fs, Ff = statics.shape[-1], forcing.shape[-1]
         inputs, forcing, outputs = inputs.float().contiguous(), forcing.float().contiguous(), outputs.float().contiguous()
@@ -605,6 +634,10 @@ class _NativeRolloutFn(torch.autograd.Function):
         sbs = 0 if st.stride(0) == 0 else N * Fs
         st = st[0].contiguous() if sbs == 0 else st.contiguous()
         desc = model._desc(B, H, W)
+        if T_in > 1:
+            desc.dx_channels = T_in * F   # the window of past states: the gradient the sweep reads
+        elif desc.dx_channels > NF:
+            desc.dx_channels = F   # one input state (F <= out_channels <= 64): its gradient is all the sweep reads
         flat = model._flat_params()
         saved_bytes, scratch = model._workspaces(desc, dev)
         cpad = model.cin_pad
@@ -616,8 +649,12 @@ class _NativeRolloutFn(torch.autograd.Function):
         # state buffer: slot 0 = input state, slot i+1 = new state of AR step i (= prediction[:, i])
         # (slot 0 is never written: AR step 0 reads the batch's input state where it lies -- every kernel takes the previous
         # state's batch stride separately -- which saves a 126 MB copy per rollout at the benchmark size)
-        states = torch.empty(B, T + 1, H, W, F, dtype=torch.float32, device=dev)
-        sbs_state = (T + 1) * N * F
+        # (T_in >= 2: slots 0 .. T_in-1 hold the input states, copied once; slot T_in + i = new state of AR step i, and the input of
+        # step i is the window of slots i .. i+T_in-1)
+        states = torch.empty(B, T_in + T, H, W, F, dtype=torch.float32, device=dev)
+        if T_in > 1:
+            states[:, :T_in].copy_(inputs)
+        sbs_state = (T_in + T) * N * F
         sbs_input = inputs.shape[1] * N * F
         loss = torch.empty(B, T, dtype=torch.float32, device=dev)
         ws = torch.empty(L.lib().p4c_loss_workspace_bytes(B, 1, N, 1) // 4, dtype=torch.float32, device=dev)
@@ -631,21 +668,24 @@ class _NativeRolloutFn(torch.autograd.Function):
         desc.weights_prepared = 1
         # "feed next step" fused: the update kernel of step i also writes step i+1's network input (new state | statics |
         # next forcing | padding), so only step 0 runs p4c_build_x.  (The NaN-mask input channel needs p4c_build_x.)
+        # (T_in >= 2: the next input is a window of several states, built by p4c_build_x; the update kernels run without x_next)
+        feed = T_in == 1
         lanes = 1
         while lanes < F // 4:
             lanes *= 2  # lanes per grid point of the 16-byte update kernel; each also owns one tail quad of x_next
-        v4_next = ((not mask_on_nan) and F % 4 == 0 and F <= 64 and Fs % 4 == 0 and cpad % 4 == 0
-                   and cpad // 4 - F // 4 <= lanes)
+        v4_next = ((not mask_on_nan) and F % 4 == 0 and F <= 64
+                   and (not feed or (Fs % 4 == 0 and cpad % 4 == 0 and cpad // 4 - F // 4 <= lanes)))
         # any other feature count (the shipped Titan configuration has 21 features): the flat kernels of csrc/losses.hip -- (N, F)
         # arrays streamed flat, the network's row tensors through LDS tiles -- take the same fused step
         esz = 2 if adt == torch.bfloat16 else 4
         flat_next = ((not mask_on_nan) and F <= 64 and (N * F) % 4 == 0 and (cpad * esz) % 16 == 0 and cpad <= 256
                      and L.diag_switch("P4C_NO_FLAT_STEP") != "1")
-        fuse_next = v4_next or flat_next
+        step_capable = v4_next or flat_next
+        fuse_next = feed and step_capable
         x_next = None
         # bf16 flavour, training: the update kernel also saves the loss gradient of every element as bf16 rows and the backward reads
         # those instead of the new state and the target (480 -> 120 bytes per grid point; P4C_SAVE_LOSS_GRAD=0: recompute)
-        save_lg = (keep_saved and adt == torch.bfloat16 and fuse_next and mask_mode == L.MASK_NONE
+        save_lg = (keep_saved and adt == torch.bfloat16 and step_capable and mask_mode == L.MASK_NONE
                    and L.diag_switch("P4C_SAVE_LOSS_GRAD") != "0")
         lgrads = torch.empty(T, B, N, F, dtype=torch.bfloat16, device=dev) if save_lg else None
         # bf16 flavour: the network's 1x1 output convolution runs INSIDE the AR step's kernel (p4c_out_conv_update_loss_fwd: y is
@@ -658,26 +698,30 @@ class _NativeRolloutFn(torch.autograd.Function):
             desc_fwd = HalfUNetDesc.from_buffer_copy(desc)
             desc_fwd.skip_out_conv = 1
         for i in range(T):
-            prev, sbs_prev = (inputs[:, 0], sbs_input) if i == 0 else (states[:, i], sbs_state)
+            if feed:
+                prev, sbs_prev = (inputs[:, 0], sbs_input) if i == 0 else (states[:, i], sbs_state)
+            else:
+                prev, sbs_prev = states[:, i + T_in - 1], sbs_state
             if x_next is not None:
                 x = x_next
             else:
                 x = torch.empty(B, H, W, cpad, dtype=adt, device=dev)
-                L.call("p4c_build_x", L.ptr(prev), sbs_prev, N * F, L.ptr(st), sbs, L.ptr(forcing[:, i]), T * N * Ff,
-                       L.ptr(x), acode, cpad, B, 1, N, F, Fs, Ff, mask_on_nan, 0, stream)
+                win, sbs_win = (prev, sbs_prev) if feed else (states[:, i], sbs_state)
+                L.call("p4c_build_x", L.ptr(win), sbs_win, N * F, L.ptr(st), sbs, L.ptr(forcing[:, i]), T * N * Ff,
+                       L.ptr(x), acode, cpad, B, T_in, N, F, Fs, Ff, mask_on_nan, 0, stream)
             if saved is None or keep_saved:
                 saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
             L.call("p4c_halfunet_forward", ctypes.byref(desc_fwd), L.ptr(x), L.ptr(flat), L.ptr(model._running),
                    None if fused_tail else L.ptr(y), L.ptr(saved), L.ptr(scratch), int(training), stream)
             if fused_tail:
-                last = i + 1 == T
+                last = i + 1 == T or not feed
                 x_next = None if last else torch.empty(B, H, W, cpad, dtype=adt, device=dev)
                 ta, tsc, tsh, tw = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
                 L.call("p4c_halfunet_tail", ctypes.byref(desc_fwd), L.ptr(flat), L.ptr(saved), ctypes.byref(ta), ctypes.byref(tsc),
                        ctypes.byref(tsh), ctypes.byref(tw))
                 L.call("p4c_out_conv_update_loss_fwd", ta, tsc, tsh, tw, model.out_channels,
                        L.ptr(prev), sbs_prev, L.ptr(outputs[:, i]), T * N * F, L.ptr(std), L.ptr(mean),
-                       L.ptr(border_flat if force_border else None), L.ptr(interior_flat), L.ptr(states[:, i + 1]), sbs_state,
+                       L.ptr(border_flat if force_border else None), L.ptr(interior_flat), L.ptr(states[:, i + T_in]), sbs_state,
                        L.ptr(weights), num_interior, L.ptr(count), kind, L.ptr(loss[:, i]), T, L.ptr(ws), B, N, F, 1.0,
                        L.ptr(x_next), cpad, L.ptr(st), sbs, Fs, L.ptr(None if last else forcing[:, i + 1]), T * N * Ff, Ff,
                        L.ptr(lgrads[i]) if save_lg else None, N * F, stream)
@@ -687,11 +731,11 @@ class _NativeRolloutFn(torch.autograd.Function):
                 continue
             step_args = (L.ptr(prev), sbs_prev, L.ptr(y), acode, NF, L.ptr(outputs[:, i]),
                          T * N * F, L.ptr(std), L.ptr(mean), L.ptr(border_flat if force_border else None), L.ptr(interior_flat),
-                         L.ptr(states[:, i + 1]), sbs_state, L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode,
+                         L.ptr(states[:, i + T_in]), sbs_state, L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode,
                          L.ptr(loss[:, i]), T, L.ptr(ws), B, N, F, 1.0)
             x_next = None
             if save_lg:
-                last = i + 1 == T
+                last = i + 1 == T or not feed
                 x_next = None if last else torch.empty(B, H, W, cpad, dtype=adt, device=dev)
                 L.call("p4c_ar_update_loss_fwd_next_saved", *step_args, L.ptr(x_next), cpad, L.ptr(st), sbs, Fs,
                        L.ptr(None if last else forcing[:, i + 1]), T * N * Ff, Ff, L.ptr(lgrads[i]), N * F, stream)
@@ -706,10 +750,11 @@ class _NativeRolloutFn(torch.autograd.Function):
                 saveds.append(saved)
         ctx.model, ctx.desc, ctx.training = model, desc, training
         ctx.meta = (B, T, H, W, F, force_border, num_interior, kind, mask_mode)
+        ctx.T_in = T_in
         ctx.tensors = (states, outputs, std, interior_flat, weights, count, xs, saveds)
         ctx.lgrads = lgrads
         ctx.set_materialize_grads(False)
-        pred = states[:, 1:]
+        pred = states[:, T_in:]
         return pred, loss
 
     @staticmethod
@@ -726,10 +771,9 @@ class _NativeRolloutFn(torch.autograd.Function):
         gflat = target if target is not None else torch.zeros_like(flat)
         adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
         dy = torch.empty(B, H, W, NF, dtype=adt, device=dev)
-        dx = torch.empty(B, H, W, NF, dtype=adt, device=dev)
+        dx = torch.empty(B, H, W, NF, dtype=adt, device=dev) if ctx.T_in == 1 else None
         dprev = torch.empty(B, H, W, F, dtype=torch.float32, device=dev)
         gl = g_loss.contiguous().float() if g_loss is not None else None
-        sbs_state = (T + 1) * N * F
         # the scratch workspace may have served another call since forward: prepare again (one launch per sweep)
         L.call("p4c_halfunet_prepare_weights", ctypes.byref(desc), L.ptr(flat), L.ptr(scratch), stream)
         desc0 = HalfUNetDesc.from_buffer_copy(desc)
@@ -744,7 +788,12 @@ class _NativeRolloutFn(torch.autograd.Function):
             L.call("p4c_side_stream_defer", 1)
         ok = False
         try:
-            out = _NativeRolloutFn._sweep(ctx, g_pred, gl, dy, dx, dprev, gflat, flat, scratch, desc, desc0, stream, target, defer)
+            if ctx.T_in > 1:
+                out = _NativeRolloutFn._sweep_window(ctx, g_pred, gl, dy, dprev, gflat, flat, scratch, desc, desc0, stream, target,
+                                                     defer)
+            else:
+                out = _NativeRolloutFn._sweep(ctx, g_pred, gl, dy, dx, dprev, gflat, flat, scratch, desc, desc0, stream, target,
+                                              defer)
             ok = True
             return out
         finally:
@@ -800,6 +849,72 @@ class _NativeRolloutFn(torch.autograd.Function):
                 xs[i] = None
                 saveds[i] = None
         if target is not None:  # already accumulated into param.grad
+            return (None,) * (17 + len(model._param_slices))
+        grads = tuple(gflat[o : o + n].view(s) for (o, n, s) in model._param_slices)
+        return (None,) * 17 + grads
+
+    @staticmethod
+    def _sweep_window(ctx, g_pred, gl, dy, dprev, gflat, flat, scratch, desc, desc0, stream, target, defer):
+        """Reverse sweep of a rollout with T_in >= 2 input states.  State slot s = i + T_in (the new state of step i) collects, summed
+        in one launch (p4c_sum_state_grads) before step i's update backward: its prediction's gradient, the residual path of step i+1
+        (whose previous state it is: dprev), and block s - k of the input gradient dx_k of every step k in i+1 .. i+T_in whose window
+        holds it.  dx_k lives in a ring of T_in + 1 buffers (written at step k, last read at step k - T_in).  Step 0's window is all
+        input data: no data gradient there."""
+        model = ctx.model
+        B, T, H, W, F, force_border, num_interior, kind, mask_mode = ctx.meta
+        T_in = ctx.T_in
+        states, outputs, std, interior_flat, weights, count, xs, saveds = ctx.tensors
+        dev = states.device
+        N = H * W
+        sbs_state = (T_in + T) * N * F
+        adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
+        dxw = NF * ((desc.dx_channels + NF - 1) // NF)
+        nring = T_in + 1
+        dxs = [torch.empty(B, H, W, dxw, dtype=adt, device=dev) for _ in range(min(nring, T))]
+        gsum = torch.empty(B, H, W, F, dtype=torch.float32, device=dev)
+        gp = g_pred.float().contiguous() if g_pred is not None else None
+        srcs = (ctypes.c_void_p * 8)()
+        sbs, scs, soff, sdt = (ctypes.c_int64 * 8)(), (ctypes.c_int * 8)(), (ctypes.c_int * 8)(), (ctypes.c_int * 8)()
+        for i in range(T - 1, -1, -1):
+            n = 0
+            parts = []
+            if gp is not None:
+                parts.append((gp[:, i], gp.stride(0), F, 0, L.F32))
+            if i + 1 < T:
+                parts.append((dprev, N * F, F, 0, L.F32))
+            s = i + T_in
+            for k in range(i + 1, min(i + T_in, T - 1) + 1):
+                parts.append((dxs[k % nring], N * dxw, dxw, (s - k) * F, acode))
+            for (t, bs, cs, off, dt) in parts:
+                srcs[n], sbs[n], scs[n], soff[n], sdt[n] = t.data_ptr(), bs, cs, off, dt
+                n += 1
+            g_next = None
+            if n:
+                L.call("p4c_sum_state_grads", L.ptr(gsum), N * F, n, srcs, sbs, scs, soff, sdt, B, N, F, stream)
+                g_next = gsum
+            if ctx.lgrads is not None:
+                L.call("p4c_ar_update_loss_bwd_saved", L.ptr(g_next), N * F, None, acode, NF,
+                       L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(ctx.lgrads[i]), N * F, L.ptr(std), L.ptr(interior_flat),
+                       int(force_border), L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF,
+                       L.ptr(dprev) if i > 0 else None, N * F, B, N, F, 1.0, stream)
+            else:
+                L.call("p4c_ar_update_loss_bwd", L.ptr(g_next), N * F, None, acode, NF,
+                       L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(states[:, s]), sbs_state, L.ptr(outputs[:, i]),
+                       T * N * F, L.ptr(std), L.ptr(interior_flat), int(force_border), L.ptr(weights), num_interior,
+                       L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF, L.ptr(dprev) if i > 0 else None, N * F, B, N, F,
+                       1.0, stream)
+            d = desc if i > 0 else desc0
+            L.call("p4c_halfunet_backward", ctypes.byref(d), L.ptr(xs[i]), L.ptr(flat), L.ptr(dy),
+                   L.ptr(dxs[i % nring]) if i > 0 else None, L.ptr(gflat), L.ptr(saveds[i]), L.ptr(scratch), int(ctx.training), stream)
+            if not defer:
+                xs[i] = None
+                saveds[i] = None
+        if defer:
+            L.call("p4c_side_stream_join", stream)
+            for i in range(T):
+                xs[i] = None
+                saveds[i] = None
+        if target is not None:
             return (None,) * (17 + len(model._param_slices))
         grads = tuple(gflat[o : o + n].view(s) for (o, n, s) in model._param_slices)
         return (None,) * 17 + grads

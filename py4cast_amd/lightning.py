@@ -230,6 +230,10 @@ class AutoRegressiveLightning(_Base):
         )
         if channels_last:
             self.model = self.model.to(memory_format=torch.channels_last)
+        # models that return the input gradient of the leading channels only (the HIP HalfUNet): every past state is differentiated
+        state_channels = num_input_steps * dataset_info.weather_dim
+        if not ds and hasattr(self.model, "grad_input_channels") and state_channels > self.model.grad_input_channels:
+            self.model.grad_input_channels = state_channels
 
         if self.model.model_type == ModelType.GRAPH:  # lightning.py:285-289
             statics.grid_statics.flatten_("ngrid", 0, 1)

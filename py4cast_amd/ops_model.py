@@ -32,7 +32,8 @@ def conv_tiles(B, H, W, CI=64, compute="f32", storage=None, ks=3):
 def conv_fwd(x: torch.Tensor, wprep: torch.Tensor, ks: int, m_blocks: int = 1, in_scale: Optional[torch.Tensor] = None,
              in_shift: Optional[torch.Tensor] = None, in_relu: bool = False, bias: Optional[torch.Tensor] = None,
              want_stats: bool = False, compute="f32"):
-    """x: (B,H,W,CI) fp32 (or bf16 with compute="bf16") NHWC, CI in {32,64,96} -> (B,H,W,64*m_blocks) of x's dtype
+    """x: (B,H,W,CI) fp32 (or bf16 with compute="bf16") NHWC, CI in {32,64,96} (or, ks = 3 without bias, any
+    multiple of 32 up to 256) -> (B,H,W,64*m_blocks) of x's dtype
     [+ per-tile channel sums]."""
     L.require_cuda(x)
     B, H, W, CI = x.shape
