@@ -884,6 +884,33 @@ int p4c_bnorm_finalize(const float* partial, int nblk, double count, int C, cons
                        float momentum, float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
                        int64_t* num_batches_tracked, p4c_stream_t stream);
 
+/* ====================================================================================
+ * UNet (mfai's UNet: model_name UNet / UNetMI355X, py4cast_amd/unet.py).
+ * ==================================================================================== */
+/* 2x2 / stride-2 transposed convolution (torch.nn.ConvTranspose2d(Cin, Cout, 2, stride=2), weight (Cin, Cout, 2, 2) fp32) as GEMMs with
+ * sub-pixel addressing on the kernels of p4c_gemm_nt / p4c_gemm_tn.  x: (B, H, W) pixels of Cin bf16 channels, pixel stride ldx; the
+ * up-sampled map: (B, 2H, 2W) pixels of Cout channels, pixel stride ldo / ldd (a column range of a wider buffer: the concatenation).
+ * Images: fwd [4 Cout][Cin] (row (2 dy + dx) Cout + co), dgrad [Cin][4 Cout]; Cin, Cout multiples of 8.  Workspaces:
+ * p4c_gemm_nt_workspace_bytes(B H W, 4 Cout, Cin) (fwd), (B H W, Cin, 4 Cout) (dgrad), p4c_gemm_tn_workspace_bytes(B H W, 4 Cout, Cin)
+ * (wgrad).  wgrad: dw in the torch layout (Cin, Cout, 2, 2), db (Cout) or NULL; accumulate != 0: ADD into them. */
+int p4c_upconv_prep_weight(const float* w, int Cin, int Cout, void* fwd, void* dgrad, p4c_stream_t stream);
+int p4c_gemm_upconv_fwd(const void* x, int64_t ldx, const void* fwd_img, const float* bias, int B, int H, int W, int Cin, int Cout,
+                        void* out, int64_t ldo, void* workspace, p4c_stream_t stream);
+int p4c_gemm_upconv_dgrad(const void* dup, int64_t ldd, const void* dgrad_img, int B, int H, int W, int Cin, int Cout, void* dx,
+                          int64_t ldx, void* workspace, p4c_stream_t stream);
+int p4c_gemm_upconv_wgrad(const void* dup, int64_t ldd, const void* x, int64_t ldx, int B, int H, int W, int Cin, int Cout, float* dw,
+                          float* db, int accumulate, void* workspace, p4c_stream_t stream);
+/* Encoder block tail: skip[p][c] (pixel stride ld) = relu(y * scale[c] + shift[c]) rounded to the storage type, pool = 2x2 / stride-2 max
+ * of those values; y (B, H, W, C) contiguous, H and W even, C a multiple of 4 up to 1024, dtype P4C_F32 | P4C_BF16.
+ * Backward: dz = (dskip + dpool routed to the window's first maximum) * relu'(act), act = the forward's skip values; partial
+ * [p4c_unet_enc_tail_bwd_blocks][2][C] = the batch-norm backward sums of p4c_inorm_reduce (sum dz, sum dz (y - mean) rstd), for
+ * p4c_inorm_finalize_bwd (B = 1) and p4c_inorm_apply (slope 1). */
+int p4c_unet_enc_tail_fwd(const void* y, const float* scale, const float* shift, void* skip, int64_t ld, void* pool, int dtype, int B, int H,
+                          int W, int C, p4c_stream_t stream);
+int p4c_unet_enc_tail_bwd_blocks(int B, int H, int W, int C);
+int p4c_unet_enc_tail_bwd(const void* y, const void* act, int64_t lda, const void* dskip, int64_t ldd, const void* dpool, const float* mean,
+                          const float* rstd, void* dz, float* partial, int dtype, int B, int H, int W, int C, p4c_stream_t stream);
+
 /* Bilinear up-sampling of a features-last bf16 map (B, H, W, C) by an integer factor (torch interpolate, align_corners = False),
  * + skip (B, H*scale, W*scale, C) when given -- mfai's UnetrUpBlock with `linear_upsampling: true` (config/CLI/model/unetrpp.yaml:29).
  * Backward in gather form (fixed order, no atomics): dx from dout; the skip's gradient is dout.  C a multiple of 8. */

@@ -98,6 +98,12 @@ SIGNATURES = {
     "p4c_gemm_nt": [P, L, P, I, I, I, I, I, I, I, P, P, L, I, P, P, L, P, L, P, P, P],
     "p4c_gemm_tn": [P, L, P, L, I, I, I, I, I, I, P, P, I, P, P],
     "p4c_bnorm_finalize": [P, I, ctypes.c_double, I, P, P, F, F, P, P, P, P, P, P, P, P],
+    "p4c_upconv_prep_weight": [P, I, I, P, P, P],
+    "p4c_gemm_upconv_fwd": [P, L, P, P, I, I, I, I, I, P, L, P, P],
+    "p4c_gemm_upconv_dgrad": [P, L, P, I, I, I, I, I, P, L, P, P],
+    "p4c_gemm_upconv_wgrad": [P, L, P, L, I, I, I, I, I, P, P, I, P, P],
+    "p4c_unet_enc_tail_fwd": [P, P, P, P, L, P, I, I, I, I, I, P],
+    "p4c_unet_enc_tail_bwd": [P, P, L, P, L, P, P, P, P, P, I, I, I, I, I, P],
 }
 OTHER = {
     "p4c_conv_wgrad_workspace_bytes": ([I, I], c_size_t),
@@ -124,4 +130,5 @@ OTHER = {
     "p4c_gemm_nt_workspace_bytes": ([I, I, I], c_size_t),
     "p4c_gemm_nt_stat_blocks": ([I, I, I], c_int),
     "p4c_gemm_tn_workspace_bytes": ([I, I, I], c_size_t),
+    "p4c_unet_enc_tail_bwd_blocks": ([I, I, I, I], c_int),
 }

@@ -86,12 +86,23 @@ struct Epi {
     int64_t ldc;
     float* stats;           // [row blocks][2][N] column sums / sums of squares of the rounded output, or NULL
     int act;
+    int up_W, up_C;         // up_C > 0: sub-pixel store of a 2x2 / stride-2 transposed convolution (p4c_gemm_upconv_fwd): row m = pixel
+                            // of a (., up_W)-wide map, column n = (dy, dx, c) with c < up_C -> row (2h+dy, 2w+dx) of the 2x grid,
+                            // channel c (bias indexed by c)
 };
 
 // one 8-wide piece of output row m at columns n .. n+7 (n a multiple of 8, all 8 inside N): v = accumulated products
 __device__ __forceinline__ void epi_piece(const Epi& e, float (&v)[8], int64_t m, int n, float (&s1)[8], float (&s2)[8]) {
+    int64_t dst = m * e.ldc + n;
+    int bn = n;
+    if (e.up_C) {
+        const int sub = n / e.up_C, c = n - sub * e.up_C;
+        const int64_t w = m % e.up_W;
+        dst = (4 * m - 2 * w + (int64_t)(sub >> 1) * 2 * e.up_W + (sub & 1)) * e.ldc + c;
+        bn = c;
+    }
     if (e.bias) {
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(e.bias + n), b1 = *reinterpret_cast<const f32x4*>(e.bias + n + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(e.bias + bn), b1 = *reinterpret_cast<const f32x4*>(e.bias + bn + 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
     }
@@ -119,7 +130,7 @@ __device__ __forceinline__ void epi_piece(const Epi& e, float (&v)[8], int64_t m
     u32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = pack2(v[2 * j], v[2 * j + 1]);
-    *reinterpret_cast<u32x4*>(e.C + m * e.ldc + n) = o;
+    *reinterpret_cast<u32x4*>(e.C + dst) = o;
     if (e.stats) {
         float ov[8];
         unpack8(o, ov);
@@ -156,7 +167,9 @@ struct NtArgs {
     int64_t lda, ldb;
     unsigned int a_bytes, b_bytes;
     int M, N, K;
-    int H, W, Cin, taps;    // taps == 9: 3x3 "same" convolution over (H, W) maps, K = 9 * Cin;  taps == 1: plain rows
+    int H, W, Cin, taps;    // taps == 9: 3x3 "same" convolution over (H, W) maps, K = 9 * Cin;  taps == 1: plain rows;  taps == 4
+                            // (MODE 2): row m = pixel (h, w) of an (H, W) map gathers the 2x2 block (2h+dy, 2w+dx) of the 2x grid A,
+                            // k = (2 dy + dx) * Cin + c -- the data gradient of a 2x2 / stride-2 transposed convolution
     int tiles_m, tiles_n;
     int nkb, splits, kb_per_split;
     float* partial;         // splits > 1: [split][tile][128][128] fp32
@@ -186,8 +199,9 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned int vo
 }
 __device__ __forceinline__ unsigned int lds_address(const void* p) { return (unsigned int)(size_t)((lds_ptr)p); }
 
-template <bool CONV>
+template <int MODE>      // 0 plain rows, 1 3x3 convolution, 2 sub-pixel gather (taps == 4)
 __global__ void __launch_bounds__(512, 2) gemm_nt_kernel(NtArgs a) {
+    constexpr bool CONV = MODE != 0, UPG = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [4][A 16 KB | B 16 KB]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -229,7 +243,10 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_kernel(NtArgs a) {
         a_row[it] = m < a.M ? (unsigned int)((int64_t)m * a.lda * 2) : OOB;
         b_row[it] = n < a.N ? (unsigned int)((int64_t)n * a.ldb * 2) : OOB;
         vmask[it] = 0u;
-        if (CONV && m < a.M) {
+        if (UPG && m < a.M) {
+            a_row[it] = (unsigned int)((int64_t)(4 * m - 2 * (m % a.W)) * a.lda * 2);
+            vmask[it] = 0xfu;
+        } else if (CONV && m < a.M) {
             const int p = m % (a.H * a.W);
             const int y = p / a.W, x = p - y * a.W;
 #pragma unroll
@@ -242,6 +259,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_kernel(NtArgs a) {
     // pixel + channel -- recomputed only when ci wraps into the next tap (no division, no tap arithmetic in the steady state)
     int kq[2], tap[2], ci[2], shift[2];
     auto tap_shift = [&](int t, int c) __attribute__((always_inline)) {
+        if (UPG) return (((t >> 1) * 2 * a.W + (t & 1)) * (int)a.lda + c) * 2;
         const int dy = t / 3 - 1, dx = t - (t / 3) * 3 - 1;
         return ((dy * a.W + dx) * (int)a.lda + c) * 2;
     };
@@ -412,6 +430,8 @@ struct TnArgs {
     int nrb, splits, rb_per_split;
     float* partial;         // [split][tile][128][128]
     float* bias_partial;    // [split][tiles_i][4][128] or NULL
+    int up_C;               // UPP: P(r, i) = the 2x grid's pixel (2h+dy, 2w+dx), channel c of i = (2 dy + dx) * up_C + c, r = (h, w) of an
+                            // (., W)-wide map -- the weight gradient of a 2x2 / stride-2 transposed convolution (p4c_gemm_upconv_wgrad)
 };
 
 #ifndef P4C_TN_EXP
@@ -423,7 +443,7 @@ constexpr int TN_STAGE_BYTES = 32768;        // P tile [64 r][128] bf16 (16 KB) 
 // and the two 16-column blocks of a 32-lane half then cover the 256-byte bank row exactly once (conflict-free)
 __device__ __forceinline__ int tn_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
-template <bool CONV, bool BIAS>
+template <bool CONV, bool BIAS, bool UPP = false>
 __global__ void __launch_bounds__(512, 2) gemm_tn_kernel(TnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [4][P tile | Q tile]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -445,6 +465,7 @@ __global__ void __launch_bounds__(512, 2) gemm_tn_kernel(TnArgs a) {
     int rrow[2], py[2], px[2];
     unsigned int p_off[2], q_off[2];
     int qdy[2], qdx[2];
+    int pcol[2], upx[2];       // UPP: the lane's P column offset (sub-pixel row shift + channel) and w of its row
     bool p_ok[2], q_ok[2];
     const unsigned int p_step = (unsigned int)(64 * a.ldp * 2), q_step = (unsigned int)(64 * a.ldq * 2);
 #pragma unroll
@@ -456,6 +477,14 @@ __global__ void __launch_bounds__(512, 2) gemm_tn_kernel(TnArgs a) {
         p_ok[it] = i0 + chk * 8 < a.Mo;
         q_ok[it] = j0 + chk * 8 < a.No;
         p_off[it] = (unsigned int)((int64_t)rr * a.ldp * 2) + (unsigned int)(i0 + chk * 8) * 2;
+        pcol[it] = 0;
+        upx[it] = 0;
+        if (UPP) {
+            const int col = i0 + chk * 8, sub = col / a.up_C, c = col - sub * a.up_C;
+            pcol[it] = ((sub >> 1) * 2 * a.W + (sub & 1)) * (int)a.ldp + c;
+            upx[it] = rr % a.W;
+            p_off[it] = (unsigned int)(((int64_t)(4 * rr - 2 * upx[it]) * a.ldp + pcol[it]) * 2);
+        }
         qdy[it] = 0;
         qdx[it] = 0;
         py[it] = 0;
@@ -487,6 +516,11 @@ __global__ void __launch_bounds__(512, 2) gemm_tn_kernel(TnArgs a) {
             rrow[it] += 64;
             p_off[it] += p_step;
             q_off[it] += q_step;
+            if (UPP) {
+                upx[it] += 64;
+                while (upx[it] >= a.W) upx[it] -= a.W;
+                p_off[it] = (unsigned int)(((int64_t)(4 * rrow[it] - 2 * upx[it]) * a.ldp + pcol[it]) * 2);
+            }
             if (CONV) {
                 px[it] += 64;
                 while (px[it] >= a.W) { px[it] -= a.W; ++py[it]; }
@@ -585,6 +619,8 @@ struct TnRedArgs {
     float* dw;
     float* db;
     int splits, tiles, tiles_i, Mo, No, Cin, taps, cchunk, accumulate;
+    int up_C;           // > 0: row i = (2 dy + dx) * up_C + c of a transposed convolution's gradient, written to dw[ci][c][dy][dx] (the
+                        // torch ConvTranspose2d layout) and db[c] = the sum of the four sub-pixel rows' column sums (rows i < up_C write it)
 };
 __device__ __forceinline__ void tn_reduce_block(const TnRedArgs& a, const int bx, const int i, float* __restrict__ turn, float* __restrict__ part) {
     const int c0 = bx * a.cchunk;
@@ -623,6 +659,25 @@ __device__ __forceinline__ void tn_reduce_block(const TnRedArgs& a, const int bx
         }
     }
     __syncthreads();
+    if (a.up_C) {
+        const int sub = i / a.up_C, co = i - sub * a.up_C;
+        for (int e = threadIdx.x; e < ne; e += 256) {
+            float* o = a.dw + ((int64_t)(c0 + e) * a.up_C + co) * 4 + sub;
+            *o = a.accumulate ? *o + turn[e] : turn[e];
+        }
+        if (a.db && bx == 0 && sub == 0 && threadIdx.x < 64) {
+            float t = 0.f;
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const int ii = i + s4 * a.up_C;
+                float u = 0.f;
+                for (int k = threadIdx.x; k < 4 * a.splits; k += 64)
+                    u += a.bias_partial[(((int64_t)(k >> 2) * a.tiles_i + (ii >> 7)) * 4 + (k & 3)) * 128 + (ii & 127)];
+                t += wave_sum(u);
+            }
+            if (threadIdx.x == 0) a.db[co] = a.accumulate ? a.db[co] + t : t;
+        }
+        return;
+    }
     float* out = a.dw + ((int64_t)i * a.Cin + c0) * a.taps;
     for (int e = threadIdx.x; e < ne; e += 256) {
         const int c = e / a.taps, tap = e - c * a.taps;
@@ -952,15 +1007,15 @@ extern "C" int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, 
     P4C_CHECK_ARG(a.splits == 1 || workspace, "p4c_gemm_nt: this shape runs split-K: workspace of p4c_gemm_nt_workspace_bytes required");
     a.partial = (float*)workspace;
     a.e.bias = bias; a.e.res = (const bf16*)res; a.e.ldr = ldr; a.e.aux_in = (const bf16*)aux_in; a.e.aux_out = (bf16*)aux_out;
-    a.e.ldaux = ldaux; a.e.C = (bf16*)C; a.e.ldc = ldc; a.e.stats = stats; a.e.act = act;
+    a.e.ldaux = ldaux; a.e.C = (bf16*)C; a.e.ldc = ldc; a.e.stats = stats; a.e.act = act; a.e.up_W = 0; a.e.up_C = 0;
     const int tiles = a.tiles_m * a.tiles_n, smem = NT_STAGES * NT_STAGE_BYTES;
     hipStream_t st = as_stream(stream);
     if (taps == 9) {
-        P4C_TRY(ensure_dyn_smem((const void*)gemm_nt_kernel<true>, smem));
-        hipLaunchKernelGGL((gemm_nt_kernel<true>), dim3(tiles, a.splits), dim3(512), smem, st, a);
+        P4C_TRY(ensure_dyn_smem((const void*)gemm_nt_kernel<1>, smem));
+        hipLaunchKernelGGL((gemm_nt_kernel<1>), dim3(tiles, a.splits), dim3(512), smem, st, a);
     } else {
-        P4C_TRY(ensure_dyn_smem((const void*)gemm_nt_kernel<false>, smem));
-        hipLaunchKernelGGL((gemm_nt_kernel<false>), dim3(tiles, a.splits), dim3(512), smem, st, a);
+        P4C_TRY(ensure_dyn_smem((const void*)gemm_nt_kernel<0>, smem));
+        hipLaunchKernelGGL((gemm_nt_kernel<0>), dim3(tiles, a.splits), dim3(512), smem, st, a);
     }
     P4C_CHECK_LAUNCH("gemm_nt");
     if (a.splits > 1) {
@@ -1055,6 +1110,7 @@ extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t l
     const int64_t p_bytes = (int64_t)R * ldp * 2, q_bytes = (int64_t)R * ldq * 2;
     P4C_CHECK_ARG(p_bytes < 0x7fffffffLL && q_bytes < 0x7fffffffLL, "p4c_gemm_tn: operands beyond 2 GiB");
     TnArgs a;
+    a.up_C = 0;
     a.P = (const bf16*)dy; a.Q = (const bf16*)x; a.ldp = ldp; a.ldq = ldq; a.p_bytes = (unsigned int)p_bytes; a.q_bytes = (unsigned int)q_bytes;
     a.R = R; a.Mo = Mo; a.No = taps * Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = taps;
     tn_plan(R, Mo, a.No, &a.tiles_i, &a.tiles_j, &a.nrb, &a.splits, &a.rb_per_split);
@@ -1076,7 +1132,7 @@ extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t l
     int cchunk = 512;
     while (cchunk > 32 && (int64_t)((Cin + cchunk - 1) / cchunk) * Mo < 1024) cchunk >>= 1;
     if (cchunk > Cin) cchunk = Cin;
-    TnRedArgs r{a.partial, a.bias_partial, dw, db, a.splits, tiles, a.tiles_i, Mo, a.No, Cin, taps, cchunk, accumulate ? 1 : 0};
+    TnRedArgs r{a.partial, a.bias_partial, dw, db, a.splits, tiles, a.tiles_i, Mo, a.No, Cin, taps, cchunk, accumulate ? 1 : 0, 0};
     if (accumulate && grad_reduce_deferring()) {
         // (the caller keeps the workspace alive until p4c_grad_reduce_flush: py4cast_amd.ops_nodeproj.GradQueue)
         std::lock_guard<std::mutex> lk(g_tn_mu);
@@ -1095,5 +1151,131 @@ extern "C" int p4c_bnorm_finalize(const float* partial, int nblk, double count, 
     hipLaunchKernelGGL(bnorm_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, as_stream(stream), partial, nblk, count, C, gamma, beta, eps,
                        momentum, running_mean, running_var, mean, rstd, scale, shift, reinterpret_cast<long long*>(num_batches_tracked));
     P4C_CHECK_LAUNCH("bnorm_finalize");
+    return P4C_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ 2x2 / stride-2 transposed convolution
+// (UNet's upconv4..1: torch.nn.ConvTranspose2d(2c, c, kernel_size=2, stride=2), weight (Cin, Cout, 2, 2)).  Every input pixel (h, w)
+// makes the 2x2 output block (2h+dy, 2w+dx) on its own, so the layer is ONE GEMM with sub-pixel addressing -- no interleave copy, and the
+// result lands in a row view of the caller's choosing (the first half of the decoder's concatenation buffer):
+//   forward  C[m][(dy, dx, co)] = sum_ci x[m][ci] w[ci][co][dy][dx]   rows m = small-grid pixels; the epilogue adds b[co] and stores at
+//                                                                      pixel (2h+dy, 2w+dx), channel co (Epi::up_W / up_C)
+//   dgrad    dx[m][ci] = sum_(dy, dx, co) dup[(2h+dy, 2w+dx)][co] w[ci][co][dy][dx]   the A loader gathers the four sub-pixels (MODE 2)
+//   wgrad    dw[ci][co][dy][dx] = sum_m dup[(2h+dy, 2w+dx)][co] x[m][ci], db[co] = sum over the 2x grid of dup   gemm_tn with P gathered
+__global__ void __launch_bounds__(256) upconv_prep_kernel(const float* __restrict__ w, int Cin, int Cout, bf16* __restrict__ fwd,
+                                                          bf16* __restrict__ dgrad) {
+    const int64_t n = (int64_t)Cin * Cout * 4;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int t = (int)(e & 3);
+        const int64_t q = e >> 2;
+        const int co = (int)(q % Cout), ci = (int)(q / Cout);
+        const bf16 v = __float2bfloat16(w[e]);
+        fwd[((int64_t)t * Cout + co) * Cin + ci] = v;            // [4 Cout][Cin]
+        dgrad[(int64_t)ci * 4 * Cout + t * Cout + co] = v;       // [Cin][4 Cout]
+    }
+}
+
+extern "C" int p4c_upconv_prep_weight(const float* w, int Cin, int Cout, void* fwd, void* dgrad, p4c_stream_t stream) {
+    P4C_CHECK_ARG(w && fwd && dgrad && Cin > 0 && Cout > 0, "p4c_upconv_prep_weight: bad arguments");
+    const int64_t n = (int64_t)Cin * Cout * 4;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(upconv_prep_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, Cin, Cout, (bf16*)fwd, (bf16*)dgrad);
+    P4C_CHECK_LAUNCH("upconv_prep");
+    return P4C_OK;
+}
+
+static int upconv_nt_launch(NtArgs& a, int mode, void* workspace, hipStream_t st) {
+    nt_plan(a.M, a.N, a.K, &a.tiles_m, &a.tiles_n, &a.nkb, &a.splits, &a.kb_per_split);
+    P4C_CHECK_ARG(a.splits == 1 || workspace, "p4c_gemm_upconv: this shape runs split-K: workspace of p4c_gemm_nt_workspace_bytes required");
+    a.partial = (float*)workspace;
+    const int tiles = a.tiles_m * a.tiles_n, smem = NT_STAGES * NT_STAGE_BYTES;
+    if (mode == 2) {
+        P4C_TRY(ensure_dyn_smem((const void*)gemm_nt_kernel<2>, smem));
+        hipLaunchKernelGGL((gemm_nt_kernel<2>), dim3(tiles, a.splits), dim3(512), smem, st, a);
+    } else {
+        P4C_TRY(ensure_dyn_smem((const void*)gemm_nt_kernel<0>, smem));
+        hipLaunchKernelGGL((gemm_nt_kernel<0>), dim3(tiles, a.splits), dim3(512), smem, st, a);
+    }
+    P4C_CHECK_LAUNCH("gemm_upconv");
+    if (a.splits > 1) {
+        NtRedArgs r{(const float*)workspace, a.splits, tiles, a.tiles_m, a.M, a.N, a.e};
+        hipLaunchKernelGGL(gemm_nt_reduce_kernel, dim3(tiles, 4), dim3(256), 0, st, r);
+        P4C_CHECK_LAUNCH("gemm_upconv_reduce");
+    }
+    return P4C_OK;
+}
+
+static void upconv_epi_clear(Epi& e) {
+    e.bias = nullptr; e.res = nullptr; e.ldr = 0; e.aux_in = nullptr; e.aux_out = nullptr; e.ldaux = 0; e.C = nullptr; e.ldc = 0;
+    e.stats = nullptr; e.act = ACT_NONE; e.up_W = 0; e.up_C = 0;
+}
+
+extern "C" int p4c_gemm_upconv_fwd(const void* x, int64_t ldx, const void* fwd_img, const float* bias, int B, int H, int W, int Cin, int Cout,
+                                   void* out, int64_t ldo, void* workspace, p4c_stream_t stream) {
+    P4C_CHECK_ARG(x && fwd_img && out, "p4c_gemm_upconv_fwd: NULL pointer");
+    P4C_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0, "p4c_gemm_upconv_fwd: B=%d H=%d W=%d Cin=%d Cout=%d",
+                  B, H, W, Cin, Cout);
+    P4C_CHECK_ARG(ldx % 8 == 0 && ldx >= Cin && ldo % 8 == 0 && ldo >= Cout, "p4c_gemm_upconv_fwd: row strides");
+    const int64_t M = (int64_t)B * H * W;
+    P4C_CHECK_ARG(M * ldx * 2 < 0x7fffffffLL && (int64_t)4 * Cout * Cin * 2 < 0x7fffffffLL && 4 * M * ldo < 0x7fffffffLL,
+                  "p4c_gemm_upconv_fwd: operands beyond 2 GiB");
+    NtArgs a;
+    a.A = (const bf16*)x; a.B = (const bf16*)fwd_img; a.lda = ldx; a.ldb = Cin;
+    a.a_bytes = (unsigned int)(M * ldx * 2); a.b_bytes = (unsigned int)((int64_t)4 * Cout * Cin * 2);
+    a.M = (int)M; a.N = 4 * Cout; a.K = Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = 1;
+    upconv_epi_clear(a.e);
+    a.e.bias = bias; a.e.C = (bf16*)out; a.e.ldc = ldo; a.e.up_W = W; a.e.up_C = Cout;
+    return upconv_nt_launch(a, 0, workspace, as_stream(stream));
+}
+
+extern "C" int p4c_gemm_upconv_dgrad(const void* dup, int64_t ldd, const void* dgrad_img, int B, int H, int W, int Cin, int Cout, void* dx,
+                                     int64_t ldx, void* workspace, p4c_stream_t stream) {
+    P4C_CHECK_ARG(dup && dgrad_img && dx, "p4c_gemm_upconv_dgrad: NULL pointer");
+    P4C_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0, "p4c_gemm_upconv_dgrad: B=%d H=%d W=%d Cin=%d Cout=%d",
+                  B, H, W, Cin, Cout);
+    P4C_CHECK_ARG(ldd % 8 == 0 && ldd >= Cout && ldx % 8 == 0 && ldx >= Cin, "p4c_gemm_upconv_dgrad: row strides");
+    const int64_t M = (int64_t)B * H * W;
+    P4C_CHECK_ARG(4 * M * ldd * 2 < 0x7fffffffLL && (int64_t)4 * Cout * Cin * 2 < 0x7fffffffLL, "p4c_gemm_upconv_dgrad: operands beyond 2 GiB");
+    NtArgs a;
+    a.A = (const bf16*)dup; a.B = (const bf16*)dgrad_img; a.lda = ldd; a.ldb = 4 * Cout;
+    a.a_bytes = (unsigned int)(4 * M * ldd * 2); a.b_bytes = (unsigned int)((int64_t)4 * Cout * Cin * 2);
+    a.M = (int)M; a.N = Cin; a.K = 4 * Cout; a.H = H; a.W = W; a.Cin = Cout; a.taps = 4;
+    upconv_epi_clear(a.e);
+    a.e.C = (bf16*)dx; a.e.ldc = ldx;
+    return upconv_nt_launch(a, 2, workspace, as_stream(stream));
+}
+
+extern "C" int p4c_gemm_upconv_wgrad(const void* dup, int64_t ldd, const void* x, int64_t ldx, int B, int H, int W, int Cin, int Cout, float* dw,
+                                     float* db, int accumulate, void* workspace, p4c_stream_t stream) {
+    P4C_CHECK_ARG(dup && x && dw && workspace, "p4c_gemm_upconv_wgrad: NULL pointer");
+    P4C_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0, "p4c_gemm_upconv_wgrad: B=%d H=%d W=%d Cin=%d Cout=%d",
+                  B, H, W, Cin, Cout);
+    P4C_CHECK_ARG(ldd % 8 == 0 && ldd >= Cout && ldx % 8 == 0 && ldx >= Cin, "p4c_gemm_upconv_wgrad: row strides");
+    const int64_t R = (int64_t)B * H * W;
+    P4C_CHECK_ARG(4 * R * ldd * 2 < 0x7fffffffLL && R * ldx * 2 < 0x7fffffffLL, "p4c_gemm_upconv_wgrad: operands beyond 2 GiB");
+    TnArgs a;
+    a.P = (const bf16*)dup; a.Q = (const bf16*)x; a.ldp = ldd; a.ldq = ldx;
+    a.p_bytes = (unsigned int)(4 * R * ldd * 2); a.q_bytes = (unsigned int)(R * ldx * 2);
+    a.R = (int)R; a.Mo = 4 * Cout; a.No = Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = 1; a.up_C = Cout;
+    tn_plan(a.R, a.Mo, a.No, &a.tiles_i, &a.tiles_j, &a.nrb, &a.splits, &a.rb_per_split);
+    const int tiles = a.tiles_i * a.tiles_j;
+    a.partial = (float*)workspace;
+    a.bias_partial = db ? (float*)workspace + (size_t)a.splits * tiles * 128 * 128 : nullptr;
+    const int smem = TN_STAGES * TN_STAGE_BYTES;
+    hipStream_t st = as_stream(stream);
+    if (db) {
+        P4C_TRY(ensure_dyn_smem((const void*)gemm_tn_kernel<false, true, true>, smem));
+        hipLaunchKernelGGL((gemm_tn_kernel<false, true, true>), dim3(tiles, a.splits), dim3(512), smem, st, a);
+    } else {
+        P4C_TRY(ensure_dyn_smem((const void*)gemm_tn_kernel<false, false, true>, smem));
+        hipLaunchKernelGGL((gemm_tn_kernel<false, false, true>), dim3(tiles, a.splits), dim3(512), smem, st, a);
+    }
+    P4C_CHECK_LAUNCH("gemm_upconv_wgrad");
+    int cchunk = 512;
+    while (cchunk > 32 && (int64_t)((Cin + cchunk - 1) / cchunk) * a.Mo < 1024) cchunk >>= 1;
+    if (cchunk > Cin) cchunk = Cin;
+    TnRedArgs r{a.partial, a.bias_partial, dw, db, a.splits, tiles, a.tiles_i, a.Mo, a.No, Cin, 1, cchunk, accumulate ? 1 : 0, Cout};
+    hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((Cin + cchunk - 1) / cchunk, a.Mo), dim3(256), 0, st, r);
+    P4C_CHECK_LAUNCH("gemm_upconv_wgrad_reduce");
     return P4C_OK;
 }
