@@ -666,7 +666,8 @@ typedef struct p4c_row_mlp_grad_sinks {
     float* dgamma;
     float* dbeta;
 } p4c_row_mlp_grad_sinks;
-int p4c_row_mlp_bwd_accumulate(const p4c_row_mlp_desc* d, const p4c_row_mlp_grad_sinks* sinks, void* workspace, p4c_stream_t stream);
+int p4c_row_mlp_bwd_accumulate(const p4c_row_mlp_desc* d, const p4c_row_mlp_grad_sinks* sinks, int defer, void* workspace,
+                               p4c_stream_t stream);
 
 /* Mesh-GNN launch grouping (round 6; csrc/nodeproj.hip).  An InteractionNet of GraphLAM / HiLAM (config/CLI/model/graphlam.yaml:19-26,
  * hilam.yaml, hilamparallel.yaml; classes taken at py4cast/models.py:66-89) multiplies a node tensor x (R, 64) bf16 with up to three
@@ -681,15 +682,16 @@ int p4c_node_proj_fwd(const void* x, int64_t R, int n, const float* const* w, co
 int p4c_node_proj_dgrad(const void* const* dy, int64_t R, int n, const float* const* w, const int32_t* ldw, void* dx, const void* acc,
                         p4c_stream_t stream);
 size_t p4c_node_proj_wgrad_workspace_bytes(int64_t R, int n);
-int p4c_node_proj_wgrad(const void* const* dy, const void* x, int64_t R, int n, float* const* dw, const int32_t* ld_dw, void* workspace,
-                        p4c_stream_t stream);
-/* Reduction queue of the parameter-gradient partials that p4c_row_mlp_bwd_accumulate and p4c_node_proj_wgrad leave.  By default each
- * call enqueues its own reduction launch.  After p4c_grad_reduce_defer(1) the reductions are queued instead (process-wide; the
- * workspaces must stay alive) and p4c_grad_reduce_flush(stream) -- the stream of the backward -- reduces all queued jobs, 32 per launch,
- * in submission order: ~550 dependent 5 us launches of a HiLAM step become ~20, and the accumulated gradients are bit-identical.
- * p4c_grad_reduce_defer returns the previous setting (on = -1: drop the queued jobs -- a backward pass that died before its flush -- and
- * reduce at once again); p4c_grad_reduce_pending the number of queued jobs. */
-int p4c_grad_reduce_defer(int on);
+int p4c_node_proj_wgrad(const void* const* dy, const void* x, int64_t R, int n, float* const* dw, const int32_t* ld_dw, int defer,
+                        void* workspace, p4c_stream_t stream);
+/* Reduction queue of the parameter-gradient partials that p4c_row_mlp_bwd_accumulate, p4c_node_proj_wgrad and an accumulating
+ * p4c_gemm_tn leave.  The caller decides per call; there is no process-wide mode.  defer = 0: the call enqueues its own reduction
+ * launch.  defer = 1: the reduction is queued instead, and the call's workspace must stay alive until the flush.
+ * p4c_grad_reduce_flush(stream) -- the stream of the backward -- reduces all queued jobs, 32 per launch, in submission order (the
+ * p4c_gemm_tn jobs first): ~550 dependent 5 us launches of a HiLAM step become ~20, and the accumulated gradients are bit-identical.
+ * p4c_grad_reduce_drop discards the queued jobs (a backward pass that died before its flush); p4c_grad_reduce_pending returns the
+ * number of queued jobs. */
+int p4c_grad_reduce_drop(void);
 int p4c_grad_reduce_pending(void);
 int p4c_grad_reduce_flush(p4c_stream_t stream);
 
@@ -872,11 +874,11 @@ int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, int N, int 
 /* Weight (+ bias) gradient: dw (Mo, Cin, taps) fp32 in the torch layout = sum over the R rows of dy[r][:Mo]^T (x) x[r] -- taps = 9:
  * x's 3x3 neighbourhood of pixel r (x = the NHWC map, R = batch * H * W) --, db (Mo) = column sums of dy (or NULL).  dy / x bf16 rows
  * with strides ldp / ldq (multiples of 8).  Split over the rows, fp32 slabs summed in a fixed order.  accumulate = 1: dw / db are ADDED
- * to (a parameter's .grad buffer: no AccumulateGrad launch per AR step).  workspace:
- * p4c_gemm_tn_workspace_bytes(R, Mo, taps * Cin) bytes. */
+ * to (a parameter's .grad buffer: no AccumulateGrad launch per AR step).  defer = 1 (accumulating calls only): the slabs' reduction joins
+ * the queue of p4c_grad_reduce_flush instead of being launched now.  workspace: p4c_gemm_tn_workspace_bytes(R, Mo, taps * Cin) bytes. */
 size_t p4c_gemm_tn_workspace_bytes(int R, int Mo, int No);
 int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t ldq, int R, int Mo, int H, int W, int Cin, int taps, float* dw,
-                float* db, int accumulate, void* workspace, p4c_stream_t stream);
+                float* db, int accumulate, int defer, void* workspace, p4c_stream_t stream);
 /* BatchNorm2d (training mode) statistics from column partial sums [nblk][2][C] over `count` values per channel: mean, rstd,
  * scale = gamma rstd, shift = beta - mean scale (C each, fp32); running_mean / running_var (optional) get torch's momentum update
  * with the unbiased variance, num_batches_tracked (optional, the module's int64 counter) is incremented by one. */

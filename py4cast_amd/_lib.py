@@ -9,7 +9,7 @@ absent, import-time / call-time errors are raised.  Build it with
 import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -132,6 +132,61 @@ def grad_written(*views):
     if GRAD_SINK_LISTENERS:
         for listener in GRAD_SINK_LISTENERS:
             listener.written(views)
+
+
+class GradQueue:
+    """Deferred reduction of the gradient partials of ONE backward pass (include/py4cast_hip.h: the ``defer`` argument of
+    p4c_gemm_tn, p4c_row_mlp_bwd_accumulate and p4c_node_proj_wgrad; p4c_grad_reduce_flush).  The queued reductions run 32 per launch
+    when the autograd engine finishes the pass (``queue_callback``); ``keep`` (the partials' workspace) stays alive until then.
+    Outside a backward pass (no graph task) nothing is deferred."""
+
+    enabled = True          # False: every call reduces at once (the A/B reference of tests/test_nodeproj_gpu.py, test_gemm_gpu.py)
+    _task = -1
+    _keep: List[torch.Tensor] = []
+    _views: List[torch.Tensor] = []      # the .grad regions the queued reductions will add into (told to grad_written at the flush)
+    _stream = None
+
+    @classmethod
+    def join(cls, keep: torch.Tensor, start: bool) -> bool:
+        """The ``defer`` flag of the call about to be made: True when this backward pass is deferring its reductions -- or starts to,
+        with ``start`` -- and then ``keep`` is held until the flush."""
+        task = torch._C._current_graph_task_id()
+        if cls._task >= 0 and cls._task != task:   # a pass that died before its callback ran: its queued jobs are void
+            lib().p4c_grad_reduce_drop()
+            cls._task, cls._keep, cls._views, cls._stream = -1, [], [], None
+        if not cls.enabled or task < 0:
+            return False
+        if cls._task != task:
+            if not start:
+                return False
+            cls._task, cls._stream = task, torch.cuda.current_stream(keep.device)
+            torch.autograd.Variable._execution_engine.queue_callback(cls.flush)
+        cls._keep.append(keep)
+        return True
+
+    @classmethod
+    def wrote(cls, views, deferred: bool) -> None:
+        """After the launch that produced the partials: ``views`` (regions of parameters' .grad) receive their sums when the queue is
+        flushed (``deferred``, what ``join`` returned) or have just received them."""
+        if not GRAD_SINK_LISTENERS:
+            return
+        views = [v for v in views if v is not None]
+        if deferred:
+            cls._views.extend(views)
+        else:
+            grad_written(*views)
+
+    @classmethod
+    def flush(cls) -> None:
+        if cls._task < 0:
+            return
+        views = cls._views
+        try:
+            check(lib().p4c_grad_reduce_flush(c_void_p(cls._stream.cuda_stream)), "p4c_grad_reduce_flush")
+        finally:
+            cls._task, cls._keep, cls._views, cls._stream = -1, [], [], None
+        if views:
+            grad_written(*views)
 
 
 # Values derived from the parameters (re-laid weight images, bf16 copies of weight blocks) are cached per parameter version in

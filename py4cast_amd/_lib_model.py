@@ -78,11 +78,11 @@ SIGNATURES = {
     "p4c_row_mlp_fwd": [MP, P],
     "p4c_row_mlp_prepare": [MP, P, P],
     "p4c_row_mlp_bwd": [MP, P, P, P],
-    "p4c_row_mlp_bwd_accumulate": [MP, SP, P, P],
+    "p4c_row_mlp_bwd_accumulate": [MP, SP, I, P, P],
     "p4c_node_proj_fwd": [P, L, I, P, P, P, P],
     "p4c_node_proj_dgrad": [P, L, I, P, P, P, P, P],
-    "p4c_node_proj_wgrad": [P, P, L, I, P, P, P, P],
-    "p4c_grad_reduce_defer": [I],
+    "p4c_node_proj_wgrad": [P, P, L, I, P, P, I, P, P],
+    "p4c_grad_reduce_drop": [],
     "p4c_grad_reduce_flush": [P],
     "p4c_window_attn_fwd": [P, P, P, I, I, I, I, I, I, I, F, I, P],
     "p4c_window_attn_bwd": [P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, P],
@@ -96,7 +96,7 @@ SIGNATURES = {
     "p4c_gemm_prep_weight_batch": [I, P, P, P, P, P, P, P, P, P, P],
     "p4c_gemm_scale_fold_bwd": [P, P, P, P, P, I, I, P, P, P, I, P],
     "p4c_gemm_nt": [P, L, P, I, I, I, I, I, I, I, P, P, L, I, P, P, L, P, L, P, P, P],
-    "p4c_gemm_tn": [P, L, P, L, I, I, I, I, I, I, P, P, I, P, P],
+    "p4c_gemm_tn": [P, L, P, L, I, I, I, I, I, I, P, P, I, I, P, P],
     "p4c_bnorm_finalize": [P, I, ctypes.c_double, I, P, P, F, F, P, P, P, P, P, P, P, P],
     "p4c_upconv_prep_weight": [P, I, I, P, P, P],
     "p4c_gemm_upconv_fwd": [P, L, P, P, I, I, I, I, I, P, L, P, P],

@@ -1101,8 +1101,9 @@ int tn_reduce_flush(hipStream_t st) {
 
 // dW (Mo, Cin, taps) fp32 = sum over the R rows of dy^T (x) [x or its 3x3 im2col view], db (Mo) = column sums of dy (or NULL)
 extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t ldq, int R, int Mo, int H, int W, int Cin, int taps,
-                           float* dw, float* db, int accumulate, void* workspace, p4c_stream_t stream) {
+                           float* dw, float* db, int accumulate, int defer, void* workspace, p4c_stream_t stream) {
     P4C_CHECK_ARG(dy && x && dw && workspace, "p4c_gemm_tn: NULL pointer");
+    P4C_CHECK_ARG(!defer || accumulate, "p4c_gemm_tn: only an accumulating call can defer its reduction");
     P4C_CHECK_ARG(R > 0 && Mo > 0 && Cin > 0 && Mo % 8 == 0 && Cin % 8 == 0 && (taps == 1 || taps == 9), "p4c_gemm_tn: R=%d Mo=%d Cin=%d taps=%d", R, Mo,
                   Cin, taps);
     P4C_CHECK_ARG(ldp % 8 == 0 && ldq % 8 == 0 && ldp >= Mo && ldq >= Cin, "p4c_gemm_tn: row strides must be multiples of 8 covering the rows");
@@ -1133,8 +1134,8 @@ extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t l
     while (cchunk > 32 && (int64_t)((Cin + cchunk - 1) / cchunk) * Mo < 1024) cchunk >>= 1;
     if (cchunk > Cin) cchunk = Cin;
     TnRedArgs r{a.partial, a.bias_partial, dw, db, a.splits, tiles, a.tiles_i, Mo, a.No, Cin, taps, cchunk, accumulate ? 1 : 0, 0};
-    if (accumulate && grad_reduce_deferring()) {
-        // (the caller keeps the workspace alive until p4c_grad_reduce_flush: py4cast_amd.ops_nodeproj.GradQueue)
+    if (defer) {
+        // (the caller keeps the workspace alive until p4c_grad_reduce_flush: py4cast_amd._lib.GradQueue)
         std::lock_guard<std::mutex> lk(g_tn_mu);
         g_tn_pending.push_back(TnPending{r, st});
         return P4C_OK;

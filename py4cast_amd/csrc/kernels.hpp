@@ -204,8 +204,9 @@ int enc_out_bwd(int storage, const void* Tx, int Hfull, int s, const void* dS, c
 
 // nodeproj.hip: queue of parameter-gradient reductions (mesh GNNs).  A job sums `slots` partials of n floats in a fixed order and ADDS the
 // result into the gradient buffers p[] (+=): GRAD_JOB_MLP = the layout of mlp.hip's partials (p = dw1, dw2, db1, db2, dgamma, dbeta; ld[0] =
-// row stride of dw1), GRAD_JOB_PROJ = up to three 64 x 64 blocks (p[i] with row stride ld[i]).  Launched at once, or -- while
-// p4c_grad_reduce_defer(1) is in force -- queued until p4c_grad_reduce_flush reduces all queued jobs GRAD_BATCH per launch.
+// row stride of dw1), GRAD_JOB_PROJ = up to three 64 x 64 blocks (p[i] with row stride ld[i]).  The calling entry point passes on its
+// caller's per-call choice: defer = 0 launches the job at once, defer = 1 queues it (its partials must stay alive) until
+// p4c_grad_reduce_flush reduces all queued jobs GRAD_BATCH per launch.  There is no process-wide mode.
 constexpr int GRAD_JOB_MLP = 0, GRAD_JOB_PROJ = 1;
 struct GradReduceJob {
     const float* partial;
@@ -214,10 +215,9 @@ struct GradReduceJob {
     int ld[3];
     int k_real, o_real;
 };
-int grad_reduce_submit(const GradReduceJob& job, hipStream_t stream);
-bool grad_reduce_deferring();      // p4c_grad_reduce_defer(1) is in force
+int grad_reduce_submit(const GradReduceJob& job, hipStream_t stream, int defer);
 // gemm.hip: the same deferral for the accumulating reductions of p4c_gemm_tn (weight gradients added into .grad buffers: the split-K
-// slabs of the calls of one backward pass are reduced TN_BATCH per launch when the pass ends); driven by the entry points above
+// slabs of the calls made with defer = 1 are reduced TN_BATCH per launch at the flush); driven by the entry points of nodeproj.hip
 int tn_reduce_flush(hipStream_t stream);
 int tn_reduce_pending();
 void tn_reduce_drop();

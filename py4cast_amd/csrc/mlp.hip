@@ -839,11 +839,12 @@ __global__ void __launch_bounds__(256) mlp_param_reduce_kernel(const float* __re
 }
 
 // the same sums ADDED into the parameters' gradient buffers: a job for the reduction queue of nodeproj.hip (grad_reduce_submit: at once,
-// or batched with the other jobs of the backward while p4c_grad_reduce_defer is on)
+// or, with defer set, batched with the other queued jobs of the backward)
 struct GradSinks {
     float* dw1; int ld_dw1, k_real;
     float* dw2; int o_real;
     float* db1; float* db2; float* dgamma; float* dbeta;
+    int defer;
 };
 
 int mlp_grid(int64_t R, int per_cu) {
@@ -900,7 +901,7 @@ int launch_bwd(const MlpArgs& a, float* grads, const GradSinks* sinks, hipStream
         job.partial = a.partial; job.slots = mlp_bwd_slots(a.R); job.n = n; job.kind = GRAD_JOB_MLP; job.K = 16 * KS;
         job.p[0] = sinks->dw1; job.p[1] = sinks->dw2; job.p[2] = sinks->db1; job.p[3] = sinks->db2; job.p[4] = sinks->dgamma; job.p[5] = sinks->dbeta;
         job.ld[0] = sinks->ld_dw1; job.k_real = sinks->k_real; job.o_real = sinks->o_real;
-        return grad_reduce_submit(job, s);
+        return grad_reduce_submit(job, s, sinks->defer);
     }
     hipLaunchKernelGGL(mlp_param_reduce_kernel, dim3((n + 31) / 32), dim3(256), 0, s, a.partial, mlp_bwd_slots(a.R), n, grads);
     P4C_CHECK_LAUNCH("mlp_param_reduce");
@@ -968,11 +969,11 @@ extern "C" int p4c_row_mlp_bwd(const p4c_row_mlp_desc* d, float* grads, void* wo
     return row_mlp_bwd_common("p4c_row_mlp_bwd", d, grads, nullptr, workspace, stream);
 }
 
-extern "C" int p4c_row_mlp_bwd_accumulate(const p4c_row_mlp_desc* d, const p4c_row_mlp_grad_sinks* sinks, void* workspace,
+extern "C" int p4c_row_mlp_bwd_accumulate(const p4c_row_mlp_desc* d, const p4c_row_mlp_grad_sinks* sinks, int defer, void* workspace,
                                           p4c_stream_t stream) {
     P4C_CHECK_ARG(d != nullptr && sinks != nullptr && workspace != nullptr, "p4c_row_mlp_bwd_accumulate: NULL pointer");
     P4C_CHECK_ARG(sinks->dw1 == nullptr || sinks->ld_dw1 >= d->k_real, "p4c_row_mlp_bwd_accumulate: bad dw1 row stride");
-    GradSinks g{sinks->dw1, sinks->ld_dw1, d->k_real, sinks->dw2, d->o_real, sinks->db1, sinks->db2, sinks->dgamma, sinks->dbeta};
+    GradSinks g{sinks->dw1, sinks->ld_dw1, d->k_real, sinks->dw2, d->o_real, sinks->db1, sinks->db2, sinks->dgamma, sinks->dbeta, defer};
     return row_mlp_bwd_common("p4c_row_mlp_bwd_accumulate", d, nullptr, &g, workspace, stream);
 }
 

@@ -13,11 +13,11 @@
 //    the small levels): ~14 launches per InteractionNet, now 3 + a share of the batched reduction.
 //
 // 2. The deferred reduction of parameter-gradient partials.  p4c_row_mlp_bwd_accumulate and node_proj_wgrad leave per-workgroup /
-//    per-wave partials; instead of one dependent ~5 us reduction launch behind each of them (~550 per HiLAM step) the jobs are queued
-//    and reduced GRAD_BATCH at a time by grad_reduce_batch_kernel (block -> (job, block of the job) through a prefix table in the kernel
-//    arguments; the pattern of wgrad_reduce_batch, conv_f32.hip).  Every job is summed exactly as its own launch would sum it and jobs
-//    are applied in submission order (a job whose destination already appears in the batch being assembled starts a new launch), so
-//    the accumulated gradients are bit-identical to the undeferred ones.
+//    per-wave partials; instead of one dependent ~5 us reduction launch behind each of them (~550 per HiLAM step) the jobs of the calls
+//    made with defer = 1 are queued and reduced GRAD_BATCH at a time by grad_reduce_batch_kernel (block -> (job, block of the job)
+//    through a prefix table in the kernel arguments; the pattern of wgrad_reduce_batch, conv_f32.hip).  Every job is summed exactly as
+//    its own launch would sum it and jobs are applied in submission order (a job whose destination already appears in the batch being
+//    assembled starts a new launch), so the accumulated gradients are bit-identical to the undeferred ones.
 #include <mutex>
 #include <vector>
 
@@ -378,7 +378,6 @@ struct Pending {
 };
 std::mutex g_mu;
 std::vector<Pending> g_pending;
-bool g_defer = false;
 
 int launch_batch(const GradBatchArgs& b, hipStream_t st) {
     hipLaunchKernelGGL(grad_reduce_batch_kernel, dim3(b.first[b.n]), dim3(256), 0, st, b);
@@ -412,18 +411,11 @@ int flush_range(const std::vector<Pending>& v, hipStream_t st) {
 
 }  // namespace
 
-bool grad_reduce_deferring() {
-    std::lock_guard<std::mutex> lk(g_mu);
-    return g_defer;
-}
-
-int grad_reduce_submit(const GradReduceJob& job, hipStream_t st) {
-    {
+int grad_reduce_submit(const GradReduceJob& job, hipStream_t st, int defer) {
+    if (defer) {
         std::lock_guard<std::mutex> lk(g_mu);
-        if (g_defer) {
-            g_pending.push_back(Pending{job, st});
-            return P4C_OK;
-        }
+        g_pending.push_back(Pending{job, st});
+        return P4C_OK;
     }
     std::vector<Pending> one{Pending{job, st}};
     return flush_range(one, st);
@@ -433,15 +425,11 @@ int grad_reduce_submit(const GradReduceJob& job, hipStream_t st) {
 
 using namespace p4c;
 
-extern "C" int p4c_grad_reduce_defer(int on) {
+extern "C" int p4c_grad_reduce_drop(void) {
     std::lock_guard<std::mutex> lk(g_mu);
-    const int was = g_defer ? 1 : 0;
-    if (on < 0) {                       // -1: drop what is queued (a backward pass that died before its flush) and reduce at once again
-        g_pending.clear();
-        tn_reduce_drop();
-    }
-    g_defer = on > 0;
-    return was;
+    g_pending.clear();
+    tn_reduce_drop();
+    return P4C_OK;
 }
 
 extern "C" int p4c_grad_reduce_pending(void) {
@@ -526,8 +514,8 @@ extern "C" size_t p4c_node_proj_wgrad_workspace_bytes(int64_t R, int n) {
     return (size_t)wgrad_slots(R) * n * C * C * sizeof(float);
 }
 
-extern "C" int p4c_node_proj_wgrad(const void* const* dy, const void* x, int64_t R, int n, float* const* dw, const int32_t* ld_dw, void* workspace,
-                                   p4c_stream_t stream) {
+extern "C" int p4c_node_proj_wgrad(const void* const* dy, const void* x, int64_t R, int n, float* const* dw, const int32_t* ld_dw, int defer,
+                                   void* workspace, p4c_stream_t stream) {
     static const int32_t ld_any[3] = {C, C, C};
     static const float dummy = 0.f;
     const float* wfake[3] = {&dummy, &dummy, &dummy};
@@ -563,5 +551,5 @@ extern "C" int p4c_node_proj_wgrad(const void* const* dy, const void* x, int64_t
         job.p[i] = dw[i];
         job.ld[i] = ld_dw[i];
     }
-    return grad_reduce_submit(job, st);
+    return grad_reduce_submit(job, st, defer);
 }

@@ -15,7 +15,7 @@ What runs where (bf16 activations, ``activation_dtype: bf16``; state after round
   summed inside the data-gradient launch;
 * aggregation: a CSR segment sum (csrc/graph.hip; no atomics, reproducible), its adjoint an edge gather;
 * parameter gradients: added straight into the parameters' ``.grad`` buffers by one batched reduction per backward pass
-  (ops_nodeproj.GradQueue) -- no per-parameter AccumulateGrad launch, no per-call reduction launch;
+  (_lib.GradQueue) -- no per-parameter AccumulateGrad launch, no per-call reduction launch;
 * the fp32 flavour (``activation_dtype: f32``, parity) keeps library GEMMs for the Linears and the row LayerNorm / gather kernels.
 The batch dimension is folded into the node dimension (edge lists replicated with node offsets, cached per batch size).
 Graph models receive (B, ngrid, C_in) and return (B, ngrid, F) (py4cast/lightning.py:526-535).

@@ -1,4 +1,4 @@
-"""Launch grouping for the mesh GNNs (include/py4cast_hip.h: p4c_node_proj_fwd / _dgrad / _wgrad, p4c_grad_reduce_defer / _flush;
+"""Launch grouping for the mesh GNNs (include/py4cast_hip.h: p4c_node_proj_fwd / _dgrad / _wgrad, p4c_grad_reduce_flush;
 csrc/nodeproj.hip).
 
 GraphLAM / HiLAM / HiLAMParallel (config/CLI/model/graphlam.yaml:19-26, hilam.yaml, hilamparallel.yaml; taken from mfai at
@@ -8,82 +8,24 @@ rows, where a launch costs its latency whatever it computes.  Two things cut the
 * ``node_proj``: the 64 x 64 blocks of the distributed first Linears that multiply one node tensor (sender / receiver part of the edge
   MLP, receiver part of the node-update MLP) as ONE launch forward, one for the data gradient (K = 64 n) and one for the weight
   gradients -- instead of n row-GEMMs each way plus, per block, a weight-gradient product, its reduction and a ``+=``;
-* ``GradQueue``: the reductions of the parameter-gradient partials (this module's and ops_mlp.row_mlp's) are queued during a backward
-  pass and run 32 jobs per launch when the autograd engine finishes the pass (``queue_callback``), in submission order: bit-identical
-  to reducing after every call, ~550 dependent 5 us launches fewer per HiLAM step.
+* ``GradQueue`` (_lib.py): the reductions of the parameter-gradient partials (this module's and ops_mlp.row_mlp's) are queued during a
+  backward pass (``defer`` = 1) and run 32 jobs per launch when the autograd engine finishes the pass (``queue_callback``), in
+  submission order: bit-identical to reducing after every call, ~550 dependent 5 us launches fewer per HiLAM step.
 
 No CPU fallback.
 """
 
 import ctypes
-from typing import List, Sequence
+from typing import Sequence
 
 import torch
 
 from . import _lib as L
+from ._lib import GradQueue
 from .ops_rows import grad_view, row_linear
 
 _P3 = ctypes.c_void_p * 3
 _I3 = ctypes.c_int32 * 3
-
-
-class GradQueue:
-    """Deferred reduction of the gradient partials of ONE backward pass.  ``begin(keep)`` (from inside an autograd Function's backward)
-    switches the library to queueing, registers the flush with the engine once per pass and keeps ``keep`` (the partials' workspace)
-    alive until the flush has been enqueued.  Outside a backward pass (no graph task) nothing is deferred."""
-
-    enabled = True          # False: every call reduces at once (the A/B reference of tests/test_nodeproj_gpu.py)
-    _task = -1
-    _keep: List[torch.Tensor] = []
-    _views: List[torch.Tensor] = []      # the .grad regions the queued reductions will add into (told to L.grad_written at the flush)
-    _stream = None
-
-    @classmethod
-    def begin(cls, keep: torch.Tensor) -> None:
-        if not cls.enabled:
-            return
-        task = torch._C._current_graph_task_id()
-        if task < 0:
-            return
-        if cls._task != task:
-            if cls._task >= 0:      # a pass that died before its callback ran: its queued jobs are void
-                L.lib().p4c_grad_reduce_defer(-1)
-                cls._keep, cls._views = [], []
-            cls._task = task
-            cls._stream = torch.cuda.current_stream(keep.device)
-            L.lib().p4c_grad_reduce_defer(1)
-            torch.autograd.Variable._execution_engine.queue_callback(cls.flush)
-        cls._keep.append(keep)
-
-    @classmethod
-    def active(cls) -> bool:
-        """the reductions of the backward pass in progress are being queued"""
-        return cls.enabled and cls._task >= 0 and cls._task == torch._C._current_graph_task_id()
-
-    @classmethod
-    def wrote(cls, views) -> None:
-        """After the launch that produced the partials: ``views`` (regions of parameters' .grad) receive their sums when the queue is
-        flushed -- or have just received them when nothing is being deferred."""
-        if not L.GRAD_SINK_LISTENERS:
-            return
-        views = [v for v in views if v is not None]
-        if cls._task >= 0 and cls._task == torch._C._current_graph_task_id():
-            cls._views.extend(views)
-        else:
-            L.grad_written(*views)
-
-    @classmethod
-    def flush(cls) -> None:
-        if cls._task < 0:
-            return
-        views = cls._views
-        try:
-            L.check(L.lib().p4c_grad_reduce_flush(ctypes.c_void_p(cls._stream.cuda_stream)), "p4c_grad_reduce_flush")
-        finally:
-            L.lib().p4c_grad_reduce_defer(0)
-            cls._task, cls._keep, cls._views, cls._stream = -1, [], [], None
-        if views:
-            L.grad_written(*views)
 
 
 def _arr(tensors: Sequence[torch.Tensor]):
@@ -132,10 +74,10 @@ class _NodeProj(torch.autograd.Function):
                    alg_bytes=R * 128 * (1 + m + (dres is not None)) + m * 64 * 64 * 4, alg_flops=2 * R * 64 * 64 * m)
         gl = [ctx.gws[i] for i in live]
         ws = torch.empty(max(L.lib().p4c_node_proj_wgrad_workspace_bytes(R, m) // 4, 1), dtype=torch.float32, device=x.device)
-        GradQueue.begin(ws)
-        L.call("p4c_node_proj_wgrad", _arr(dyl), L.ptr(x), R, m, _arr(gl), _lds(gl), L.ptr(ws), L.stream(x.device),
+        defer = GradQueue.join(ws, start=True)
+        L.call("p4c_node_proj_wgrad", _arr(dyl), L.ptr(x), R, m, _arr(gl), _lds(gl), int(defer), L.ptr(ws), L.stream(x.device),
                alg_bytes=R * 128 * (1 + m) + ws.numel() * 4, alg_flops=2 * R * 64 * 64 * m)
-        GradQueue.wrote(gl)
+        GradQueue.wrote(gl, defer)
         return (dx,) + none
 
 

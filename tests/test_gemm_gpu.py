@@ -290,12 +290,11 @@ def test_batch_norm_node_with_channel_dropout_and_handed_on_residual(gpu_device)
 
 def test_accumulating_weight_gradients_are_reduced_in_batches_at_the_end_of_the_backward(gpu_device):
     """Round 6: inside a backward pass the split-K slabs of the weight-gradient calls that ADD into .grad buffers are queued and summed 32
-    calls per launch when the pass ends (csrc/gemm.hip: gemm_tn_reduce_batch_kernel, driven by ops_nodeproj.GradQueue).  Same bits as
+    calls per launch when the pass ends (csrc/gemm.hip: gemm_tn_reduce_batch_kernel, driven by _lib.GradQueue).  Same bits as
     one reduction per call -- also for a weight used by several steps of a rollout (its additions stay in submission order) -- and
     nothing is left in the queue."""
     from py4cast_amd import _lib as L
     from py4cast_amd import ops_gemm as G
-    from py4cast_amd.ops_nodeproj import GradQueue
 
     dev = gpu_device
     torch.manual_seed(71)
@@ -318,11 +317,11 @@ def test_accumulating_weight_gradients_are_reduced_in_batches_at_the_end_of_the_
     for mode in (False, True, True):
         for p in params:
             p.grad = torch.zeros_like(p)
-        GradQueue.enabled = mode
+        L.GradQueue.enabled = mode
         try:
             rollout().backward()
         finally:
-            GradQueue.enabled = True
+            L.GradQueue.enabled = True
         assert L.lib().p4c_grad_reduce_pending() == 0
         out.setdefault(mode, []).append([p.grad.clone() for p in params])
     for a, b in zip(out[False][0], out[True][0]):

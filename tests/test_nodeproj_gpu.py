@@ -94,6 +94,7 @@ def test_node_proj_without_gradient_buffers_takes_the_autograd_route(gpu_device)
 
 def _stack(gpu_device, deferred, seed=41, reuse=False):
     """three 'AR steps' of projection -> fused MLP -> projection on shared parameters; returns every accumulated gradient"""
+    from py4cast_amd import _lib as L
     from py4cast_amd import ops_nodeproj as NP
     from py4cast_amd.ops_mlp import row_mlp
 
@@ -106,7 +107,7 @@ def _stack(gpu_device, deferred, seed=41, reuse=False):
     for p in params:
         p.grad = torch.zeros_like(p)
     x = torch.randn(1458, 64, device=gpu_device).bfloat16().requires_grad_(True)
-    NP.GradQueue.enabled = deferred
+    L.GradQueue.enabled = deferred
     try:
         loss = 0.0
         h = x
@@ -119,7 +120,7 @@ def _stack(gpu_device, deferred, seed=41, reuse=False):
             loss = loss + h.float().square().mean()
         loss.backward()
     finally:
-        NP.GradQueue.enabled = True
+        L.GradQueue.enabled = True
     return [p.grad.clone() for p in params] + [x.grad.clone()]
 
 
@@ -136,8 +137,9 @@ def test_deferred_reduction_is_bit_identical(gpu_device, reuse):
     assert L.lib().p4c_grad_reduce_pending() == 0
 
 
-def test_queue_flushes_more_jobs_than_one_launch_holds(gpu_device):
-    """40 independent projections in one backward pass (> 32 jobs per launch) + a flush through the C entry points directly"""
+def test_queue_flushes_more_jobs_than_one_launch_holds_and_drop_empties_it(gpu_device):
+    """40 independent projections in one backward pass (> 32 jobs per launch); then p4c_grad_reduce_drop and a flush through the C
+    entry points directly on the empty queue"""
     from py4cast_amd import _lib as L
     from py4cast_amd.ops_nodeproj import node_proj
 
@@ -152,7 +154,7 @@ def test_queue_flushes_more_jobs_than_one_launch_holds(gpu_device):
         assert _rel(w.grad, ref) < 5e-4
     lib = L.lib()
     assert lib.p4c_grad_reduce_pending() == 0
-    assert lib.p4c_grad_reduce_defer(1) == 0 and lib.p4c_grad_reduce_defer(-1) == 1 and lib.p4c_grad_reduce_defer(0) == 0
+    assert lib.p4c_grad_reduce_drop() == 0 and lib.p4c_grad_reduce_pending() == 0
     L.check(lib.p4c_grad_reduce_flush(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
 

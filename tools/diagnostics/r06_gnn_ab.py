@@ -6,11 +6,12 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import bench  # noqa: E402
+from py4cast_amd import _lib as L  # noqa: E402
 from py4cast_amd import ops_nodeproj as NP  # noqa: E402
 from py4cast_amd import ops_rows as R  # noqa: E402
 
 if os.environ.get("P4C_R06_NO_DEFER") == "1":
-    NP.GradQueue.enabled = False
+    L.GradQueue.enabled = False
 if os.environ.get("P4C_R06_OLD_PROJ") == "1":
     def old(x, weights, grads_in_place=True):
         weights = list(weights)
