@@ -6,7 +6,8 @@
 //             buffer (pixel stride ld, the caller points at channel C); the 2x2 / stride-2 max of the stored values -> pool (B, H/2, W/2, C).
 //   backward: one pass: dA = dskip + the pooled gradient routed to its window's maximum (ties: the first maximum in the scan order
 //             (0,0) (0,1) (1,0) (1,1), as torch's max_pool2d), dz = dA * relu'(a) -> dz (B, H, W, C), and the batch-norm backward sums
-//             of p4c_inorm_reduce (sum dz, sum dz xhat) in its partial layout [blk][2][C] -> p4c_inorm_finalize_bwd, p4c_inorm_apply.
+//             of p4c_inorm_reduce (sum dz, sum dz xhat, of dz in fp32 before its rounding to the storage type) in its partial layout
+//             [blk][2][C] -> p4c_inorm_finalize_bwd, p4c_inorm_apply.
 // Thread = 4 channels of one 2x2 window (16 B fp32 / 8 B bf16 per pixel); fixed-order sums (bit-identical reruns).
 #include "common.hpp"
 
@@ -96,11 +97,12 @@ __global__ void __launch_bounds__(256) enc_tail_bwd_kernel(const T* __restrict__
                     d[j] = a[k][j] > 0.f ? da : 0.f;
                 }
                 store4f(dz + px[k] * C + c, d);
-                const p4c_f32x4 dr = load4f(dz + px[k] * C + c);     // the stored gradient: what the apply pass reads
+                // the sums take dz before it is rounded to the storage type: dgamma / dbeta are the sums of the exact dskip + routed dpool
+                // (summing the stored bf16 values instead put ~2^-9 relative noise per routed element into them, 3e-3 in the 2-norm)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    s0[j] += dr[j];
-                    s1[j] = __builtin_fmaf(dr[j], (v[j] - mu[j]) * rs[j], s1[j]);
+                    s0[j] += d[j];
+                    s1[j] = __builtin_fmaf(d[j], (v[j] - mu[j]) * rs[j], s1[j]);
                 }
             }
         }

@@ -54,6 +54,7 @@ def _step(lm, case):
     ("HiLAM", 3, "scaled_ar", 2e-3),
     ("HiLAMParallel", 3, "scaled_ar", 2e-3),
     ("UNetRPP", 6, "diff_ar", 2e-2),         # configuration 5 (6-step diff_ar)
+    ("UNet", 3, "scaled_ar", 1e-4),          # bench.py --model UNet (measured 1.1e-5: every convolution native, batch statistics)
 ])
 def test_bench_workload_of_every_model_family(gpu_device, tmp_path_factory, model, T, strategy, loss_tol):
     """The benchmark workload of each widened model: finite prediction of the right shape, forced borders equal to the targets bit

@@ -40,10 +40,27 @@ def gen(dev, seed):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("C", [64, 128, 256, 512])
 def test_enc_tail_against_float64(gpu_device, dtype, C):
+    _check_enc_tail(gpu_device, dtype, 3, 6, 10, C)
+
+
+# the backward's launch plan at the model's sizes: 256 / (C / 4) windows per workgroup, at most BWD_BLOCKS_MAX = 1024 workgroups -- past
+# that a thread loops over several windows and sums their batch-norm terms: 2 x 512 x 512 x 64 (level 1 at the benchmark size) would
+# need 8 192 workgroups, 2 x 128 x 128 x 256 8 192, 2 x 64 x 64 x 512 4 096;
+# C = 4 (256 windows per workgroup), C = 12 (three channel quads: 85 windows, one idle thread), C = 1024 (one window, the whole
+# workgroup on one window's channels); H = 2: one pooled row; eval: the running statistics, the mean / variance terms zeroed
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("B,H,W,C,training", [
+    (2, 512, 512, 64, True), (2, 128, 128, 256, True), (2, 64, 64, 512, True),
+    (3, 6, 10, 4, True), (3, 6, 10, 12, True), (3, 6, 10, 1024, True), (2, 2, 10, 64, True),
+    (3, 6, 10, 128, False), (2, 128, 128, 256, False),
+])
+def test_enc_tail_plans_against_float64(gpu_device, dtype, B, H, W, C, training):
+    _check_enc_tail(gpu_device, dtype, B, H, W, C, training)
+
+
+def _check_enc_tail(dev, dtype, B, H, W, C, training=True):
     from py4cast_amd.unet import enc_tail
 
-    dev = gpu_device
-    B, H, W = 3, 6, 10
     g = gen(dev, C)
     y = torch.randn(B, H, W, C, device=dev, generator=g)
     y[:, :2, :4] = 0.75                                # flat regions: pooling windows with ties
@@ -53,12 +70,18 @@ def test_enc_tail_against_float64(gpu_device, dtype, C):
     with torch.no_grad():
         bn.weight.uniform_(0.5, 1.5, generator=g)
         bn.bias.uniform_(-0.2, 0.2, generator=g)
+        if not training:
+            bn.running_mean.uniform_(-0.3, 0.3, generator=g)
+            bn.running_var.uniform_(0.5, 2.0, generator=g)
+    if not training:
+        bn.eval()
+    rm64, rv64 = (None, None) if training else (bn.running_mean.double(), bn.running_var.double())
     yg = y.clone().requires_grad_(True)
     buf, pool = enc_tail(yg, None, bn)
     act = buf[..., C:]
     # reference forward in float64 from the same y
     y64 = y.double().requires_grad_(True)
-    z64 = F.batch_norm(y64.permute(0, 3, 1, 2), None, None, bn.weight.double(), bn.bias.double(), True, 0.1, bn.eps)
+    z64 = F.batch_norm(y64.permute(0, 3, 1, 2), rm64, rv64, bn.weight.double(), bn.bias.double(), training, 0.1, bn.eps)
     a64 = torch.relu(z64).permute(0, 2, 3, 1)
     if dtype == torch.bfloat16:
         close_bf16(act.float(), a64, "skip")
@@ -82,7 +105,8 @@ def test_enc_tail_against_float64(gpu_device, dtype, C):
     gamma64 = bn.weight.double().detach().requires_grad_(True)
     beta64 = bn.bias.double().detach().requires_grad_(True)
     y64b = y.double().requires_grad_(True)
-    z = F.batch_norm(y64b.permute(0, 3, 1, 2), None, None, gamma64, beta64, True, 0.1, bn.eps).permute(0, 2, 3, 1)
+    z = F.batch_norm(y64b.permute(0, 3, 1, 2), None if rm64 is None else rm64.clone(), None if rv64 is None else rv64.clone(), gamma64,
+                     beta64, training, 0.1, bn.eps).permute(0, 2, 3, 1)
     z.backward(dz)
     if dtype == torch.bfloat16:
         close_bf16(yg.grad.float(), y64b.grad, "dy")
@@ -95,14 +119,27 @@ def test_enc_tail_against_float64(gpu_device, dtype, C):
 # ------------------------------------------------------------------------------------------------ kernel (b): transposed convolution
 @pytest.mark.parametrize("Cin,Cout", [(1024, 512), (512, 256), (256, 128), (128, 64)])
 def test_upconv_against_float64(gpu_device, Cin, Cout):
+    _check_upconv(gpu_device, 2, 5, 7, Cin, Cout)       # ragged: 70 rows, off the 128-row tiles
+
+
+# the four transposed convolutions of the benchmark grid (2 x 512 x 512, f = 64): upconv4 (M = 2 048 rows, 16 row tiles) runs without
+# split-K and the sub-pixel epilogue inside the GEMM kernel across tile boundaries; W = 20, H = 13, B = 3: 128-row tiles straddle image
+# rows and samples; no bias
+@pytest.mark.parametrize("B,H,W,Cin,Cout,bias", [
+    (2, 32, 32, 1024, 512, True), (2, 64, 64, 512, 256, True), (2, 128, 128, 256, 128, True), (2, 256, 256, 128, 64, True),
+    (3, 13, 20, 256, 128, True), (3, 13, 20, 1024, 512, True), (2, 16, 16, 512, 256, False),
+])
+def test_upconv_plans_against_float64(gpu_device, B, H, W, Cin, Cout, bias):
+    _check_upconv(gpu_device, B, H, W, Cin, Cout, bias)
+
+
+def _check_upconv(dev, B, H, W, Cin, Cout, bias=True):
     from py4cast_amd.unet import upconv_into
 
-    dev = gpu_device
-    B, H, W = 2, 5, 7                                  # ragged: 70 rows, off the 128-row tiles
     g = gen(dev, Cin)
     x = torch.randn(B, H, W, Cin, device=dev, generator=g).to(torch.bfloat16)
     w = (torch.randn(Cin, Cout, 2, 2, device=dev, generator=g) / Cin ** 0.5).requires_grad_(True)
-    b = (0.1 * torch.randn(Cout, device=dev, generator=g)).requires_grad_(True)
+    b = (0.1 * torch.randn(Cout, device=dev, generator=g)).requires_grad_(True) if bias else None
     sentinel = torch.randn(B, 2 * H, 2 * W, Cout, device=dev, generator=g).to(torch.bfloat16)
     buf = torch.empty(B, 2 * H, 2 * W, 2 * Cout, device=dev, dtype=torch.bfloat16)
     buf[..., Cout:] = sentinel
@@ -111,7 +148,7 @@ def test_upconv_against_float64(gpu_device, Cin, Cout):
     out = upconv_into(xg, w, b, base.clone())
     assert torch.equal(out[..., Cout:], sentinel)       # the skip half is untouched
     wq = w.detach().to(torch.bfloat16).double().requires_grad_(True)
-    bd = b.detach().double().requires_grad_(True)
+    bd = b.detach().double().requires_grad_(True) if bias else None
     xd = x.double().requires_grad_(True)
     ref = F.conv_transpose2d(xd.permute(0, 3, 1, 2), wq, bd, stride=2).permute(0, 2, 3, 1)
     ref_cat = torch.cat((ref, sentinel.double()), dim=-1)
@@ -120,15 +157,15 @@ def test_upconv_against_float64(gpu_device, Cin, Cout):
     out.backward(dout)
     ref_cat.backward(dout.double())
     close_bf16(xg.grad.float(), xd.grad, "upconv dx")
-    assert rel(w.grad, wq.grad) <= 5e-4 and rel(b.grad, bd.grad) <= 5e-4
+    assert rel(w.grad, wq.grad) <= 5e-4 and (not bias or rel(b.grad, bd.grad) <= 5e-4)
     assert torch.equal(base.grad[..., Cout:], dout[..., Cout:])      # the skip half's gradient passes through
     assert not base.grad[..., :Cout].any()                             # the overwritten channels' earlier values get none
     # with the .grad buffers present the weight / bias gradients are ADDED there by the reduction (ops_gemm's convention)
-    gw0, gb0, gx0 = w.grad.clone(), b.grad.clone(), xg.grad.clone()
+    gw0, gb0, gx0 = w.grad.clone(), b.grad.clone() if bias else None, xg.grad.clone()
     base2 = base.detach().clone().requires_grad_(True)
     out2 = upconv_into(xg, w, b, base2.clone(), grad_owned=True)      # (the model's form: the incoming gradient is zeroed in place)
     out2.backward(dout.clone())
-    assert rel(w.grad, 2 * gw0) <= 1e-6 and rel(b.grad, 2 * gb0) <= 1e-6 and rel(xg.grad, 2 * gx0) <= 1e-6
+    assert rel(w.grad, 2 * gw0) <= 1e-6 and (not bias or rel(b.grad, 2 * gb0) <= 1e-6) and rel(xg.grad, 2 * gx0) <= 1e-6
     assert torch.equal(base2.grad[..., Cout:], dout[..., Cout:]) and not base2.grad[..., :Cout].any()
 
 
