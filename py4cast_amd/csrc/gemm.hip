@@ -927,7 +927,7 @@ __global__ void __launch_bounds__(256) scale_fold_bwd_kernel(const float* __rest
     for (int k = threadIdx.x; k < K; k += 256) {
         const float r = dw_raw[(int64_t)c * K + k];
         dot += r * w[(int64_t)c * K + k];
-        const float v = g * r;
+        const float v = __fmul_rn(g, r);      // (rounded before the add: no fused multiply-add, .grad = prefill + g (.) dW_raw exactly)
         dw[(int64_t)c * K + k] = accumulate ? dw[(int64_t)c * K + k] + v : v;
     }
     dot = wave_sum(dot);
@@ -938,7 +938,8 @@ __global__ void __launch_bounds__(256) scale_fold_bwd_kernel(const float* __rest
         const float dbr = db_raw ? db_raw[c] : 0.f;
         if (b) t += b[c] * dbr;
         dgamma[c] = accumulate ? dgamma[c] + t : t;
-        if (db) db[c] = accumulate ? db[c] + g * dbr : g * dbr;
+        const float gb = __fmul_rn(g, dbr);
+        if (db) db[c] = accumulate ? db[c] + gb : gb;
     }
 }
 }}  // namespace p4c::gemm

@@ -633,10 +633,13 @@ __global__ void __launch_bounds__(256) sum_leading_kernel(const T* __restrict__ 
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
     p4c_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (accumulate) acc = load4f(out + i);
     for (int b = 0; b < nb; ++b) {
         const p4c_f32x4 v = load4f(x + (int64_t)b * n + i);
         acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2]; acc[3] += v[3];
+    }
+    if (accumulate) {      // the finished sum is added once: .grad = prefill + g, as autograd's accumulation would give
+        const p4c_f32x4 o = load4f(out + i);
+        acc[0] = o[0] + acc[0]; acc[1] = o[1] + acc[1]; acc[2] = o[2] + acc[2]; acc[3] = o[3] + acc[3];
     }
     store4f(out + i, acc);
 }
