@@ -919,6 +919,36 @@ int p4c_unet_enc_tail_bwd(const void* y, const void* act, int64_t lda, const voi
 int p4c_upsample_bilinear_fwd(const void* x, const void* skip, void* out, int B, int H, int W, int C, int scale, p4c_stream_t stream);
 int p4c_upsample_bilinear_bwd(const void* dout, void* dx, int B, int H, int W, int C, int scale, p4c_stream_t stream);
 
+/* Segformer (csrc/segformer.hip), features-last bf16 storage, fp32 arithmetic, fixed-order sums (no atomics).
+ * Patch gather: cols (B Ho Wo, C k^2) with column c k^2 + ky k + kx = x[b][oy stride - pad + ky][ox stride - pad + kx][c] (zero outside),
+ * nn.Unfold's order; scatter: its adjoint dx[..][c] for c < cgrad (gather form, ky then kx), dx of pixel stride C.
+ * Channel LayerNorm (lucidrains): y = (x - mean) / (std + eps) g + b over the C features of each row (C up to 512), stats [R][2] =
+ * (mean, biased std); backward: dx (+ dadd), partial [p4c_seg_chan_ln_bwd_blocks][2][C] = (sum dy xhat, sum dy).
+ * p4c_seg_reduce_partials: out1[e] (+)= sum_r partial[r][e] (e < n1), out2[e - n1] likewise (n1 <= e < n1 + n2), r in order.
+ * Depthwise 3x3 (padding 1): w (C, 9) fp32, bias (C) or NULL, C a multiple of 8; wgrad: partial [p4c_seg_dw3x3_wgrad_rows][10 C] =
+ * (dw (C, 9) | db (C)) for p4c_seg_reduce_partials(n1 = 9 C, n2 = C).
+ * Spatial-reduction attention, head_dim 32: q / out / dout / dq rows (B, Nq, heads 32), kv / dkv rows (B, Nk, 2 heads 32) (keys in the
+ * first heads 32 columns), Nk up to 256; lse (B, heads, Nq) fp32 written by the forward; the backward's workspace holds per-tile dK / dV.
+ * Decoder sum: out (B, H, W, C) = z0 + sum_{l=1..3} nearest_up_{2^l}(z_l), z_l (B, H / 2^l, W / 2^l, C); backward: dz_l = 2^l x 2^l block
+ * sums of dout (dz0 = dout). */
+int p4c_seg_patch_gather(const void* x, void* cols, int B, int H, int W, int C, int k, int stride, int pad, p4c_stream_t stream);
+int p4c_seg_patch_scatter(const void* dcols, void* dx, int B, int H, int W, int C, int k, int stride, int pad, int cgrad, p4c_stream_t stream);
+int p4c_seg_chan_ln_fwd(const void* x, const float* g, const float* b, float eps, void* y, float* stats, int64_t R, int C, p4c_stream_t stream);
+int p4c_seg_chan_ln_bwd_blocks(int64_t R);
+int p4c_seg_chan_ln_bwd(const void* x, const void* dy, const float* g, const float* stats, float eps, const void* dadd, void* dx, float* partial,
+                        int64_t R, int C, p4c_stream_t stream);
+int p4c_seg_reduce_partials(const float* partial, int nb, int n1, float* out1, int n2, float* out2, int accumulate, p4c_stream_t stream);
+int p4c_seg_dw3x3_fwd(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, p4c_stream_t stream);
+int p4c_seg_dw3x3_dgrad(const void* dy, const float* w, void* dx, int B, int H, int W, int C, p4c_stream_t stream);
+int p4c_seg_dw3x3_wgrad_rows(int B, int H, int W);
+int p4c_seg_dw3x3_wgrad(const void* x, const void* dy, float* partial, int B, int H, int W, int C, p4c_stream_t stream);
+int p4c_seg_sra_fwd(const void* q, const void* kv, void* out, float* lse, int B, int Nq, int Nk, int heads, float scale, p4c_stream_t stream);
+size_t p4c_seg_sra_bwd_workspace_bytes(int B, int Nq, int Nk, int heads);
+int p4c_seg_sra_bwd(const void* q, const void* kv, const void* out, const void* dout, const float* lse, void* dq, void* dkv, float* workspace,
+                    int B, int Nq, int Nk, int heads, float scale, p4c_stream_t stream);
+int p4c_seg_upsum_fwd(const void* z0, const void* z1, const void* z2, const void* z3, void* out, int B, int H, int W, int C, p4c_stream_t stream);
+int p4c_seg_upsum_bwd(const void* dout, void* dz1, void* dz2, void* dz3, int B, int H, int W, int C, p4c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,18 @@ SIGNATURES = {
     "p4c_gemm_upconv_wgrad": [P, L, P, L, I, I, I, I, I, P, P, I, P, P],
     "p4c_unet_enc_tail_fwd": [P, P, P, P, L, P, I, I, I, I, I, P],
     "p4c_unet_enc_tail_bwd": [P, P, L, P, L, P, P, P, P, P, I, I, I, I, I, P],
+    "p4c_seg_patch_gather": [P, P, I, I, I, I, I, I, I, P],
+    "p4c_seg_patch_scatter": [P, P, I, I, I, I, I, I, I, I, P],
+    "p4c_seg_chan_ln_fwd": [P, P, P, F, P, P, L, I, P],
+    "p4c_seg_chan_ln_bwd": [P, P, P, P, F, P, P, P, L, I, P],
+    "p4c_seg_reduce_partials": [P, I, I, P, I, P, I, P],
+    "p4c_seg_dw3x3_fwd": [P, P, P, P, I, I, I, I, P],
+    "p4c_seg_dw3x3_dgrad": [P, P, P, I, I, I, I, P],
+    "p4c_seg_dw3x3_wgrad": [P, P, P, I, I, I, I, P],
+    "p4c_seg_sra_fwd": [P, P, P, P, I, I, I, I, F, P],
+    "p4c_seg_sra_bwd": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
+    "p4c_seg_upsum_fwd": [P, P, P, P, P, I, I, I, I, P],
+    "p4c_seg_upsum_bwd": [P, P, P, P, I, I, I, I, P],
 }
 OTHER = {
     "p4c_conv_wgrad_workspace_bytes": ([I, I], c_size_t),
@@ -131,4 +143,7 @@ OTHER = {
     "p4c_gemm_nt_stat_blocks": ([I, I, I], c_int),
     "p4c_gemm_tn_workspace_bytes": ([I, I, I], c_size_t),
     "p4c_unet_enc_tail_bwd_blocks": ([I, I, I, I], c_int),
+    "p4c_seg_chan_ln_bwd_blocks": ([L], c_int),
+    "p4c_seg_dw3x3_wgrad_rows": ([I, I, I], c_int),
+    "p4c_seg_sra_bwd_workspace_bytes": ([I, I, I, I], c_size_t),
 }
