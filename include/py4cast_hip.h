@@ -859,7 +859,8 @@ int p4c_gemm_scale_fold_bwd(const float* dw_raw, const float* db_raw, const floa
                             float* dw, float* db, float* dgamma, int accumulate, p4c_stream_t stream);
 /* C (M, N) bf16 = epilogue(A x Bimg^T), Bimg (N, K) bf16 with K contiguous (p4c_gemm_prep_weight), fp32 accumulation.
  * taps = 1: A = (M, K) bf16 rows, row stride lda.  taps = 9: A = an NHWC map (batch, H, W, Cin), M = batch * H * W pixels, pixel
- * stride lda >= Cin, K = 9 * Cin: the 3x3 "same" convolution with zero padding (no im2col buffer).
+ * stride lda >= Cin, K = 9 * Cin: the 3x3 "same" convolution with zero padding (no im2col buffer); dil (1 for taps = 1): its
+ * dilation d -- tap (ky, kx) reads pixel (y + (ky - 1) d, x + (kx - 1) d), padding d, the same weight image.
  * Epilogue, in this order: + bias[n] (fp32, optional); act = 1: the bf16-rounded pre-activation goes to aux_out (row stride ldaux) and
  * GELU (erf form) of it on; act = 2: times GELU'(aux_in) (the data gradient through a GELU); + res[m][n] (bf16, row stride ldr,
  * optional); rounded to bf16 into C (row stride ldc).  stats (optional): [p4c_gemm_nt_stat_blocks][2][N] fp32 column sums and sums of
@@ -868,17 +869,17 @@ int p4c_gemm_scale_fold_bwd(const float* dw_raw, const float* db_raw, const floa
  * order (reruns are bit-identical). */
 size_t p4c_gemm_nt_workspace_bytes(int M, int N, int K);
 int p4c_gemm_nt_stat_blocks(int M, int N, int K);
-int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, int N, int K, int H, int W, int Cin, int taps, const float* bias,
-                const void* res, int64_t ldr, int act, const void* aux_in, void* aux_out, int64_t ldaux, void* C, int64_t ldc,
+int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, int N, int K, int H, int W, int Cin, int taps, int dil,
+                const float* bias, const void* res, int64_t ldr, int act, const void* aux_in, void* aux_out, int64_t ldaux, void* C, int64_t ldc,
                 float* stats, void* workspace, p4c_stream_t stream);
 /* Weight (+ bias) gradient: dw (Mo, Cin, taps) fp32 in the torch layout = sum over the R rows of dy[r][:Mo]^T (x) x[r] -- taps = 9:
- * x's 3x3 neighbourhood of pixel r (x = the NHWC map, R = batch * H * W) --, db (Mo) = column sums of dy (or NULL).  dy / x bf16 rows
+ * x's 3x3 neighbourhood of pixel r with dilation dil (x = the NHWC map, R = batch * H * W) --, db (Mo) = column sums of dy (or NULL).  dy / x bf16 rows
  * with strides ldp / ldq (multiples of 8).  Split over the rows, fp32 slabs summed in a fixed order.  accumulate = 1: dw / db are ADDED
  * to (a parameter's .grad buffer: no AccumulateGrad launch per AR step).  defer = 1 (accumulating calls only): the slabs' reduction joins
  * the queue of p4c_grad_reduce_flush instead of being launched now.  workspace: p4c_gemm_tn_workspace_bytes(R, Mo, taps * Cin) bytes. */
 size_t p4c_gemm_tn_workspace_bytes(int R, int Mo, int No);
-int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t ldq, int R, int Mo, int H, int W, int Cin, int taps, float* dw,
-                float* db, int accumulate, int defer, void* workspace, p4c_stream_t stream);
+int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t ldq, int R, int Mo, int H, int W, int Cin, int taps, int dil,
+                float* dw, float* db, int accumulate, int defer, void* workspace, p4c_stream_t stream);
 /* BatchNorm2d (training mode) statistics from column partial sums [nblk][2][C] over `count` values per channel: mean, rstd,
  * scale = gamma rstd, shift = beta - mean scale (C each, fp32); running_mean / running_var (optional) get torch's momentum update
  * with the unbiased variance, num_batches_tracked (optional, the module's int64 counter) is incremented by one. */
@@ -918,6 +919,10 @@ int p4c_unet_enc_tail_bwd(const void* y, const void* act, int64_t lda, const voi
  * Backward in gather form (fixed order, no atomics): dx from dout; the skip's gradient is dout.  C a multiple of 8. */
 int p4c_upsample_bilinear_fwd(const void* x, const void* skip, void* out, int B, int H, int W, int C, int scale, p4c_stream_t stream);
 int p4c_upsample_bilinear_bwd(const void* dout, void* dx, int B, int H, int W, int C, int scale, p4c_stream_t stream);
+/* The same with align_corners = True (source coordinate o (in - 1) / (out - 1): smp's segmentation head, nn.UpsamplingBilinear2d), no
+ * skip; scale 1..16. */
+int p4c_upsample_bilinear_ac_fwd(const void* x, void* out, int B, int H, int W, int C, int scale, p4c_stream_t stream);
+int p4c_upsample_bilinear_ac_bwd(const void* dout, void* dx, int B, int H, int W, int C, int scale, p4c_stream_t stream);
 
 /* Segformer (csrc/segformer.hip), features-last bf16 storage, fp32 arithmetic, fixed-order sums (no atomics).
  * Patch gather: cols (B Ho Wo, C k^2) with column c k^2 + ky k + kx = x[b][oy stride - pad + ky][ox stride - pad + kx][c] (zero outside),
@@ -948,6 +953,34 @@ int p4c_seg_sra_bwd(const void* q, const void* kv, const void* out, const void* 
                     int B, int Nq, int Nk, int heads, float scale, p4c_stream_t stream);
 int p4c_seg_upsum_fwd(const void* z0, const void* z1, const void* z2, const void* z3, void* out, int B, int H, int W, int C, p4c_stream_t stream);
 int p4c_seg_upsum_bwd(const void* dout, void* dz1, void* dz2, void* dz3, int B, int H, int W, int C, p4c_stream_t stream);
+
+/* DeepLabV3 (csrc/deeplab.hip), features-last bf16 storage, fp32 arithmetic, fixed-order sums (no atomics).
+ * Stem tail: pool (B, Ho, Wo, C) = max_pool2d(relu(y scale + shift), 3, stride 2, padding 1) with Ho = (H - 1) / 2 + 1, the activation
+ * rounded to bf16 before the max; arg (B, Ho, Wo, C) bytes = the window's first maximum in row-major order (0..8).  Backward: dz (B, H,
+ * W, C) = relu'(a) * (sum of the dpool of the windows whose maximum is this pixel) and partial [p4c_deeplab_stem_bwd_blocks][2][C] =
+ * (sum dz, sum dz (y - mean) rstd) for p4c_inorm_finalize_bwd.  C a multiple of 4 up to 1024.
+ * Column sums: partial (B, S, C) fp32, row chunk s of sample b summed in row order (x: B HW rows of stride ld).
+ * Pooling-branch head (ASPP): mean (B, C) = (sum over S of partial) / HW, z (B, D) = mean W^T (w (D, C) fp32), BatchNorm over the B
+ * samples (training: batch statistics, running update with the unbiased variance; eval: the running statistics), ReLU -> out (B, D)
+ * fp32; stat (2, D) = (mean, rstd).  B 2..16 in training.  Backward: gpart (B, S, D) = column sums of the pooled columns' gradient ->
+ * dz (B, D), dgamma / dbeta (D), dw (D, C), dmean (B, C); p4c_deeplab_pool_broadcast: dx (B, HW, C) bf16 = dmean / HW.
+ * Assemble: buf (B HW, 5 D) = [a0 | a1 | a2 | a3 | out of the pixel's sample]; backward: d0..d3 (B HW, D) = the first four slices. */
+int p4c_deeplab_stem_fwd(const void* y, const float* scale, const float* shift, void* pool, void* arg, int B, int H, int W, int C,
+                         p4c_stream_t stream);
+int p4c_deeplab_stem_bwd_blocks(int B, int H, int W, int C);
+int p4c_deeplab_stem_bwd(const void* y, const void* dpool, const void* arg, const float* scale, const float* shift, const float* mean,
+                         const float* rstd, void* dz, float* partial, int B, int H, int W, int C, p4c_stream_t stream);
+int p4c_deeplab_colsum(const void* x, int64_t ld, float* partial, int B, int HW, int C, int S, p4c_stream_t stream);
+int p4c_deeplab_pool_head_fwd(const float* partial, int S, int HW, const float* w, const float* gamma, const float* beta, float eps,
+                              float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, int training, int B,
+                              int C, int D, float* mean, float* z, float* stat, float* out, p4c_stream_t stream);
+int p4c_deeplab_pool_head_bwd(const float* gpart, int S, const float* z, const float* stat, const float* out, const float* gamma,
+                              const float* mean, const float* w, int training, int B, int C, int D, float* dz, float* dgamma,
+                              float* dbeta, float* dw, float* dmean, p4c_stream_t stream);
+int p4c_deeplab_pool_broadcast(const float* dmean, void* dx, int B, int HW, int C, p4c_stream_t stream);
+int p4c_deeplab_assemble_fwd(const void* a0, const void* a1, const void* a2, const void* a3, const float* pooled, void* buf, int B, int HW,
+                             int D, p4c_stream_t stream);
+int p4c_deeplab_assemble_bwd(const void* dbuf, void* d0, void* d1, void* d2, void* d3, int B, int HW, int D, p4c_stream_t stream);
 
 #ifdef __cplusplus
 }

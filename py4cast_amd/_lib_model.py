@@ -95,8 +95,8 @@ SIGNATURES = {
     "p4c_gemm_prep_weight_scaled": [P, P, P, P, I, I, I, P, P, P],
     "p4c_gemm_prep_weight_batch": [I, P, P, P, P, P, P, P, P, P, P],
     "p4c_gemm_scale_fold_bwd": [P, P, P, P, P, I, I, P, P, P, I, P],
-    "p4c_gemm_nt": [P, L, P, I, I, I, I, I, I, I, P, P, L, I, P, P, L, P, L, P, P, P],
-    "p4c_gemm_tn": [P, L, P, L, I, I, I, I, I, I, P, P, I, I, P, P],
+    "p4c_gemm_nt": [P, L, P, I, I, I, I, I, I, I, I, P, P, L, I, P, P, L, P, L, P, P, P],
+    "p4c_gemm_tn": [P, L, P, L, I, I, I, I, I, I, I, P, P, I, I, P, P],
     "p4c_bnorm_finalize": [P, I, ctypes.c_double, I, P, P, F, F, P, P, P, P, P, P, P, P],
     "p4c_upconv_prep_weight": [P, I, I, P, P, P],
     "p4c_gemm_upconv_fwd": [P, L, P, P, I, I, I, I, I, P, L, P, P],
@@ -116,6 +116,16 @@ SIGNATURES = {
     "p4c_seg_sra_bwd": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
     "p4c_seg_upsum_fwd": [P, P, P, P, P, I, I, I, I, P],
     "p4c_seg_upsum_bwd": [P, P, P, P, I, I, I, I, P],
+    "p4c_upsample_bilinear_ac_fwd": [P, P, I, I, I, I, I, P],
+    "p4c_upsample_bilinear_ac_bwd": [P, P, I, I, I, I, I, P],
+    "p4c_deeplab_stem_fwd": [P, P, P, P, P, I, I, I, I, P],
+    "p4c_deeplab_stem_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    "p4c_deeplab_colsum": [P, L, P, I, I, I, I, P],
+    "p4c_deeplab_pool_head_fwd": [P, I, I, P, P, P, F, F, P, P, P, I, I, I, I, P, P, P, P, P],
+    "p4c_deeplab_pool_head_bwd": [P, I, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P],
+    "p4c_deeplab_pool_broadcast": [P, P, I, I, I, P],
+    "p4c_deeplab_assemble_fwd": [P, P, P, P, P, P, I, I, I, P],
+    "p4c_deeplab_assemble_bwd": [P, P, P, P, P, I, I, I, P],
 }
 OTHER = {
     "p4c_conv_wgrad_workspace_bytes": ([I, I], c_size_t),
@@ -146,4 +156,5 @@ OTHER = {
     "p4c_seg_chan_ln_bwd_blocks": ([L], c_int),
     "p4c_seg_dw3x3_wgrad_rows": ([I, I, I], c_int),
     "p4c_seg_sra_bwd_workspace_bytes": ([I, I, I, I], c_size_t),
+    "p4c_deeplab_stem_bwd_blocks": ([I, I, I, I], c_int),
 }

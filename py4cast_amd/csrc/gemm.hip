@@ -170,6 +170,7 @@ struct NtArgs {
     int H, W, Cin, taps;    // taps == 9: 3x3 "same" convolution over (H, W) maps, K = 9 * Cin;  taps == 1: plain rows;  taps == 4
                             // (MODE 2): row m = pixel (h, w) of an (H, W) map gathers the 2x2 block (2h+dy, 2w+dx) of the 2x grid A,
                             // k = (2 dy + dx) * Cin + c -- the data gradient of a 2x2 / stride-2 transposed convolution
+    int dil;                // taps == 9: dilation d -- tap t reads pixel (y + (t / 3 - 1) d, x + (t % 3 - 1) d), padding d; 1 otherwise
     int tiles_m, tiles_n;
     int nkb, splits, kb_per_split;
     float* partial;         // splits > 1: [split][tile][128][128] fp32
@@ -251,7 +252,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_kernel(NtArgs a) {
             const int y = p / a.W, x = p - y * a.W;
 #pragma unroll
             for (int t = 0; t < 9; ++t)
-                if ((unsigned)(y + t / 3 - 1) < (unsigned)a.H && (unsigned)(x + t % 3 - 1) < (unsigned)a.W) vmask[it] |= 1u << t;
+                if ((unsigned)(y + (t / 3 - 1) * a.dil) < (unsigned)a.H && (unsigned)(x + (t % 3 - 1) * a.dil) < (unsigned)a.W) vmask[it] |= 1u << t;
         }
     }
     // the chunk a lane fetches: (lane & 7) ^ (4 it + (lane >> 4))
@@ -260,7 +261,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_kernel(NtArgs a) {
     int kq[2], tap[2], ci[2], shift[2];
     auto tap_shift = [&](int t, int c) __attribute__((always_inline)) {
         if (UPG) return (((t >> 1) * 2 * a.W + (t & 1)) * (int)a.lda + c) * 2;
-        const int dy = t / 3 - 1, dx = t - (t / 3) * 3 - 1;
+        const int dy = (t / 3 - 1) * a.dil, dx = (t - (t / 3) * 3 - 1) * a.dil;
         return ((dy * a.W + dx) * (int)a.lda + c) * 2;
     };
 #pragma unroll
@@ -426,6 +427,7 @@ struct TnArgs {
     unsigned int p_bytes, q_bytes;
     int R, Mo, No;
     int H, W, Cin, taps;
+    int dil;                // CONV: dilation of the 3x3 taps (NtArgs::dil)
     int tiles_i, tiles_j;
     int nrb, splits, rb_per_split;
     float* partial;         // [split][tile][128][128]
@@ -493,8 +495,8 @@ __global__ void __launch_bounds__(512, 2) gemm_tn_kernel(TnArgs a) {
             int col = j0 + chk * 8;
             const int tap = col / a.Cin;
             col -= tap * a.Cin;
-            qdy[it] = tap / 3 - 1;
-            qdx[it] = tap - (tap / 3) * 3 - 1;
+            qdy[it] = (tap / 3 - 1) * a.dil;
+            qdx[it] = (tap - (tap / 3) * 3 - 1) * a.dil;
             q_off[it] = (unsigned int)((int64_t)rr * a.ldq * 2 + ((qdy[it] * a.W + qdx[it]) * (int)a.ldq + col) * 2);
             const int p = rr % (a.H * a.W);
             py[it] = p / a.W;
@@ -981,13 +983,14 @@ extern "C" int p4c_gemm_nt_stat_blocks(int M, int N, int K) {
 }
 
 // C = epilogue(A x Bimg^T).  taps == 1: A = (M, K) rows with row stride lda.  taps == 9: A = an NHWC map (batch, H, W, Cin) with
-// M = batch * H * W pixels and pixel stride lda (>= Cin), K = 9 * Cin: the 3x3 "same" convolution (zero padding).
-extern "C" int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, int N, int K, int H, int W, int Cin, int taps,
+// M = batch * H * W pixels and pixel stride lda (>= Cin), K = 9 * Cin: the 3x3 "same" convolution with dilation dil (zero padding dil).
+extern "C" int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, int N, int K, int H, int W, int Cin, int taps, int dil,
                            const float* bias, const void* res, int64_t ldr, int act, const void* aux_in, void* aux_out, int64_t ldaux,
                            void* C, int64_t ldc, float* stats, void* workspace, p4c_stream_t stream) {
     P4C_CHECK_ARG(A && Bimg && C, "p4c_gemm_nt: NULL pointer");
     P4C_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0, "p4c_gemm_nt: M=%d N=%d K=%d (N, K multiples of 8)", M, N, K);
     P4C_CHECK_ARG(taps == 1 || taps == 9, "p4c_gemm_nt: taps must be 1 or 9");
+    P4C_CHECK_ARG(dil == 1 || (taps == 9 && dil > 1 && dil < 4096), "p4c_gemm_nt: dil=%d (1, or 2 ... 4095 for the 3x3 convolution)", dil);
     P4C_CHECK_ARG(lda % 8 == 0 && ldc % 8 == 0 && ldc >= N, "p4c_gemm_nt: row strides must be multiples of 8 (ldc >= N)");
     if (taps == 9) {
         P4C_CHECK_ARG(H > 0 && W > 0 && Cin > 0 && Cin % 8 == 0 && K == 9 * Cin && M % (H * W) == 0 && lda >= Cin,
@@ -1003,7 +1006,7 @@ extern "C" int p4c_gemm_nt(const void* A, int64_t lda, const void* Bimg, int M, 
     NtArgs a;
     a.A = (const bf16*)A; a.B = (const bf16*)Bimg; a.lda = lda; a.ldb = K;
     a.a_bytes = (unsigned int)a_bytes; a.b_bytes = (unsigned int)b_bytes;
-    a.M = M; a.N = N; a.K = K; a.H = H; a.W = W; a.Cin = Cin; a.taps = taps;
+    a.M = M; a.N = N; a.K = K; a.H = H; a.W = W; a.Cin = Cin; a.taps = taps; a.dil = dil;
     nt_plan(M, N, K, &a.tiles_m, &a.tiles_n, &a.nkb, &a.splits, &a.kb_per_split);
     P4C_CHECK_ARG(a.splits == 1 || workspace, "p4c_gemm_nt: this shape runs split-K: workspace of p4c_gemm_nt_workspace_bytes required");
     a.partial = (float*)workspace;
@@ -1100,8 +1103,9 @@ int tn_reduce_flush(hipStream_t st) {
 }
 }  // namespace p4c
 
-// dW (Mo, Cin, taps) fp32 = sum over the R rows of dy^T (x) [x or its 3x3 im2col view], db (Mo) = column sums of dy (or NULL)
-extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t ldq, int R, int Mo, int H, int W, int Cin, int taps,
+// dW (Mo, Cin, taps) fp32 = sum over the R rows of dy^T (x) [x or its 3x3 im2col view with dilation dil], db (Mo) = column sums of dy
+// (or NULL)
+extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t ldq, int R, int Mo, int H, int W, int Cin, int taps, int dil,
                            float* dw, float* db, int accumulate, int defer, void* workspace, p4c_stream_t stream) {
     P4C_CHECK_ARG(dy && x && dw && workspace, "p4c_gemm_tn: NULL pointer");
     P4C_CHECK_ARG(!defer || accumulate, "p4c_gemm_tn: only an accumulating call can defer its reduction");
@@ -1109,12 +1113,13 @@ extern "C" int p4c_gemm_tn(const void* dy, int64_t ldp, const void* x, int64_t l
                   Cin, taps);
     P4C_CHECK_ARG(ldp % 8 == 0 && ldq % 8 == 0 && ldp >= Mo && ldq >= Cin, "p4c_gemm_tn: row strides must be multiples of 8 covering the rows");
     P4C_CHECK_ARG(taps == 1 || (H > 0 && W > 0 && R % (H * W) == 0), "p4c_gemm_tn: convolution needs R a multiple of H W");
+    P4C_CHECK_ARG(dil == 1 || (taps == 9 && dil > 1 && dil < 4096), "p4c_gemm_tn: dil=%d (1, or 2 ... 4095 for the 3x3 convolution)", dil);
     const int64_t p_bytes = (int64_t)R * ldp * 2, q_bytes = (int64_t)R * ldq * 2;
     P4C_CHECK_ARG(p_bytes < 0x7fffffffLL && q_bytes < 0x7fffffffLL, "p4c_gemm_tn: operands beyond 2 GiB");
     TnArgs a;
     a.up_C = 0;
     a.P = (const bf16*)dy; a.Q = (const bf16*)x; a.ldp = ldp; a.ldq = ldq; a.p_bytes = (unsigned int)p_bytes; a.q_bytes = (unsigned int)q_bytes;
-    a.R = R; a.Mo = Mo; a.No = taps * Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = taps;
+    a.R = R; a.Mo = Mo; a.No = taps * Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = taps; a.dil = dil;
     tn_plan(R, Mo, a.No, &a.tiles_i, &a.tiles_j, &a.nrb, &a.splits, &a.rb_per_split);
     const int tiles = a.tiles_i * a.tiles_j;
     a.partial = (float*)workspace;
@@ -1224,7 +1229,7 @@ extern "C" int p4c_gemm_upconv_fwd(const void* x, int64_t ldx, const void* fwd_i
     NtArgs a;
     a.A = (const bf16*)x; a.B = (const bf16*)fwd_img; a.lda = ldx; a.ldb = Cin;
     a.a_bytes = (unsigned int)(M * ldx * 2); a.b_bytes = (unsigned int)((int64_t)4 * Cout * Cin * 2);
-    a.M = (int)M; a.N = 4 * Cout; a.K = Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = 1;
+    a.M = (int)M; a.N = 4 * Cout; a.K = Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = 1; a.dil = 1;
     upconv_epi_clear(a.e);
     a.e.bias = bias; a.e.C = (bf16*)out; a.e.ldc = ldo; a.e.up_W = W; a.e.up_C = Cout;
     return upconv_nt_launch(a, 0, workspace, as_stream(stream));
@@ -1241,7 +1246,7 @@ extern "C" int p4c_gemm_upconv_dgrad(const void* dup, int64_t ldd, const void* d
     NtArgs a;
     a.A = (const bf16*)dup; a.B = (const bf16*)dgrad_img; a.lda = ldd; a.ldb = 4 * Cout;
     a.a_bytes = (unsigned int)(4 * M * ldd * 2); a.b_bytes = (unsigned int)((int64_t)4 * Cout * Cin * 2);
-    a.M = (int)M; a.N = Cin; a.K = 4 * Cout; a.H = H; a.W = W; a.Cin = Cout; a.taps = 4;
+    a.M = (int)M; a.N = Cin; a.K = 4 * Cout; a.H = H; a.W = W; a.Cin = Cout; a.taps = 4; a.dil = 1;
     upconv_epi_clear(a.e);
     a.e.C = (bf16*)dx; a.e.ldc = ldx;
     return upconv_nt_launch(a, 2, workspace, as_stream(stream));
@@ -1258,7 +1263,7 @@ extern "C" int p4c_gemm_upconv_wgrad(const void* dup, int64_t ldd, const void* x
     TnArgs a;
     a.P = (const bf16*)dup; a.Q = (const bf16*)x; a.ldp = ldd; a.ldq = ldx;
     a.p_bytes = (unsigned int)(4 * R * ldd * 2); a.q_bytes = (unsigned int)(R * ldx * 2);
-    a.R = (int)R; a.Mo = 4 * Cout; a.No = Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = 1; a.up_C = Cout;
+    a.R = (int)R; a.Mo = 4 * Cout; a.No = Cin; a.H = H; a.W = W; a.Cin = Cin; a.taps = 1; a.dil = 1; a.up_C = Cout;
     tn_plan(a.R, a.Mo, a.No, &a.tiles_i, &a.tiles_j, &a.nrb, &a.splits, &a.rb_per_split);
     const int tiles = a.tiles_i * a.tiles_j;
     a.partial = (float*)workspace;

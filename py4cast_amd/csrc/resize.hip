@@ -115,6 +115,91 @@ __global__ void __launch_bounds__(256) upsample_bwd_kernel(const bf16* __restric
     }
 }
 
+// align_corners = True (smp's segmentation head, nn.UpsamplingBilinear2d): source coordinate o (in - 1) / (out - 1), as torch's
+// area_pixel_compute_scale / _source_index compute it in fp32
+__device__ __forceinline__ void src_index_ac(int o, float sc, int in_size, int& i0, int& i1, float& lam) {
+    const float s = sc * (float)o;
+    i0 = (int)s;
+    if (i0 > in_size - 1) i0 = in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    lam = s - (float)i0;
+}
+__host__ __device__ inline float ac_scale(int in_size, int out_size) { return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f; }
+
+__global__ void __launch_bounds__(256) upsample_ac_fwd_kernel(const bf16* __restrict__ x, bf16* __restrict__ out, int B, int H, int W, int C, int scale) {
+    const int OH = H * scale, OW = W * scale, cq = C >> 3;
+    const float sy = ac_scale(H, OH), sx = ac_scale(W, OW);
+    const int64_t total = (int64_t)B * OH * OW * cq;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int q = (int)(i % cq);
+        int64_t p = i / cq;
+        const int ox = (int)(p % OW);
+        p /= OW;
+        const int oy = (int)(p % OH), b = (int)(p / OH);
+        int y0, y1, x0, x1;
+        float ly, lx;
+        src_index_ac(oy, sy, H, y0, y1, ly);
+        src_index_ac(ox, sx, W, x0, x1, lx);
+        const bf16* xb = x + (int64_t)b * H * W * C + 8 * q;
+        float a[8], bq[8], c[8], d[8], o[8];
+        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y0 * W + x0) * C), a);
+        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y0 * W + x1) * C), bq);
+        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y1 * W + x0) * C), c);
+        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y1 * W + x1) * C), d);
+        const float hy0 = 1.f - ly, wx0 = 1.f - lx;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = hy0 * (wx0 * a[j] + lx * bq[j]) + ly * (wx0 * c[j] + lx * d[j]);
+        *reinterpret_cast<u32x4*>(out + (((int64_t)b * OH + oy) * OW + ox) * C + 8 * q) = pack8(o);
+    }
+}
+
+// output rows that may read input row i: s o in [i - 1, i + 1] (a conservative range; the loop checks each one exactly)
+__device__ __forceinline__ void ac_range(int i, float sc, int out_size, int& lo, int& hi) {
+    if (sc <= 0.f) { lo = 0; hi = out_size - 1; return; }
+    lo = max(0, (int)floorf((float)(i - 1) / sc) - 1);
+    hi = min(out_size - 1, (int)ceilf((float)(i + 1) / sc) + 1);
+}
+
+__global__ void __launch_bounds__(256) upsample_ac_bwd_kernel(const bf16* __restrict__ dout, bf16* __restrict__ dx, int B, int H, int W, int C,
+                                                              int scale) {
+    const int OH = H * scale, OW = W * scale, cq = C >> 3;
+    const float sy = ac_scale(H, OH), sx = ac_scale(W, OW);
+    const int64_t total = (int64_t)B * H * W * cq;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int q = (int)(i % cq);
+        int64_t p = i / cq;
+        const int ix = (int)(p % W);
+        p /= W;
+        const int iy = (int)(p % H), b = (int)(p / H);
+        float acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+        int oy_lo, oy_hi, ox_lo, ox_hi;
+        ac_range(iy, sy, OH, oy_lo, oy_hi);
+        ac_range(ix, sx, OW, ox_lo, ox_hi);
+        const bf16* db = dout + (int64_t)b * OH * OW * C + 8 * q;
+        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+            int y0, y1;
+            float ly;
+            src_index_ac(oy, sy, H, y0, y1, ly);
+            const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
+            if (wy == 0.f) continue;
+            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+                int x0, x1;
+                float lx;
+                src_index_ac(ox, sx, W, x0, x1, lx);
+                const float w = wy * ((x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f));
+                if (w == 0.f) continue;
+                float g[8];
+                unpack8(*reinterpret_cast<const u32x4*>(db + ((int64_t)oy * OW + ox) * C), g);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(w, g[j], acc[j]);
+            }
+        }
+        *reinterpret_cast<u32x4*>(dx + (((int64_t)b * H + iy) * W + ix) * C + 8 * q) = pack8(acc);
+    }
+}
+
 int grid_for(int64_t total) {
     int64_t blocks = (total + 255) / 256;
     const int64_t cap = (int64_t)num_cus() * 16;
@@ -144,5 +229,26 @@ extern "C" int p4c_upsample_bilinear_bwd(const void* dout, void* dx, int B, int 
     const int64_t total = (int64_t)B * H * W * (C / 8);
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const bf16*)dout, (bf16*)dx, B, H, W, C, scale);
     P4C_CHECK_LAUNCH("upsample_bwd");
+    return P4C_OK;
+}
+
+// align_corners = True: out (B, H scale, W scale, C) from x (B, H, W, C); backward in gather form (fixed order, no atomics)
+extern "C" int p4c_upsample_bilinear_ac_fwd(const void* x, void* out, int B, int H, int W, int C, int scale, p4c_stream_t stream) {
+    P4C_CHECK_ARG(x && out, "p4c_upsample_bilinear_ac_fwd: NULL pointer");
+    P4C_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && scale >= 1 && scale <= 16, "p4c_upsample_bilinear_ac_fwd: B=%d H=%d W=%d C=%d "
+                  "scale=%d (C a multiple of 8, scale 1..16)", B, H, W, C, scale);
+    const int64_t total = (int64_t)B * H * scale * W * scale * (C / 8);
+    hipLaunchKernelGGL(upsample_ac_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const bf16*)x, (bf16*)out, B, H, W, C, scale);
+    P4C_CHECK_LAUNCH("upsample_ac_fwd");
+    return P4C_OK;
+}
+
+extern "C" int p4c_upsample_bilinear_ac_bwd(const void* dout, void* dx, int B, int H, int W, int C, int scale, p4c_stream_t stream) {
+    P4C_CHECK_ARG(dout && dx, "p4c_upsample_bilinear_ac_bwd: NULL pointer");
+    P4C_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && scale >= 1 && scale <= 16, "p4c_upsample_bilinear_ac_bwd: bad sizes");
+    const int64_t total = (int64_t)B * H * W * (C / 8);
+    hipLaunchKernelGGL(upsample_ac_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), (const bf16*)dout, (bf16*)dx, B, H, W, C,
+                       scale);
+    P4C_CHECK_LAUNCH("upsample_ac_bwd");
     return P4C_OK;
 }

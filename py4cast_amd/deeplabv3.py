@@ -1,0 +1,579 @@
+"""
+DeepLabV3 on MI355X -- the model behind ``model_name: DeepLabV3`` (the reference's config/CLI/model/deeplabv3.yaml; registry key
+``DeepLabV3`` of its tests/test_models.py).  The reference takes the class from mfai v5.0.1, which wraps segmentation_models_pytorch's
+DeepLabV3; neither is installed here: PARITY UNPINNED.  The network is smp's DeepLabV3 as its public documentation and torchvision's
+ResNet describe it, restated in tests/deeplabv3_reference.py (float64) and checked against that.
+
+Assumptions (the architecture as written here):
+* encoder (state-dict keys ``encoder.*`` = torchvision's ResNet keys without ``fc``): conv1 7x7 / 2 / padding 3 (no bias) -> bn1 -> ReLU
+  -> max-pool 3x3 / 2 / padding 1 -> layer1..4 of BasicBlocks (resnet18 [2, 2, 2, 2], resnet34 [3, 4, 6, 3]; widths 64 / 128 / 256 / 512;
+  ``relu(bn2(conv2(relu(bn1(conv1 x)))) + identity)``, downsample = 1x1 conv (no bias) + BN in the first block of layer2..4);
+  output stride 8 (smp's make_dilated): layer3's convolutions stride 1 / dilation 2, layer4's stride 1 / dilation 4, padding (k // 2) d;
+  only layer2 keeps its stride 2;
+* decoder = Sequential(ASPP, Conv 3x3 dc -> dc (no bias), BN, ReLU), dc = decoder_channels; ASPP(rates 12, 24, 36): convs.0 = 1x1 conv
+  -> BN -> ReLU, convs.1..3 = 3x3 conv (padding = dilation = rate) -> BN -> ReLU, convs.4 = AdaptiveAvgPool2d(1) -> 1x1 conv -> BN -> ReLU
+  broadcast over the map; project = 1x1 conv 5 dc -> dc -> BN -> ReLU -> Dropout(0.5) on the channel concatenation of the five;
+* segmentation_head = (Conv 1x1 dc -> out with bias, UpsamplingBilinear2d(8): align_corners=True); no activation;
+* initialisation: encoder convs kaiming-normal (fan_out, relu), decoder convs kaiming-uniform (fan_in, relu), head xavier-uniform with
+  zero bias, BN weight 1 / bias 0.  ``encoder_weights: True`` never downloads: a torchvision checkpoint is taken from
+  ``encoder_weights_path`` or the torch hub cache, and conv1 is patched for in_channels != 3 as smp does.
+
+What runs where, bf16 (``compute_dtype`` / ``activation_dtype`` "bf16"), features-last (B, H, W, C) throughout:
+* stride-1 3x3 convolutions (dilations 1, 2, 4, 12, 24, 36) and the 1x1 ones: the implicit-GEMM kernels of csrc/gemm.hip
+  (``ops_gemm.conv2d_nhwc(dilation=d)``) with the batch-norm statistics from the GEMM epilogue; BN (+ residual) + ReLU:
+  ``ops_gemm.batch_norm_act``; the residual's gradient is added in conv1's data-gradient epilogue (``passthrough``);
+* the strided convolutions (conv1 7x7 / 2, layer2.0.conv1 3x3 / 2, layer2.0.downsample 1x1 / 2): a patch gather
+  (``p4c_seg_patch_gather``, nn.Unfold's column order) + one GEMM with the statistics epilogue; the data gradient is the GEMM + the
+  gather-form scatter (skipped for the network input);
+* the stem tail (bn1 + ReLU + the 3x3 / 2 max-pool) in one pass each way, the ASPP pooling branch in fp32 and the projection's 5 dc-wide
+  input (csrc/deeplab.hip); the project's Dropout as the multiplier of its batch-norm pass;
+* the head's ×8 bilinear up-sampling with align_corners=True (csrc/resize.hip), on the head output padded to 8 channels.
+fp32 (the parity flavour): the same network on library operations (NCHW inside).
+"""
+
+import glob
+import os
+import warnings
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import _lib as L
+from . import ops_gemm as G
+from .base import ModelABC, ModelType
+from .segformer import _PatchGather
+from .unet import _bn_stats
+
+try:
+    from dataclasses_json import dataclass_json
+except Exception:  # pragma: no cover
+    def dataclass_json(cls):
+        return cls
+
+
+ENCODER_BLOCKS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
+ASPP_RATES = (12, 24, 36)
+
+
+@dataclass_json
+@dataclass
+class DeepLabV3Settings:
+    """mfai's DeepLabV3Settings fields (config/CLI/model/deeplabv3.yaml) + the MI355X knobs."""
+
+    encoder_name: str = "resnet18"
+    encoder_depth: int = 5
+    encoder_weights: bool = True
+    decoder_channels: int = 256
+    activation: Optional[str] = None
+    upsampling: int = 8
+    aux_params: Optional[dict] = None
+    # MI355X-specific
+    compute_dtype: str = "f32"      # "f32" (library operations, the parity flavour) or "bf16" (the native route)
+    activation_dtype: Optional[str] = None   # HBM storage of activations: "f32" | "bf16"; None = compute_dtype
+    aspp_dropout: float = 0.5       # mfai's hard-coded p of the ASPP projection's Dropout (0: the parity tests' deterministic network)
+    encoder_weights_path: Optional[str] = None   # a torchvision resnet checkpoint (.pth); None: look in torch.hub's checkpoint cache
+
+
+# ---------------------------------------------------------------- module tree (keys as smp / torchvision)
+class BasicBlock(nn.Module):
+    def __init__(self, cin: int, cout: int, stride: int, dilation: int):
+        super().__init__()
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride=stride, padding=dilation, dilation=dilation, bias=False)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(cout, cout, 3, padding=dilation, dilation=dilation, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride, bias=False), nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        idn = x if self.downsample is None else self.downsample(x)
+        y = self.relu(self.bn1(self.conv1(x)))
+        return self.relu(self.bn2(self.conv2(y)) + idn)
+
+
+class ResNetEncoder(nn.Module):
+    """torchvision's ResNet (BasicBlock) without avgpool / fc, output stride 8 (layer3 dilation 2, layer4 dilation 4)"""
+
+    def __init__(self, in_channels: int, blocks):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels, 64, 7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
+        cin = 64
+        for i, (n, width, stride, dil) in enumerate(zip(blocks, (64, 128, 256, 512), (1, 2, 1, 1), (1, 1, 2, 4))):
+            layer = []
+            for j in range(n):
+                layer.append(BasicBlock(cin, width, stride if j == 0 else 1, dil))
+                cin = width
+            setattr(self, f"layer{i + 1}", nn.Sequential(*layer))
+
+    def forward(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        return self.layer4(self.layer3(self.layer2(self.layer1(x))))
+
+
+class ASPPConv(nn.Sequential):
+    def __init__(self, cin: int, cout: int, rate: int):
+        super().__init__(nn.Conv2d(cin, cout, 3, padding=rate, dilation=rate, bias=False), nn.BatchNorm2d(cout), nn.ReLU())
+
+
+class ASPPPooling(nn.Sequential):
+    def __init__(self, cin: int, cout: int):
+        super().__init__(nn.AdaptiveAvgPool2d(1), nn.Conv2d(cin, cout, 1, bias=False), nn.BatchNorm2d(cout), nn.ReLU())
+
+    def forward(self, x):
+        size = x.shape[-2:]
+        for mod in self:
+            x = mod(x)
+        return x.expand(-1, -1, *size)      # bilinear from 1x1 = broadcast
+
+
+class ASPP(nn.Module):
+    def __init__(self, cin: int, cout: int, rates, dropout: float):
+        super().__init__()
+        self.convs = nn.ModuleList([nn.Sequential(nn.Conv2d(cin, cout, 1, bias=False), nn.BatchNorm2d(cout), nn.ReLU())]
+                                   + [ASPPConv(cin, cout, r) for r in rates] + [ASPPPooling(cin, cout)])
+        self.project = nn.Sequential(nn.Conv2d(5 * cout, cout, 1, bias=False), nn.BatchNorm2d(cout), nn.ReLU(), nn.Dropout(dropout))
+
+    def forward(self, x):
+        return self.project(torch.cat([c(x) for c in self.convs], dim=1))
+
+
+# ---------------------------------------------------------------- native nodes
+class _PatchConv(torch.autograd.Function):
+    """y (B, Ho, Wo, Co) = Conv2d(C, Co, k, stride, pad, bias=False) of a features-last bf16 map as a patch gather (nn.Unfold's column
+    order) + one GEMM whose epilogue leaves the batch-norm column sums; w2d = the weight's (Co, C k^2) view"""
+
+    @staticmethod
+    def forward(ctx, x, w2d, k, stride, pad):
+        cols = _PatchGather.forward(ctx, x, k, stride, pad)
+        B, Ho, Wo, K = cols.shape
+        Co = w2d.shape[0]
+        c2 = cols.view(-1, K)
+        fwd, dgr = G.weight_images(w2d, 1)
+        y, _, stats = G.gemm_nt(c2, fwd, Co, K, want_stats=True)
+        ctx.save_for_backward(c2, dgr)
+        ctx.pgeom, ctx.wdtype = (B, Ho, Wo, K, Co), w2d.dtype
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        return y.view(B, Ho, Wo, Co), stats
+
+    @staticmethod
+    def backward(ctx, dy, _dstats):
+        c2, dgr = ctx.saved_tensors
+        B, Ho, Wo, K, Co = ctx.pgeom
+        dy2 = G._rows(dy, Co)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dcols = G.gemm_nt(dy2, dgr, K, Co)[0].view(B, Ho, Wo, K)
+            dx = _PatchGather.backward(ctx, dcols)[0]
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw, _ = G.gemm_tn(dy2, c2, Co, K)
+            dw = dw.to(ctx.wdtype)
+        return dx, dw, None, None, None
+
+
+class _StemTail(torch.autograd.Function):
+    """pool = max_pool2d(relu(bn(y)), 3, 2, 1) of the stem convolution's raw output; one native pass each way (csrc/deeplab.hip) + the
+    batch norm's finalize / apply"""
+
+    @staticmethod
+    def forward(ctx, y, stats, gamma, beta, bn, training):
+        yc = y.contiguous()
+        B, H, W, C = yc.shape
+        dev = yc.device
+        st = _bn_stats(yc, stats, bn, training)
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        pool = torch.empty(B, Ho, Wo, C, dtype=yc.dtype, device=dev)
+        arg = torch.empty(B, Ho, Wo, C, dtype=torch.uint8, device=dev)
+        L.call("p4c_deeplab_stem_fwd", L.ptr(yc), L.ptr(st[2]), L.ptr(st[3]), L.ptr(pool), L.ptr(arg), B, H, W, C, L.stream(dev),
+               alg_bytes=2 * yc.numel() + 3 * pool.numel())
+        ctx.save_for_backward(yc, st, arg)
+        ctx.training = bool(training)
+        ctx.has_affine = gamma is not None
+        return pool
+
+    @staticmethod
+    def backward(ctx, dpool):
+        yc, st, arg = ctx.saved_tensors
+        B, H, W, C = yc.shape
+        dev = yc.device
+        N = B * H * W
+        dpool = dpool.contiguous()
+        nb = L.lib().p4c_deeplab_stem_bwd_blocks(B, H, W, C)
+        part = torch.empty(1, nb, 2, C, dtype=torch.float32, device=dev)
+        dz = torch.empty_like(yc)
+        L.call("p4c_deeplab_stem_bwd", L.ptr(yc), L.ptr(dpool), L.ptr(arg), L.ptr(st[2]), L.ptr(st[3]), L.ptr(st[0]), L.ptr(st[1]), L.ptr(dz),
+               L.ptr(part), B, H, W, C, L.stream(dev), alg_bytes=4 * yc.numel() + 3 * dpool.numel())
+        co = torch.empty(2, C, dtype=torch.float32, device=dev)
+        dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
+        L.call("p4c_inorm_finalize_bwd", L.ptr(part), nb, 1, N, C, 0, None, None, L.ptr(co[0]), L.ptr(co[1]), L.ptr(dgb[0]), L.ptr(dgb[1]),
+               L.stream(dev))
+        if not ctx.training:
+            co.zero_()          # running statistics are constants
+        dy = torch.empty_like(yc)
+        L.call("p4c_inorm_apply", L.ptr(yc), None, L.ptr(dz), L.ptr(dz), L.ptr(st[2]), None, L.ptr(st[0]), L.ptr(st[1]), L.ptr(co[0]),
+               L.ptr(co[1]), 1.0, L.ptr(dy), None, L.dtype_code(yc.dtype), 1, N, C, L.stream(dev), alg_bytes=2 * yc.numel() * 3)
+        dg = dgb[0] if ctx.has_affine else None
+        db = dgb[1] if ctx.has_affine else None
+        return dy, None, dg, db, None, None
+
+
+def stem_tail(y: torch.Tensor, stats, bn: nn.BatchNorm2d) -> torch.Tensor:
+    """``max_pool2d(relu(bn(y)), 3, stride=2, padding=1)`` of a features-last bf16 map y (B, H, W, C), C a multiple of 4 up to 1024;
+    ``stats``: the producer's column sums or None"""
+    L.require_cuda(y)
+    if y.dtype != torch.bfloat16 or y.dim() != 4 or y.shape[-1] % 4 or y.shape[-1] > 1024:
+        raise L.P4CError(f"deeplabv3.stem_tail: unsupported map {tuple(y.shape)} {y.dtype}")
+    training = bn.training or bn.running_mean is None
+    return _StemTail.apply(y, stats if training else None, bn.weight, bn.bias, bn, training)
+
+
+def _colsum_chunks(HW: int) -> int:
+    return max(1, min(HW, HW // 256))
+
+
+class _AsppAssemble(torch.autograd.Function):
+    """buf (B, H, W, 5 D) = [a0 | a1 | a2 | a3 | relu(bn(conv1x1(mean_hw x)))] -- the four spatial branches and the pooling branch
+    (fp32, broadcast over the map); the projection's input without a concatenation of five full maps"""
+
+    @staticmethod
+    def forward(ctx, x, a0, a1, a2, a3, w, gamma, beta, bn, training):
+        xc = x.contiguous()
+        B, H, W, C = xc.shape
+        D = w.shape[0]
+        HW = H * W
+        dev = xc.device
+        S = _colsum_chunks(HW)
+        part = torch.empty(B, S, C, dtype=torch.float32, device=dev)
+        L.call("p4c_deeplab_colsum", L.ptr(xc), C, L.ptr(part), B, HW, C, S, L.stream(dev), alg_bytes=2 * xc.numel())
+        w32 = G._f32(w).reshape(D, C)
+        mean = torch.empty(B, C, dtype=torch.float32, device=dev)
+        z = torch.empty(B, D, dtype=torch.float32, device=dev)
+        stat = torch.empty(2, D, dtype=torch.float32, device=dev)
+        pooled = torch.empty(B, D, dtype=torch.float32, device=dev)
+        track = bn.track_running_stats and bn.running_mean is not None
+        nbt = bn.num_batches_tracked if (track and training) else None
+        mom = 0.1 if bn.momentum is None else bn.momentum
+        L.call("p4c_deeplab_pool_head_fwd", L.ptr(part), S, HW, L.ptr(w32), L.ptr(G._f32(gamma)), L.ptr(G._f32(beta)), float(bn.eps), float(mom),
+               L.ptr(bn.running_mean if track else None), L.ptr(bn.running_var if track else None), L.ptr(nbt), int(training), B, C, D,
+               L.ptr(mean), L.ptr(z), L.ptr(stat), L.ptr(pooled), L.stream(dev))
+        a = [t.contiguous() for t in (a0, a1, a2, a3)]
+        buf = torch.empty(B, H, W, 5 * D, dtype=xc.dtype, device=dev)
+        L.call("p4c_deeplab_assemble_fwd", *[L.ptr(t) for t in a], L.ptr(pooled), L.ptr(buf), B, HW, D, L.stream(dev), alg_bytes=2 * 9 * B * HW * D)
+        ctx.save_for_backward(w32, mean, z, stat, pooled, G._f32(gamma) if gamma is not None else None)
+        ctx.geom = (B, H, W, C, D, S)
+        ctx.training = bool(training)
+        ctx.dtypes = (xc.dtype, w.dtype, w.shape)
+        return buf
+
+    @staticmethod
+    def backward(ctx, dbuf):
+        w32, mean, z, stat, pooled, g32 = ctx.saved_tensors
+        B, H, W, C, D, S = ctx.geom
+        HW = H * W
+        dev = dbuf.device
+        dbuf = dbuf.contiguous()
+        d = [torch.empty(B, H, W, D, dtype=dbuf.dtype, device=dev) for _ in range(4)]
+        L.call("p4c_deeplab_assemble_bwd", L.ptr(dbuf), *[L.ptr(t) for t in d], B, HW, D, L.stream(dev), alg_bytes=2 * 8 * B * HW * D)
+        gpart = torch.empty(B, S, D, dtype=torch.float32, device=dev)
+        L.call("p4c_deeplab_colsum", L.ptr(dbuf[..., 4 * D:]), 5 * D, L.ptr(gpart), B, HW, D, S, L.stream(dev), alg_bytes=2 * B * HW * D)
+        dz = torch.empty(B, D, dtype=torch.float32, device=dev)
+        dgb = torch.empty(2, D, dtype=torch.float32, device=dev)
+        dw = torch.empty(D, C, dtype=torch.float32, device=dev)
+        dmean = torch.empty(B, C, dtype=torch.float32, device=dev)
+        L.call("p4c_deeplab_pool_head_bwd", L.ptr(gpart), S, L.ptr(z), L.ptr(stat), L.ptr(pooled), L.ptr(g32), L.ptr(mean), L.ptr(w32),
+               int(ctx.training), B, C, D, L.ptr(dz), L.ptr(dgb[0]), L.ptr(dgb[1]), L.ptr(dw), L.ptr(dmean), L.stream(dev))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(B, H, W, C, dtype=ctx.dtypes[0], device=dev)
+            L.call("p4c_deeplab_pool_broadcast", L.ptr(dmean), L.ptr(dx), B, HW, C, L.stream(dev), alg_bytes=2 * B * HW * C)
+        dwt = dw.view(ctx.dtypes[2]).to(ctx.dtypes[1])
+        dg, db = (dgb[0], dgb[1]) if g32 is not None else (None, None)
+        return dx, d[0], d[1], d[2], d[3], dwt, dg, db, None, None
+
+
+def aspp_assemble(x: torch.Tensor, branches, pool_branch: ASPPPooling) -> torch.Tensor:
+    """(B, H, W, 5 D) bf16 = channel concatenation of the four spatial ASPP branches (each (B, H, W, D) bf16) and the pooling branch of x
+    (B, H, W, C) bf16 broadcast over the map; the pooling branch runs in fp32 (mean, 1x1 conv, BatchNorm over the batch, ReLU)"""
+    L.require_cuda(x)
+    conv, bn = pool_branch[1], pool_branch[2]
+    B, H, W, C = x.shape
+    D = conv.weight.shape[0]
+    if (x.dtype != torch.bfloat16 or C % 4 or D % 4 or len(branches) != 4 or B > 16 or B * C * 4 > 65536
+            or any(t.shape != (B, H, W, D) or t.dtype != torch.bfloat16 for t in branches)):
+        raise L.P4CError(f"deeplabv3.aspp_assemble: unsupported operands (x {tuple(x.shape)} {x.dtype}, D {D}, B {B} of at most 16)")
+    training = bn.training or bn.running_mean is None
+    if training and B < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
+    if training and bn.momentum is None and bn.track_running_stats:
+        raise L.P4CError("deeplabv3.aspp_assemble: BatchNorm2d(momentum=None) (cumulative average) is not served; give a momentum")
+    return _AsppAssemble.apply(x, *branches, conv.weight, bn.weight, bn.bias, bn, training)
+
+
+class _UpsampleAC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale):
+        xc = x.contiguous()
+        B, H, W, C = xc.shape
+        out = torch.empty(B, H * scale, W * scale, C, dtype=xc.dtype, device=xc.device)
+        L.call("p4c_upsample_bilinear_ac_fwd", L.ptr(xc), L.ptr(out), B, H, W, C, scale, L.stream(xc.device), alg_bytes=2 * (xc.numel() + out.numel()))
+        ctx.geom = (B, H, W, C, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, H, W, C, scale = ctx.geom
+        dout = dout.contiguous()
+        dx = torch.empty(B, H, W, C, dtype=dout.dtype, device=dout.device)
+        L.call("p4c_upsample_bilinear_ac_bwd", L.ptr(dout), L.ptr(dx), B, H, W, C, scale, L.stream(dout.device),
+               alg_bytes=2 * (dx.numel() + dout.numel()))
+        return dx, None
+
+
+def upsample_bilinear_ac(x: torch.Tensor, scale: int) -> torch.Tensor:
+    """``F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=True)`` of a features-last bf16 map, C a multiple of 8"""
+    L.require_cuda(x)
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or x.shape[-1] % 8 or not 1 <= scale <= 16:
+        raise L.P4CError(f"deeplabv3.upsample_bilinear_ac: unsupported operands (x {tuple(x.shape)} {x.dtype}, scale {scale})")
+    return _UpsampleAC.apply(x, int(scale))
+
+
+# ---------------------------------------------------------------- encoder weights
+_WARNED = set()
+
+
+def _find_checkpoint(name: str, path: Optional[str]) -> Optional[str]:
+    if path:
+        return path
+    hub = os.path.join(torch.hub.get_dir(), "checkpoints")
+    found = sorted(glob.glob(os.path.join(hub, f"{name}-*.pth")))
+    return found[0] if found else None
+
+
+def load_encoder_weights(encoder: ResNetEncoder, name: str, in_channels: int, path: Optional[str] = None) -> bool:
+    """torchvision ``name`` weights into ``encoder`` from ``path`` or the first ``<name>-*.pth`` of torch.hub's checkpoint cache, without
+    any download; ``fc.*`` ignored; conv1 patched for in_channels != 3 as smp does (1 channel: the sum over the RGB kernels; otherwise
+    kernel i = RGB kernel i % 3, all scaled by 3 / in_channels).  No file: a warning (once per name) and False."""
+    ck = _find_checkpoint(name, path)
+    if ck is None or not os.path.isfile(ck):
+        key = (name, path)
+        if key not in _WARNED:
+            _WARNED.add(key)
+            where = path if path else os.path.join(torch.hub.get_dir(), "checkpoints")
+            warnings.warn(f"DeepLabV3MI355X: no {name} checkpoint found ({where}); the encoder keeps its random initialisation "
+                          "(nothing is downloaded)")
+        return False
+    sd = torch.load(ck, map_location="cpu", weights_only=True)
+    sd = {k: v for k, v in sd.items() if not k.startswith("fc.")}
+    w = sd["conv1.weight"]
+    if in_channels != w.shape[1]:
+        if in_channels == 1:
+            nw = w.sum(1, keepdim=True)
+        else:
+            nw = torch.empty(w.shape[0], in_channels, *w.shape[2:], dtype=w.dtype)
+            for i in range(in_channels):
+                nw[:, i] = w[:, i % w.shape[1]]
+            nw = nw * (w.shape[1] / in_channels)
+        sd["conv1.weight"] = nw
+    encoder.load_state_dict(sd)
+    return True
+
+
+# ---------------------------------------------------------------- the model
+class DeepLabV3MI355X(ModelABC, nn.Module):
+    """smp's DeepLabV3 as mfai builds it (module docstring) on the native kernels of this package."""
+
+    settings_kls = DeepLabV3Settings
+    onnx_supported = False
+    supported_num_spatial_dims = (2,)
+    num_spatial_dims = 2
+    features_last = True
+    model_type = ModelType.CONVOLUTIONAL
+    register = True
+    is_native_hip = True
+    rollout_padded_output = False
+
+    def __init__(self, in_channels: int, out_channels: int, input_shape: tuple = None, settings: DeepLabV3Settings = DeepLabV3Settings(),
+                 *args, **kwargs):
+        super().__init__()
+        self.in_channels, self.out_channels, self.input_shape = in_channels, out_channels, input_shape
+        self.num_output_features = out_channels
+        self._settings = s = settings
+        if s.encoder_name not in ENCODER_BLOCKS:
+            raise ValueError(f"DeepLabV3MI355X: encoder_name {s.encoder_name!r} is not served (one of {sorted(ENCODER_BLOCKS)})")
+        if s.encoder_depth != 5:
+            raise ValueError(f"DeepLabV3MI355X: encoder_depth {s.encoder_depth} is not served (5)")
+        if s.decoder_channels <= 0 or s.decoder_channels % 8:
+            raise ValueError(f"DeepLabV3MI355X: decoder_channels must be a positive multiple of 8, got {s.decoder_channels}")
+        if s.activation is not None:
+            raise ValueError(f"DeepLabV3MI355X: activation {s.activation!r} is not served (None: identity)")
+        if s.upsampling != 8:
+            raise ValueError(f"DeepLabV3MI355X: upsampling {s.upsampling} is not served (8: the output has the input's grid)")
+        if s.aux_params is not None:
+            raise ValueError("DeepLabV3MI355X: aux_params (the classification head) is not served")
+        if not 0.0 <= s.aspp_dropout < 1.0:
+            raise ValueError(f"DeepLabV3MI355X: aspp_dropout must be in [0, 1), got {s.aspp_dropout}")
+        act = s.activation_dtype or s.compute_dtype
+        if s.compute_dtype not in ("f32", "bf16") or act not in ("f32", "bf16"):
+            raise ValueError(f"DeepLabV3MI355X: compute_dtype / activation_dtype must be 'f32' or 'bf16', got {s.compute_dtype} / {act}")
+        if act != s.compute_dtype:
+            raise ValueError(f"DeepLabV3MI355X: compute_dtype {s.compute_dtype} with activation_dtype {act} is not served: the bf16 route "
+                             "keeps bf16 activations, the fp32 route fp32 ones")
+        self.act_dtype = torch.bfloat16 if act == "bf16" else torch.float32
+        dc = s.decoder_channels
+        self.encoder = ResNetEncoder(in_channels, ENCODER_BLOCKS[s.encoder_name])
+        self.decoder = nn.Sequential(ASPP(512, dc, ASPP_RATES, s.aspp_dropout), nn.Conv2d(dc, dc, 3, padding=1, bias=False),
+                                     nn.BatchNorm2d(dc), nn.ReLU())
+        self.segmentation_head = nn.Sequential(nn.Conv2d(dc, out_channels, 1), nn.UpsamplingBilinear2d(scale_factor=8))
+        self._init_weights()
+        if s.encoder_weights:
+            load_encoder_weights(self.encoder, s.encoder_name, in_channels, s.encoder_weights_path)
+        self.last_dropout_mask = None      # the bf16 route's last Dropout draw (N, dc) fp32 in {0, 1} (tests)
+        self.prefers_hip_graph = False     # eager 23.7 ms vs replay 23.9 ms per bench step: the launches hide behind the GEMMs
+        self.timed_entry_points = ("p4c_gemm_nt", "p4c_gemm_tn", "p4c_seg_patch_gather", "p4c_seg_patch_scatter", "p4c_deeplab_stem_fwd",
+                                   "p4c_deeplab_stem_bwd", "p4c_deeplab_colsum", "p4c_deeplab_assemble_fwd", "p4c_deeplab_assemble_bwd",
+                                   "p4c_deeplab_pool_broadcast", "p4c_upsample_bilinear_ac_fwd", "p4c_upsample_bilinear_ac_bwd",
+                                   "p4c_inorm_apply", "p4c_inorm_apply_mul")
+        self.check_required_attributes()
+
+    roofline_from_entry_points = True    # bench.py: time every call of the native entry points above
+
+    def _init_weights(self):
+        for m in self.encoder.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        for m in self.decoder.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_uniform_(m.weight, mode="fan_in", nonlinearity="relu")
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        head = self.segmentation_head[0]
+        nn.init.xavier_uniform_(head.weight)
+        nn.init.constant_(head.bias, 0)
+
+    @property
+    def settings(self):
+        return self._settings
+
+    def roofline(self, ktimes, B, H, W):
+        """bench.py: achieved HBM rate of the native entry point that takes the most time (the UNETR++ accounting)"""
+        from .unetrpp import UNetRPPMI355X
+
+        return UNetRPPMI355X.roofline(self, ktimes, B, H, W)
+
+    @property
+    def native(self) -> bool:
+        """the bf16 route (csrc/gemm.hip, csrc/deeplab.hip, csrc/resize.hip); fp32 runs on the library"""
+        return self.act_dtype == torch.bfloat16
+
+    @property
+    def cin_pad(self) -> int:
+        return (self.in_channels + 7) // 8 * 8
+
+    @property
+    def rollout_input_format(self):
+        """(dtype, channel count) of the rows the rollout's build_x should emit: bf16, zero-padded to the GEMM's 8-channel granularity"""
+        if not self.native:
+            return None
+        return torch.bfloat16, self.cin_pad
+
+    def check_grid(self, H: int, W: int) -> None:
+        if H % 8 or W % 8:
+            nh, nw = (H + 7) // 8 * 8, (W + 7) // 8 * 8
+            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width divisible by 8. Consider pad "
+                               f"your images to shape ({nh}, {nw}).")
+
+    # ---------------------------------------------------------------- the bf16 route
+    @staticmethod
+    def _patch(conv: nn.Conv2d, x: torch.Tensor):
+        """strided convolution: patch gather + GEMM; (y, stats)"""
+        w = conv.weight
+        if w.shape[1] != x.shape[-1]:        # conv1 on zero-padded input rows: zero weight columns for the padding channels
+            w = F.pad(w, (0, 0, 0, 0, 0, x.shape[-1] - w.shape[1]))
+        k = conv.kernel_size[0]
+        return _PatchConv.apply(x, w.reshape(w.shape[0], -1), k, conv.stride[0], conv.padding[0])
+
+    def _block(self, blk: BasicBlock, x: torch.Tensor) -> torch.Tensor:
+        d = blk.conv1.dilation[0]
+        if blk.downsample is not None:
+            if blk.conv1.stride[0] != 1:
+                y1, st1 = self._patch(blk.conv1, x)
+                yd, std = self._patch(blk.downsample[0], x)
+            else:
+                y1, st1 = G.conv2d_nhwc(x, blk.conv1.weight, want_stats=True, dilation=d)
+                yd, std = G.conv2d_nhwc(x, blk.downsample[0].weight, want_stats=True)
+            idn = G.batch_norm_act(yd, std, blk.downsample[1], slope=1.0)
+        else:
+            y1, st1, idn = G.conv2d_nhwc(x, blk.conv1.weight, want_stats=True, passthrough=True, dilation=d)
+        h = G.batch_norm_act(y1, st1, blk.bn1, slope=0.0)
+        y2, st2 = G.conv2d_nhwc(h, blk.conv2.weight, want_stats=True, dilation=blk.conv2.dilation[0])
+        return G.batch_norm_act(y2, st2, blk.bn2, slope=0.0, res=idn)
+
+    def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
+        enc = self.encoder
+        y, st = self._patch(enc.conv1, x)
+        h = stem_tail(y, st, enc.bn1)
+        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
+            for blk in layer:
+                h = self._block(blk, h)
+        aspp, dconv, dbn = self.decoder[0], self.decoder[1], self.decoder[2]
+        branches = []
+        for i, br in enumerate(aspp.convs[:4]):
+            conv, bn = br[0], br[1]
+            yb, sb = G.conv2d_nhwc(h, conv.weight, want_stats=True, dilation=conv.dilation[0])
+            branches.append(G.batch_norm_act(yb, sb, bn, slope=0.0))
+        cat = aspp_assemble(h, branches, aspp.convs[4])
+        pconv, pbn, drop = aspp.project[0], aspp.project[1], aspp.project[3]
+        yp, sp = G.conv2d_nhwc(cat, pconv.weight, want_stats=True)
+        if self.training and drop.p > 0:
+            keep = 1.0 - drop.p
+            mask = torch.empty(yp.numel() // yp.shape[-1], yp.shape[-1], dtype=torch.float32, device=yp.device).bernoulli_(keep)
+            self.last_dropout_mask = mask
+            a = G.batch_norm_act(yp, sp, pbn, slope=0.0, mul=mask, mul_factor=1.0 / keep)
+        else:
+            self.last_dropout_mask = None
+            a = G.batch_norm_act(yp, sp, pbn, slope=0.0)
+        yd, sd = G.conv2d_nhwc(a, dconv.weight, want_stats=True)
+        a = G.batch_norm_act(yd, sd, dbn, slope=0.0)
+        head = self.segmentation_head[0]
+        w, b = head.weight, head.bias
+        pad = (-w.shape[0]) % 8
+        if pad:                      # zero output rows up to the 8-channel granularity, sliced off after the up-sampling
+            w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, pad))
+            b = F.pad(b, (0, pad))
+        z = G.conv2d_nhwc(a, w, b)
+        up = upsample_bilinear_ac(z, 8)
+        return up[..., : self.out_channels] if pad else up
+
+    # ---------------------------------------------------------------- nn.Module API
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (B, H, W, in_channels) (or the rollout's zero-padded rows) -> (B, H, W, out_channels); H and W multiples of 8."""
+        L.require_cuda(x)
+        self.check_grid(x.shape[1], x.shape[2])
+        if x.shape[-1] < self.in_channels:
+            raise L.P4CError(f"DeepLabV3MI355X: expected {self.in_channels} input channels, got {x.shape[-1]}")
+        out_dtype = x.dtype
+        x = x.to(self.act_dtype)
+        if self.native:
+            if self.training and x.shape[0] < 2:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                                 f"{torch.Size([x.shape[0], self._settings.decoder_channels, 1, 1])}")
+            if x.shape[-1] % 8:
+                x = F.pad(x, (0, self.cin_pad - x.shape[-1]))
+            y = self._forward_native(x.contiguous())
+        else:
+            xin = x[..., : self.in_channels].permute(0, 3, 1, 2)
+            y = self.segmentation_head(self.decoder(self.encoder(xin))).permute(0, 2, 3, 1)
+        return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)

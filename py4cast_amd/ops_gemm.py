@@ -199,9 +199,10 @@ def _f32(p: Optional[torch.Tensor]):
 
 
 def gemm_nt(A: torch.Tensor, img: torch.Tensor, N: int, K: int, conv=None, bias=None, res=None, act=ACT_NONE, aux_in=None,
-            want_stats=False, out=None):
+            want_stats=False, out=None, dilation=1):
     """C = epilogue(A x img^T).  A: (M, >= K) bf16 rows, or with conv = (H, W, Cin) the NHWC map as (M = batch H W, Cin-or-wider)
-    rows.  Returns (C, aux_out or None, stats or None); `out`: a preallocated (M, >= N) row view to write into."""
+    rows (3x3 taps ``dilation`` pixels apart).  Returns (C, aux_out or None, stats or None); `out`: a preallocated (M, >= N) row view
+    to write into."""
     lib = L.lib()
     M = A.shape[0]
     H, W, Cin, taps = (conv[0], conv[1], conv[2], 9) if conv is not None else (0, 0, 0, 1)
@@ -213,14 +214,15 @@ def gemm_nt(A: torch.Tensor, img: torch.Tensor, N: int, K: int, conv=None, bias=
         stats = torch.empty(lib.p4c_gemm_nt_stat_blocks(M, N, K), 2, N, dtype=torch.float32, device=A.device)
     nbytes = lib.p4c_gemm_nt_workspace_bytes(M, N, K)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=A.device) if nbytes else None
-    L.call("p4c_gemm_nt", L.ptr(A), A.stride(0), L.ptr(img), M, N, K, H, W, Cin, taps, L.ptr(bias), L.ptr(res),
+    L.call("p4c_gemm_nt", L.ptr(A), A.stride(0), L.ptr(img), M, N, K, H, W, Cin, taps, int(dilation), L.ptr(bias), L.ptr(res),
            0 if res is None else res.stride(0), act, L.ptr(aux_in), L.ptr(aux_out), 0 if aux is None else aux.stride(0), L.ptr(C), C.stride(0),
            L.ptr(stats), L.ptr(ws), L.stream(A.device), alg_bytes=2 * (M * (K if conv is None else Cin) + N * K + M * N), alg_flops=2 * M * N * K)
     return C, aux_out, stats
 
 
-def gemm_tn(dy: torch.Tensor, x: torch.Tensor, Mo: int, Cin: int, conv=None, want_bias=False, sink=None):
-    """dW (Mo, Cin[, 3, 3]) fp32 and db (Mo) or None from dy (R, >= Mo) and x (R, >= Cin) bf16 rows (conv = (H, W): x is the NHWC map).
+def gemm_tn(dy: torch.Tensor, x: torch.Tensor, Mo: int, Cin: int, conv=None, want_bias=False, sink=None, dilation=1):
+    """dW (Mo, Cin[, 3, 3]) fp32 and db (Mo) or None from dy (R, >= Mo) and x (R, >= Cin) bf16 rows (conv = (H, W): x is the NHWC map,
+    3x3 taps ``dilation`` pixels apart).
     sink = (gw, gb): ADD both into these fp32 buffers (views of the parameters' .grad) instead, and return (None, None)."""
     lib = L.lib()
     R = dy.shape[0]
@@ -236,7 +238,7 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, Mo: int, Cin: int, conv=None, wan
     # step before.  A gradient exchange that listens for the sums as they become final (FlatDDP(overlap=True), eager steps of N > 1
     # ranks) does not start the queue: there a call reduces at once and reports it, unless the pass already queues.
     defer = L.GradQueue.join(ws, start=not L.GRAD_SINK_LISTENERS) if sink is not None else False
-    L.call("p4c_gemm_tn", L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), R, Mo, H, W, Cin, taps, L.ptr(dw), L.ptr(db), int(sink is not None),
+    L.call("p4c_gemm_tn", L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), R, Mo, H, W, Cin, taps, int(dilation), L.ptr(dw), L.ptr(db), int(sink is not None),
            int(defer), L.ptr(ws), L.stream(dy.device), alg_bytes=2 * R * (Mo + Cin) + 4 * Mo * Cin * taps, alg_flops=2 * R * Mo * Cin * taps)
     if sink is not None:
         L.GradQueue.wrote([dw, db], defer)    # (FlatDDP(overlap=True) counts these: now, or at the flush when the sums were queued)
@@ -427,11 +429,11 @@ def mlp(x, w1, b1, w2, b2, res=None) -> torch.Tensor:
 
 
 class _Conv(torch.autograd.Function):
-    """y (B,H,W,Co) = conv(x (B,H,W,>=Ci), w (Co,Ci,k,k)) (+ bias) (+ res), k = 3 ("same", zero padding) or 1; second output: the column
-    sums of y for a batch norm (not differentiable: the norm's backward accounts for them analytically)."""
+    """y (B,H,W,Co) = conv(x (B,H,W,>=Ci), w (Co,Ci,k,k)) (+ bias) (+ res), k = 3 ("same": zero padding = dilation) or 1; second
+    output: the column sums of y for a batch norm (not differentiable: the norm's backward accounts for them analytically)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, res, want_stats, passthrough=False):
+    def forward(ctx, x, w, b, res, want_stats, passthrough=False, dilation=1):
         Co, Ci, k = w.shape[0], w.shape[1], w.shape[2]
         B, H, W_, Cx = x.shape
         taps = k * k
@@ -439,11 +441,12 @@ class _Conv(torch.autograd.Function):
         fwd, dgr = weight_images(w, taps)
         r2 = None if res is None else _rows(res.detach(), Co)
         if taps == 9:
-            y, _, stats = gemm_nt(xm, fwd, Co, 9 * Ci, conv=(H, W_, Ci), bias=_f32(b), res=r2, want_stats=want_stats)
+            y, _, stats = gemm_nt(xm, fwd, Co, 9 * Ci, conv=(H, W_, Ci), bias=_f32(b), res=r2, want_stats=want_stats, dilation=dilation)
         else:
             y, _, stats = gemm_nt(xm, fwd, Co, Ci, bias=_f32(b), res=r2, want_stats=want_stats)
         ctx.save_for_backward(xm, dgr)
         ctx.geom, ctx.has_bias, ctx.has_res = (B, H, W_, Cx, Co, Ci, taps), b is not None, res is not None
+        ctx.dilation = dilation
         ctx.wdtype, ctx.bdtype, ctx.wshape = w.dtype, (None if b is None else b.dtype), w.shape
         ctx.sink = _sink(w, b)
         ctx.set_materialize_grads(False)     # (no zero-filled "gradient" of the statistics output: a fill launch per convolution)
@@ -457,7 +460,7 @@ class _Conv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dstats, dpass):
         if dy is None:
-            return dpass, None, None, None, None, None
+            return dpass, None, None, None, None, None, None
         xm, dgr = ctx.saved_tensors
         B, H, W_, Cx, Co, Ci, taps = ctx.geom
         dy2 = _rows(dy, Co)
@@ -466,7 +469,7 @@ class _Conv(torch.autograd.Function):
             fold = dpass is not None and Cx == Ci and dpass.dtype == dy.dtype
             r2 = _rows(dpass, Cx) if fold else None
             if taps == 9:
-                dx = gemm_nt(dy2, dgr, Ci, 9 * Co, conv=(H, W_, Co), res=r2)[0]
+                dx = gemm_nt(dy2, dgr, Ci, 9 * Co, conv=(H, W_, Co), res=r2, dilation=ctx.dilation)[0]
             else:
                 dx = gemm_nt(dy2, dgr, Ci, Co, res=r2)[0]
             if Cx > Ci:      # the map was wider than the weight's input channels (zero-padded rows): no gradient there
@@ -476,26 +479,30 @@ class _Conv(torch.autograd.Function):
                 dx = dx + dpass
         dw = db = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dw, db = gemm_tn(dy2, xm, Co, Ci, conv=(H, W_) if taps == 9 else None, want_bias=ctx.has_bias, sink=ctx.sink)
+            dw, db = gemm_tn(dy2, xm, Co, Ci, conv=(H, W_) if taps == 9 else None, want_bias=ctx.has_bias, sink=ctx.sink,
+                             dilation=ctx.dilation)
             dw = None if dw is None else dw.view(ctx.wshape).to(ctx.wdtype)
             db = None if db is None else db.to(ctx.bdtype)
-        return dx, dw, db, (dy if ctx.has_res else None), None, None
+        return dx, dw, db, (dy if ctx.has_res else None), None, None, None
 
 
-def conv_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
+def conv_supported(x: torch.Tensor, w: torch.Tensor, dilation: int = 1) -> bool:
     return (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and w.dtype == torch.float32 and w.dim() == 4
             and w.shape[2] == w.shape[3] and w.shape[2] in (1, 3) and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0
-            and x.shape[-1] >= w.shape[1] and x.shape[-1] % 8 == 0)
+            and x.shape[-1] >= w.shape[1] and x.shape[-1] % 8 == 0
+            and isinstance(dilation, int) and (dilation == 1 or (w.shape[2] == 3 and 1 < dilation < 4096)))
 
 
-def conv2d_nhwc(x, w, b=None, res=None, want_stats=False, passthrough=False):
-    """3x3 "same" / 1x1 convolution of a features-last map; returns y, or (y, stats) with want_stats.  ``passthrough``: x is appended to
-    the results -- hand THAT tensor to the other consumers of x (a residual connection): their gradient is then added inside the data
+def conv2d_nhwc(x, w, b=None, res=None, want_stats=False, passthrough=False, dilation=1):
+    """3x3 "same" / 1x1 convolution of a features-last map; returns y, or (y, stats) with want_stats.  ``dilation``: the 3x3 taps are
+    that many pixels apart, with as much zero padding (torch's Conv2d(padding=d, dilation=d)).  ``passthrough``: x is appended to the
+    results -- hand THAT tensor to the other consumers of x (a residual connection): their gradient is then added inside the data
     gradient's epilogue."""
     L.require_cuda(x)
-    if not conv_supported(x, w):
-        raise L.P4CError(f"ops_gemm.conv2d_nhwc: unsupported operands (x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} {w.dtype})")
-    y, stats, xp = _Conv.apply(x, w, b, res, bool(want_stats), bool(passthrough))
+    if not conv_supported(x, w, dilation):
+        raise L.P4CError(f"ops_gemm.conv2d_nhwc: unsupported operands (x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} {w.dtype}, "
+                         f"dilation {dilation})")
+    y, stats, xp = _Conv.apply(x, w, b, res, bool(want_stats), bool(passthrough), int(dilation))
     out = (y, stats) if want_stats else (y,)
     if passthrough:
         out = out + (xp,)

@@ -4,7 +4,8 @@ reference's ``py4cast_plugin_example.py``; see py4cast/models.py:23-46): registe
 MI355X-native models.  Put the repository root on PYTHONPATH and ``model_name: HalfUNet`` (or
 ``HalfUNetMI355X`` next to a real mfai install, which already owns the name ``HalfUNet``)
 selects the HIP implementation; likewise ``GraphLam`` / ``GraphLamMI355X`` (mesh GNN on the edge kernels) and
-``SwinUNetR`` / ``SwinUNetRMI355X`` (fused window attention), ``UNet`` / ``UNetMI355X``, ``Segformer`` / ``SegformerMI355X``.
+``SwinUNetR`` / ``SwinUNetRMI355X`` (fused window attention), ``UNet`` / ``UNetMI355X``, ``Segformer`` / ``SegformerMI355X``,
+``DeepLabV3`` / ``DeepLabV3MI355X``.
 """
 
 from dataclasses import dataclass
@@ -24,6 +25,7 @@ from py4cast_amd.hilamparallel import HiLamParallelMI355X, HiLamParallelSettings
 from py4cast_amd.unetrpp import UNetRPPMI355X, UNetRPPSettings  # noqa: F401,E402
 from py4cast_amd.unet import UNetMI355X, UNetSettings  # noqa: F401,E402
 from py4cast_amd.segformer import SegformerMI355X, SegformerSettings  # noqa: F401,E402
+from py4cast_amd.deeplabv3 import DeepLabV3MI355X, DeepLabV3Settings  # noqa: F401,E402
 
 if not HAVE_MFAI:
     # stand-alone: take the upstream names so that config/CLI/model/halfunet.yaml / graphlam.yaml work unchanged
@@ -52,6 +54,9 @@ if not HAVE_MFAI:
         register = True
 
     class Segformer(SegformerMI355X):   # config/CLI/model/segformer.yaml (mfai's Segformer)
+        register = True
+
+    class DeepLabV3(DeepLabV3MI355X):   # config/CLI/model/deeplabv3.yaml (mfai's DeepLabV3, smp's network)
         register = True
 
 
