@@ -1,6 +1,7 @@
 """
 DeepLabV3 (py4cast_amd/deeplabv3.py) on the GPU: the dilated implicit-GEMM convolution (csrc/gemm.hip, forward / data / weight
-gradient), the stem tail, the ASPP pooling branch with the projection's input and the align_corners=True up-sampling (csrc/deeplab.hip,
+gradient), the strided convolutions as patch gather + GEMM (_PatchConv, at the network's three geometries), an identity residual block
+at dilations 1 / 2 / 4 (conv1's passthrough into the residual batch norm), the stem tail, the ASPP pooling branch with the projection's input and the align_corners=True up-sampling (csrc/deeplab.hip,
 csrc/resize.hip) against float64 torch on the same operands; the whole network against the float64 restatement
 (tests/deeplabv3_reference.py) in both flavours, the Dropout node with its mask, the native route of a bf16 step (no library
 convolution / GEMM / cat / pool / interpolate / norm / dropout; bit-identical reruns), HIP-graph replay against the eager step and a
@@ -80,6 +81,133 @@ def test_dilation_is_rejected_where_unserved(gpu_device):
     assert not G.conv_supported(x, torch.zeros(8, 8, 1, 1, device=gpu_device), 2)
     assert not G.conv_supported(x, torch.zeros(8, 8, 3, 3, device=gpu_device), 0)
     assert G.conv_supported(x, torch.zeros(8, 8, 3, 3, device=gpu_device), 36)
+
+
+# ------------------------------------------------------------------------------------------------ strided convolutions (_PatchConv)
+@pytest.mark.parametrize("B,H,W,C,Ci,Co,k,s,p", [(2, 64, 64, 72, 69, 64, 7, 2, 3), (1, 37, 50, 72, 69, 64, 7, 2, 3), (2, 32, 48, 48, 46, 64, 7, 2, 3),
+                                                 (2, 64, 48, 64, 64, 128, 3, 2, 1), (2, 33, 17, 64, 64, 128, 3, 2, 1),
+                                                 (2, 64, 64, 64, 64, 128, 1, 2, 0), (1, 31, 45, 64, 64, 128, 1, 2, 0)])
+def test_patch_conv_against_float64(gpu_device, B, H, W, C, Ci, Co, k, s, p):
+    """DeepLabV3MI355X._patch (patch gather + GEMM with the statistics epilogue; backward: GEMM + the gather-form scatter, and the
+    weight GEMM) at the network's strided geometries: the stem's 7x7 / 2 / 3 on a map zero-padded to C > Ci channels (the weight's
+    zero-padded columns), layer2.0's 3x3 / 2 / 1 and its downsample's 1x1 / 2 / 0 -- odd and non-square grids included"""
+    from py4cast_amd.deeplabv3 import DeepLabV3MI355X
+
+    dev = gpu_device
+    g = gen(dev, H * W + C + k)
+    x = torch.randn(B, H, W, C, device=dev, generator=g)
+    x[..., Ci:] = 0                                    # the zero-padded input rows, as the model pads them
+    x = x.to(torch.bfloat16)
+    conv = torch.nn.Conv2d(Ci, Co, k, stride=s, padding=p, bias=False).to(dev)
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(Co, Ci, k, k, device=dev, generator=g) / (Ci * k * k) ** 0.5)
+
+    def run():
+        conv.weight.grad = None
+        xg = x.clone().requires_grad_(True)
+        y, st = DeepLabV3MI355X._patch(conv, xg)
+        y.backward(dy)
+        torch.cuda.synchronize()
+        return y.detach(), st, xg.grad, conv.weight.grad.clone()
+
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    dy = torch.randn(B, Ho, Wo, Co, device=dev, generator=g).to(torch.bfloat16)
+    y, st, dx, dw = run()
+    assert y.shape == (B, Ho, Wo, Co) and dx.shape == x.shape
+    x64 = x.double().permute(0, 3, 1, 2).requires_grad_(True)
+    w64 = F.pad(conv.weight.detach().to(torch.bfloat16).double(), (0, 0, 0, 0, 0, C - Ci)).requires_grad_(True)   # as the GEMM reads it
+    y64 = F.conv2d(x64, w64, stride=s, padding=p)
+    close_bf16(y.float().permute(0, 3, 1, 2), y64, "y")
+    # the statistics epilogue: column sums of the ROUNDED output
+    sm = st.double().sum(0)
+    yr = y.double().reshape(-1, Co)
+    assert rel(sm[0], yr.sum(0)) <= 1e-5 and rel(sm[1], (yr * yr).sum(0)) <= 1e-5
+    y64.backward(dy.double().permute(0, 3, 1, 2))
+    close_bf16(dx.float().permute(0, 3, 1, 2), x64.grad, "dx")
+    assert not dx[..., Ci:].any(), "dx of the padding channels"
+    assert rel(dw, w64.grad[:, :Ci]) <= 5e-4, rel(dw, w64.grad[:, :Ci])
+    # a rerun is bit-identical
+    y2, st2, dx2, dw2 = run()
+    assert torch.equal(y2, y) and torch.equal(st2, st) and torch.equal(dx2, dx) and torch.equal(dw2, dw)
+
+
+# ------------------------------------------------------------------------------------------------ residual block
+@pytest.mark.parametrize("d", [1, 2, 4])
+@pytest.mark.parametrize("B,H,W,C", [(2, 32, 32, 64), (2, 24, 40, 128)])
+def test_residual_block_against_float64(gpu_device, d, B, H, W, C):
+    """an identity BasicBlock as DeepLabV3MI355X._block runs it: y1, st1, idn = conv2d_nhwc(x, w1, passthrough=True, dilation=d);
+    h = relu(bn1(y1)); out = relu(bn2(conv2d_nhwc(h, w2, dilation=d)) + idn) -- the residual's gradient added in conv1's data-gradient
+    epilogue.  Each stage against float64 on the device's own stored operands and incoming gradients (retained), decisions from the
+    stored outputs"""
+    from py4cast_amd import ops_gemm as G
+
+    dev = gpu_device
+    g = gen(dev, 100 * d + C + H)
+    x = torch.randn(B, H, W, C, device=dev, generator=g).to(torch.bfloat16)
+    w1 = (torch.randn(C, C, 3, 3, device=dev, generator=g) / (3 * C ** 0.5)).requires_grad_(True)
+    w2 = (torch.randn(C, C, 3, 3, device=dev, generator=g) / (3 * C ** 0.5)).requires_grad_(True)
+    bn1, bn2 = torch.nn.BatchNorm2d(C).to(dev), torch.nn.BatchNorm2d(C).to(dev)
+    with torch.no_grad():
+        for bn in (bn1, bn2):
+            bn.weight.uniform_(0.5, 1.5, generator=g)
+            bn.bias.uniform_(-0.3, 0.3, generator=g)
+    xg = x.clone().requires_grad_(True)
+    y1, st1, idn = G.conv2d_nhwc(xg, w1, want_stats=True, passthrough=True, dilation=d)
+    h = G.batch_norm_act(y1, st1, bn1, slope=0.0)
+    y2, st2 = G.conv2d_nhwc(h, w2, want_stats=True, dilation=d)
+    out = G.batch_norm_act(y2, st2, bn2, slope=0.0, res=idn)
+    for t in (y1, h, y2):
+        t.retain_grad()
+    dout = torch.randn(out.shape, device=dev, generator=g).to(torch.bfloat16)
+    out.backward(dout)
+    torch.cuda.synchronize()
+
+    def conv64(inp, w, dy=None):
+        i64 = inp.detach().double().permute(0, 3, 1, 2).requires_grad_(True)
+        w64 = w.detach().to(torch.bfloat16).double().requires_grad_(True)
+        o = F.conv2d(i64, w64, padding=d, dilation=d)
+        if dy is None:
+            return o.permute(0, 2, 3, 1).detach()
+        o.backward(dy.double().permute(0, 3, 1, 2))
+        return o.permute(0, 2, 3, 1).detach(), i64.grad.permute(0, 2, 3, 1), w64.grad
+
+    def bn64(y, bn, res=None, mask=None, dz=None):
+        r = y.detach().double().reshape(-1, C)
+        n = r.shape[0]
+        mean, var = r.mean(0), r.var(0, unbiased=False)
+        rstd = torch.rsqrt(var + bn.eps)
+        xhat = (r - mean) * rstd
+        z = xhat * bn.weight.detach().double() + bn.bias.detach().double()
+        if res is not None:
+            z = z + res.detach().double().reshape(-1, C)
+        o = torch.relu(z).view(y.shape)
+        if dz is None:
+            return o, None, None, None
+        dzz = dz.detach().double().reshape(-1, C) * mask.reshape(-1, C)
+        db, dg = dzz.sum(0), (dzz * xhat).sum(0)
+        dy = bn.weight.detach().double() * rstd * (dzz - db / n - xhat * dg / n)
+        return o, dy.view(y.shape), dg, db
+
+    # forward, stage by stage on the stored operands
+    close_bf16(y1.float(), conv64(x, w1), "y1")
+    close_bf16(h.float(), bn64(y1, bn1)[0], "h")
+    close_bf16(y2.float(), conv64(h, w2), "y2")
+    close_bf16(out.float(), bn64(y2, bn2, res=x)[0], "out")
+    assert torch.equal(idn, x)
+    # backward, stage by stage on the device's incoming gradients and stored decisions
+    _, dy2, dg2, db2 = bn64(y2, bn2, res=x, mask=out.detach() > 0, dz=dout)
+    close_bf16(y2.grad.float(), dy2, "dy2")
+    assert rel(bn2.weight.grad, dg2) <= 5e-3 and rel(bn2.bias.grad, db2) <= 5e-3
+    _, dh, dw2 = conv64(h, w2, y2.grad)
+    close_bf16(h.grad.float(), dh, "dh")
+    assert rel(w2.grad, dw2) <= 3e-3, rel(w2.grad, dw2)
+    _, dy1, dg1, db1 = bn64(y1, bn1, mask=h.detach() > 0, dz=h.grad)
+    close_bf16(y1.grad.float(), dy1, "dy1")
+    assert rel(bn1.weight.grad, dg1) <= 5e-3 and rel(bn1.bias.grad, db1) <= 5e-3
+    _, dx1, dw1 = conv64(x, w1, y1.grad)
+    dres = dout.double() * (out.detach() > 0)            # the identity edge: relu'(bn2(y2) + x) dout
+    close_bf16(xg.grad.float(), dx1 + dres, "dx (conv1's data gradient + the residual's, one epilogue)")
+    assert rel(w1.grad, dw1) <= 3e-3, rel(w1.grad, dw1)
 
 
 # ------------------------------------------------------------------------------------------------ stem tail
