@@ -393,6 +393,24 @@ def kernel_bytes():
     return out
 
 
+def entry_point_roofline(ktimes):
+    """bench.py's roofline object of a model that times its native entry points: the achieved HBM rate of the one that takes the most
+    time -- the algorithmic bytes of its calls (stated by the wrappers next to each call, kernel_bytes()) over their HIP-event
+    durations ``ktimes`` = kernel_times().  None when no timed entry point states its bytes."""
+    nbytes = kernel_bytes()
+    names = [k for k in ktimes if k in nbytes]
+    if not names:
+        return None
+    name = max(names, key=lambda k: ktimes[k][0] * ktimes[k][1])
+    calls, avg_ms = ktimes[name]
+    gbs = nbytes[name] / (calls * avg_ms * 1e-3) / 1e9
+    return {"bound": "hbm", "kernel": f"{name} (all launches)", "achieved": gbs, "peak": 8000.0, "unit": "GB/s",
+            "frac": gbs / 8000.0, "traffic": None, "algorithmic_bytes_per_launch": nbytes[name] / calls,
+            "avg_launch_ms": avg_ms, "launches": calls,
+            "all": {k: {"calls": ktimes[k][0], "avg_ms": round(ktimes[k][1], 4),
+                        "GBps": round(nbytes[k] / (ktimes[k][0] * ktimes[k][1] * 1e-3) / 1e9, 1)} for k in names}}
+
+
 # bench.py's step-level roofline of the widened models: with WORK[0] a dict, every native call adds the algorithmic HBM bytes / matrix
 # flops its wrapper states ({"bytes": .., "flops": .., "calls": .., "unstated": ..}); None = off (no cost on the product path)
 WORK = [None]

@@ -23,8 +23,8 @@ What runs where, bf16 (``compute_dtype`` / ``activation_dtype`` "bf16"), feature
   (``ops_gemm.conv2d_nhwc(dilation=d)``) with the batch-norm statistics from the GEMM epilogue; BN (+ residual) + ReLU:
   ``ops_gemm.batch_norm_act``; the residual's gradient is added in conv1's data-gradient epilogue (``passthrough``);
 * the strided convolutions (conv1 7x7 / 2, layer2.0.conv1 3x3 / 2, layer2.0.downsample 1x1 / 2): a patch gather
-  (``p4c_seg_patch_gather``, nn.Unfold's column order) + one GEMM with the statistics epilogue; the data gradient is the GEMM + the
-  gather-form scatter (skipped for the network input);
+  (``p4c_seg_patch_gather``, nn.Unfold's column order) + one GEMM with the statistics epilogue (``ops_patch._PatchConv``); the data
+  gradient is the GEMM + the gather-form scatter (skipped for the network input);
 * the stem tail (bn1 + ReLU + the 3x3 / 2 max-pool) in one pass each way, the ASPP pooling branch in fp32 and the projection's 5 dc-wide
   input (csrc/deeplab.hip); the project's Dropout as the multiplier of its batch-norm pass;
 * the head's ×8 bilinear up-sampling with align_corners=True (csrc/resize.hip), on the head output padded to 8 channels.
@@ -38,14 +38,13 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
 from . import ops_gemm as G
-from .base import ModelABC, ModelType
-from .segformer import _PatchGather
-from .unet import _bn_stats
+from .base import ModelType
+from .conv_model import ConvModelMI355X, cast_out, crop_channels, pad_head, pad_rows, pad_weight_in
+from .ops_patch import _PatchConv
 
 try:
     from dataclasses_json import dataclass_json
@@ -146,40 +145,6 @@ class ASPP(nn.Module):
 
 
 # ---------------------------------------------------------------- native nodes
-class _PatchConv(torch.autograd.Function):
-    """y (B, Ho, Wo, Co) = Conv2d(C, Co, k, stride, pad, bias=False) of a features-last bf16 map as a patch gather (nn.Unfold's column
-    order) + one GEMM whose epilogue leaves the batch-norm column sums; w2d = the weight's (Co, C k^2) view"""
-
-    @staticmethod
-    def forward(ctx, x, w2d, k, stride, pad):
-        cols = _PatchGather.forward(ctx, x, k, stride, pad)
-        B, Ho, Wo, K = cols.shape
-        Co = w2d.shape[0]
-        c2 = cols.view(-1, K)
-        fwd, dgr = G.weight_images(w2d, 1)
-        y, _, stats = G.gemm_nt(c2, fwd, Co, K, want_stats=True)
-        ctx.save_for_backward(c2, dgr)
-        ctx.pgeom, ctx.wdtype = (B, Ho, Wo, K, Co), w2d.dtype
-        ctx.mark_non_differentiable(stats)
-        ctx.set_materialize_grads(False)
-        return y.view(B, Ho, Wo, Co), stats
-
-    @staticmethod
-    def backward(ctx, dy, _dstats):
-        c2, dgr = ctx.saved_tensors
-        B, Ho, Wo, K, Co = ctx.pgeom
-        dy2 = G._rows(dy, Co)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dcols = G.gemm_nt(dy2, dgr, K, Co)[0].view(B, Ho, Wo, K)
-            dx = _PatchGather.backward(ctx, dcols)[0]
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw, _ = G.gemm_tn(dy2, c2, Co, K)
-            dw = dw.to(ctx.wdtype)
-        return dx, dw, None, None, None
-
-
 class _StemTail(torch.autograd.Function):
     """pool = max_pool2d(relu(bn(y)), 3, 2, 1) of the stem convolution's raw output; one native pass each way (csrc/deeplab.hip) + the
     batch norm's finalize / apply"""
@@ -189,7 +154,7 @@ class _StemTail(torch.autograd.Function):
         yc = y.contiguous()
         B, H, W, C = yc.shape
         dev = yc.device
-        st = _bn_stats(yc, stats, bn, training)
+        st = G.bn_statistics(yc, stats, bn, training)
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         pool = torch.empty(B, Ho, Wo, C, dtype=yc.dtype, device=dev)
         arg = torch.empty(B, Ho, Wo, C, dtype=torch.uint8, device=dev)
@@ -205,24 +170,13 @@ class _StemTail(torch.autograd.Function):
         yc, st, arg = ctx.saved_tensors
         B, H, W, C = yc.shape
         dev = yc.device
-        N = B * H * W
         dpool = dpool.contiguous()
         nb = L.lib().p4c_deeplab_stem_bwd_blocks(B, H, W, C)
         part = torch.empty(1, nb, 2, C, dtype=torch.float32, device=dev)
         dz = torch.empty_like(yc)
         L.call("p4c_deeplab_stem_bwd", L.ptr(yc), L.ptr(dpool), L.ptr(arg), L.ptr(st[2]), L.ptr(st[3]), L.ptr(st[0]), L.ptr(st[1]), L.ptr(dz),
                L.ptr(part), B, H, W, C, L.stream(dev), alg_bytes=4 * yc.numel() + 3 * dpool.numel())
-        co = torch.empty(2, C, dtype=torch.float32, device=dev)
-        dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
-        L.call("p4c_inorm_finalize_bwd", L.ptr(part), nb, 1, N, C, 0, None, None, L.ptr(co[0]), L.ptr(co[1]), L.ptr(dgb[0]), L.ptr(dgb[1]),
-               L.stream(dev))
-        if not ctx.training:
-            co.zero_()          # running statistics are constants
-        dy = torch.empty_like(yc)
-        L.call("p4c_inorm_apply", L.ptr(yc), None, L.ptr(dz), L.ptr(dz), L.ptr(st[2]), None, L.ptr(st[0]), L.ptr(st[1]), L.ptr(co[0]),
-               L.ptr(co[1]), 1.0, L.ptr(dy), None, L.dtype_code(yc.dtype), 1, N, C, L.stream(dev), alg_bytes=2 * yc.numel() * 3)
-        dg = dgb[0] if ctx.has_affine else None
-        db = dgb[1] if ctx.has_affine else None
+        dy, dg, db = G.bn_tail_backward(yc, dz, part, nb, st, ctx.training, ctx.has_affine)
         return dy, None, dg, db, None, None
 
 
@@ -251,6 +205,7 @@ class _AsppAssemble(torch.autograd.Function):
         D = w.shape[0]
         HW = H * W
         dev = xc.device
+        mom, rm, rv, nbt = G.bn_running(bn, training, dev)
         S = _colsum_chunks(HW)
         part = torch.empty(B, S, C, dtype=torch.float32, device=dev)
         L.call("p4c_deeplab_colsum", L.ptr(xc), C, L.ptr(part), B, HW, C, S, L.stream(dev), alg_bytes=2 * xc.numel())
@@ -259,11 +214,8 @@ class _AsppAssemble(torch.autograd.Function):
         z = torch.empty(B, D, dtype=torch.float32, device=dev)
         stat = torch.empty(2, D, dtype=torch.float32, device=dev)
         pooled = torch.empty(B, D, dtype=torch.float32, device=dev)
-        track = bn.track_running_stats and bn.running_mean is not None
-        nbt = bn.num_batches_tracked if (track and training) else None
-        mom = 0.1 if bn.momentum is None else bn.momentum
         L.call("p4c_deeplab_pool_head_fwd", L.ptr(part), S, HW, L.ptr(w32), L.ptr(G._f32(gamma)), L.ptr(G._f32(beta)), float(bn.eps), float(mom),
-               L.ptr(bn.running_mean if track else None), L.ptr(bn.running_var if track else None), L.ptr(nbt), int(training), B, C, D,
+               L.ptr(rm), L.ptr(rv), L.ptr(nbt), int(training), B, C, D,
                L.ptr(mean), L.ptr(z), L.ptr(stat), L.ptr(pooled), L.stream(dev))
         a = [t.contiguous() for t in (a0, a1, a2, a3)]
         buf = torch.empty(B, H, W, 5 * D, dtype=xc.dtype, device=dev)
@@ -313,8 +265,6 @@ def aspp_assemble(x: torch.Tensor, branches, pool_branch: ASPPPooling) -> torch.
     training = bn.training or bn.running_mean is None
     if training and B < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
-    if training and bn.momentum is None and bn.track_running_stats:
-        raise L.P4CError("deeplabv3.aspp_assemble: BatchNorm2d(momentum=None) (cumulative average) is not served; give a momentum")
     return _AsppAssemble.apply(x, *branches, conv.weight, bn.weight, bn.bias, bn, training)
 
 
@@ -388,25 +338,16 @@ def load_encoder_weights(encoder: ResNetEncoder, name: str, in_channels: int, pa
 
 
 # ---------------------------------------------------------------- the model
-class DeepLabV3MI355X(ModelABC, nn.Module):
+class DeepLabV3MI355X(ConvModelMI355X):
     """smp's DeepLabV3 as mfai builds it (module docstring) on the native kernels of this package."""
 
     settings_kls = DeepLabV3Settings
-    onnx_supported = False
-    supported_num_spatial_dims = (2,)
-    num_spatial_dims = 2
-    features_last = True
     model_type = ModelType.CONVOLUTIONAL
-    register = True
-    is_native_hip = True
-    rollout_padded_output = False
 
     def __init__(self, in_channels: int, out_channels: int, input_shape: tuple = None, settings: DeepLabV3Settings = DeepLabV3Settings(),
                  *args, **kwargs):
-        super().__init__()
-        self.in_channels, self.out_channels, self.input_shape = in_channels, out_channels, input_shape
-        self.num_output_features = out_channels
-        self._settings = s = settings
+        super().__init__(in_channels, out_channels, input_shape, settings)
+        s = settings
         if s.encoder_name not in ENCODER_BLOCKS:
             raise ValueError(f"DeepLabV3MI355X: encoder_name {s.encoder_name!r} is not served (one of {sorted(ENCODER_BLOCKS)})")
         if s.encoder_depth != 5:
@@ -421,13 +362,7 @@ class DeepLabV3MI355X(ModelABC, nn.Module):
             raise ValueError("DeepLabV3MI355X: aux_params (the classification head) is not served")
         if not 0.0 <= s.aspp_dropout < 1.0:
             raise ValueError(f"DeepLabV3MI355X: aspp_dropout must be in [0, 1), got {s.aspp_dropout}")
-        act = s.activation_dtype or s.compute_dtype
-        if s.compute_dtype not in ("f32", "bf16") or act not in ("f32", "bf16"):
-            raise ValueError(f"DeepLabV3MI355X: compute_dtype / activation_dtype must be 'f32' or 'bf16', got {s.compute_dtype} / {act}")
-        if act != s.compute_dtype:
-            raise ValueError(f"DeepLabV3MI355X: compute_dtype {s.compute_dtype} with activation_dtype {act} is not served: the bf16 route "
-                             "keeps bf16 activations, the fp32 route fp32 ones")
-        self.act_dtype = torch.bfloat16 if act == "bf16" else torch.float32
+        self._resolve_dtypes(s)
         dc = s.decoder_channels
         self.encoder = ResNetEncoder(in_channels, ENCODER_BLOCKS[s.encoder_name])
         self.decoder = nn.Sequential(ASPP(512, dc, ASPP_RATES, s.aspp_dropout), nn.Conv2d(dc, dc, 3, padding=1, bias=False),
@@ -443,8 +378,6 @@ class DeepLabV3MI355X(ModelABC, nn.Module):
                                    "p4c_deeplab_pool_broadcast", "p4c_upsample_bilinear_ac_fwd", "p4c_upsample_bilinear_ac_bwd",
                                    "p4c_inorm_apply", "p4c_inorm_apply_mul")
         self.check_required_attributes()
-
-    roofline_from_entry_points = True    # bench.py: time every call of the native entry points above
 
     def _init_weights(self):
         for m in self.encoder.modules():
@@ -463,32 +396,6 @@ class DeepLabV3MI355X(ModelABC, nn.Module):
         nn.init.xavier_uniform_(head.weight)
         nn.init.constant_(head.bias, 0)
 
-    @property
-    def settings(self):
-        return self._settings
-
-    def roofline(self, ktimes, B, H, W):
-        """bench.py: achieved HBM rate of the native entry point that takes the most time (the UNETR++ accounting)"""
-        from .unetrpp import UNetRPPMI355X
-
-        return UNetRPPMI355X.roofline(self, ktimes, B, H, W)
-
-    @property
-    def native(self) -> bool:
-        """the bf16 route (csrc/gemm.hip, csrc/deeplab.hip, csrc/resize.hip); fp32 runs on the library"""
-        return self.act_dtype == torch.bfloat16
-
-    @property
-    def cin_pad(self) -> int:
-        return (self.in_channels + 7) // 8 * 8
-
-    @property
-    def rollout_input_format(self):
-        """(dtype, channel count) of the rows the rollout's build_x should emit: bf16, zero-padded to the GEMM's 8-channel granularity"""
-        if not self.native:
-            return None
-        return torch.bfloat16, self.cin_pad
-
     def check_grid(self, H: int, W: int) -> None:
         if H % 8 or W % 8:
             nh, nw = (H + 7) // 8 * 8, (W + 7) // 8 * 8
@@ -499,9 +406,7 @@ class DeepLabV3MI355X(ModelABC, nn.Module):
     @staticmethod
     def _patch(conv: nn.Conv2d, x: torch.Tensor):
         """strided convolution: patch gather + GEMM; (y, stats)"""
-        w = conv.weight
-        if w.shape[1] != x.shape[-1]:        # conv1 on zero-padded input rows: zero weight columns for the padding channels
-            w = F.pad(w, (0, 0, 0, 0, 0, x.shape[-1] - w.shape[1]))
+        w = pad_weight_in(conv.weight, x.shape[-1])        # (conv1 on zero-padded input rows)
         k = conv.kernel_size[0]
         return _PatchConv.apply(x, w.reshape(w.shape[0], -1), k, conv.stride[0], conv.padding[0])
 
@@ -548,14 +453,8 @@ class DeepLabV3MI355X(ModelABC, nn.Module):
         yd, sd = G.conv2d_nhwc(a, dconv.weight, want_stats=True)
         a = G.batch_norm_act(yd, sd, dbn, slope=0.0)
         head = self.segmentation_head[0]
-        w, b = head.weight, head.bias
-        pad = (-w.shape[0]) % 8
-        if pad:                      # zero output rows up to the 8-channel granularity, sliced off after the up-sampling
-            w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, pad))
-            b = F.pad(b, (0, pad))
-        z = G.conv2d_nhwc(a, w, b)
-        up = upsample_bilinear_ac(z, 8)
-        return up[..., : self.out_channels] if pad else up
+        w, b = pad_head(head.weight, head.bias)       # (8-channel granularity: sliced off after the up-sampling)
+        return crop_channels(upsample_bilinear_ac(G.conv2d_nhwc(a, w, b), 8), self.out_channels)
 
     # ---------------------------------------------------------------- nn.Module API
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -570,10 +469,8 @@ class DeepLabV3MI355X(ModelABC, nn.Module):
             if self.training and x.shape[0] < 2:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size "
                                  f"{torch.Size([x.shape[0], self._settings.decoder_channels, 1, 1])}")
-            if x.shape[-1] % 8:
-                x = F.pad(x, (0, self.cin_pad - x.shape[-1]))
-            y = self._forward_native(x.contiguous())
+            y = self._forward_native(pad_rows(x, self.cin_pad).contiguous())
         else:
             xin = x[..., : self.in_channels].permute(0, 3, 1, 2)
             y = self.segmentation_head(self.decoder(self.encoder(xin))).permute(0, 2, 3, 1)
-        return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)
+        return cast_out(y, out_dtype)

@@ -11,7 +11,8 @@ They carry what mfai's UNETR++ / SwinUNETR (py4cast/models.py:10-20; config/CLI/
   output for the batch norm that follows
 * ``batch_norm_act(y, stats, ...)``   BatchNorm2d (training statistics from the producer's sums, running statistics updated) +
   LeakyReLU (+ residual) as one node on the streaming kernels of csrc/inorm.hip (a batch norm is an instance norm of the batch seen
-  as one sample)
+  as one sample); its front ``bn_statistics`` / ``bn_running`` and the tail backward ``bn_tail_backward`` also serve the fused
+  tails of unet.py and deeplabv3.py
 
 No CPU fallback: every entry point raises on CPU tensors."""
 
@@ -509,31 +510,74 @@ def conv2d_nhwc(x, w, b=None, res=None, want_stats=False, passthrough=False, dil
     return out if len(out) > 1 else y
 
 
+def bn_running(bn: torch.nn.BatchNorm2d, training: bool, device):
+    """(momentum, running_mean, running_var, num_batches_tracked) as a native batch-norm statistics kernel takes them: the running
+    buffers when the module tracks them (else None), the counter in training only -- it is incremented by the statistics kernel itself,
+    on the device, so captured into a HIP graph like the kernels around it.  Refuses what the kernels do not serve."""
+    if training and bn.momentum is None and bn.track_running_stats:
+        # torch: the cumulative moving average, factor 1 / num_batches_tracked -- a per-step value the fused finalize does not take
+        raise L.P4CError("ops_gemm.bn_running: BatchNorm2d(momentum=None) (cumulative average) is not served; give a momentum")
+    track = bn.track_running_stats and bn.running_mean is not None
+    nbt = bn.num_batches_tracked if (track and training) else None
+    if nbt is not None and (nbt.dtype != torch.int64 or nbt.device != device):
+        raise L.P4CError("ops_gemm.bn_running: num_batches_tracked must be an int64 tensor on the map's device")
+    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
+    return (0.1 if bn.momentum is None else bn.momentum), rm, rv, nbt
+
+
+def bn_statistics(yc: torch.Tensor, stats, bn: torch.nn.BatchNorm2d, training: bool) -> torch.Tensor:
+    """(mean, rstd, scale, shift) (4, C) fp32 of a BatchNorm2d over the rows of yc (N, C): from the producer's sums, one reduction pass
+    (p4c_inorm_reduce), or the running statistics (eval); updates the running statistics and num_batches_tracked in training"""
+    C = yc.shape[-1]
+    N = yc.numel() // C
+    dev = yc.device
+    st = torch.empty(4, C, dtype=torch.float32, device=dev)
+    g32, b32 = _f32(bn.weight), _f32(bn.bias)
+    if training:
+        mom, rm, rv, nbt = bn_running(bn, True, dev)
+        if stats is None:
+            nb = L.lib().p4c_inorm_blocks(N, C)
+            stats = torch.empty(nb, 2, C, dtype=torch.float32, device=dev)
+            L.call("p4c_inorm_reduce", L.ptr(yc), None, None, None, None, 1.0, L.ptr(stats), L.dtype_code(yc.dtype), 1, N, C, L.stream(dev))
+        L.call("p4c_bnorm_finalize", L.ptr(stats), stats.shape[0], float(N), C, L.ptr(g32), L.ptr(b32), float(bn.eps), float(mom),
+               L.ptr(rm), L.ptr(rv), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), L.ptr(nbt), L.stream(dev))
+    else:
+        st[0] = bn.running_mean
+        st[1] = torch.rsqrt(bn.running_var.float() + bn.eps)
+        st[2] = st[1] * (1.0 if g32 is None else g32)
+        st[3] = (0.0 if b32 is None else b32) - st[0] * st[2]
+    return st
+
+
+def bn_tail_backward(yc, dz, part, nb, st, training: bool, has_affine: bool):
+    """(dy, dgamma, dbeta) of a batch norm whose fused tail (activation, pooling) has left dz = the gradient at the norm's output and
+    the partial sums `part` (1, nb, 2, C) of dz and dz * xhat: finalize, then one apply pass (csrc/inorm.hip)"""
+    C = yc.shape[-1]
+    N = yc.numel() // C
+    dev = yc.device
+    co = torch.empty(2, C, dtype=torch.float32, device=dev)
+    dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
+    L.call("p4c_inorm_finalize_bwd", L.ptr(part), nb, 1, N, C, 0, None, None, L.ptr(co[0]), L.ptr(co[1]), L.ptr(dgb[0]), L.ptr(dgb[1]),
+           L.stream(dev))
+    if not training:
+        co.zero_()          # running statistics are constants: dy = scale * dz
+    dy = torch.empty_like(yc)
+    L.call("p4c_inorm_apply", L.ptr(yc), None, L.ptr(dz), L.ptr(dz), L.ptr(st[2]), None, L.ptr(st[0]), L.ptr(st[1]), L.ptr(co[0]),
+           L.ptr(co[1]), 1.0, L.ptr(dy), None, L.dtype_code(yc.dtype), 1, N, C, L.stream(dev), alg_bytes=yc.element_size() * yc.numel() * 3)
+    return (dy, dgb[0], dgb[1]) if has_affine else (dy, None, None)
+
+
 class _BatchNormAct(torch.autograd.Function):
     """out = lrelu(batch_norm(y) (+ res), slope) for y (B,H,W,C) features-last: statistics over (B,H,W) per channel from the producer's
     partial sums (training) or the running statistics (eval); the streaming kernels of csrc/inorm.hip with the batch as ONE sample."""
 
     @staticmethod
-    def forward(ctx, y, stats, gamma, beta, res, running_mean, running_var, training, momentum, eps, slope, batches_tracked=None,
-                res_passthrough=False, mul=None, mul_factor=1.0):
+    def forward(ctx, y, stats, gamma, beta, res, bn, training, slope, res_passthrough=False, mul=None, mul_factor=1.0):
         yc = y.contiguous()
         C = yc.shape[-1]
         N = yc.numel() // C
         dev = yc.device
-        st = torch.empty(4, C, dtype=torch.float32, device=dev)
-        g32, b32 = _f32(gamma), _f32(beta)
-        if training:
-            if stats is None:   # no producer sums: one reduction pass (p4c_inorm_reduce)
-                nb = L.lib().p4c_inorm_blocks(N, C)
-                stats = torch.empty(nb, 2, C, dtype=torch.float32, device=dev)
-                L.call("p4c_inorm_reduce", L.ptr(yc), None, None, None, None, 1.0, L.ptr(stats), L.dtype_code(yc.dtype), 1, N, C, L.stream(dev))
-            L.call("p4c_bnorm_finalize", L.ptr(stats), stats.shape[0], float(N), C, L.ptr(g32), L.ptr(b32), float(eps), float(momentum),
-                   L.ptr(running_mean), L.ptr(running_var), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), L.ptr(batches_tracked), L.stream(dev))
-        else:
-            st[0] = running_mean
-            st[1] = torch.rsqrt(running_var.float() + eps)
-            st[2] = st[1] * (1.0 if g32 is None else g32)
-            st[3] = (0.0 if b32 is None else b32) - st[0] * st[2]
+        st = bn_statistics(yc, stats, bn, training)
         out = torch.empty_like(yc)
         rc = None if res is None else res.contiguous()
         # mul (groups, C) fp32 >= 0, mul_factor: a multiplier per (row group, channel) behind the activation -- a channel dropout's draw
@@ -560,7 +604,7 @@ class _BatchNormAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dpass):
         if dout is None:
-            return (None, None, None, None, dpass) + (None,) * 10
+            return (None, None, None, None, dpass) + (None,) * 6
         yc, out, st, *rest = ctx.saved_tensors
         mul = rest[0] if rest else None
         C = yc.shape[-1]
@@ -604,7 +648,7 @@ class _BatchNormAct(torch.autograd.Function):
             dres = dpass if dres is None else dres + dpass
         dg = None if ctx.gdtype is None else dgb[0].to(ctx.gdtype)
         db = None if ctx.gdtype is None else dgb[1].to(ctx.gdtype)
-        return (dy, None, dg, db, dres) + (None,) * 10
+        return (dy, None, dg, db, dres) + (None,) * 6
 
 
 def batch_norm_act(y, stats, bn: torch.nn.BatchNorm2d, slope: float = 1.0, res=None, res_passthrough=False, mul=None, mul_factor=1.0):
@@ -618,20 +662,8 @@ def batch_norm_act(y, stats, bn: torch.nn.BatchNorm2d, slope: float = 1.0, res=N
     if y.dtype not in (torch.bfloat16, torch.float32) or y.shape[-1] % 4 or y.shape[-1] > 1024:
         raise L.P4CError(f"ops_gemm.batch_norm_act: unsupported map {tuple(y.shape)} {y.dtype}")
     training = bn.training or bn.running_mean is None
-    if bn.momentum is None and training and bn.track_running_stats:
-        # torch: the cumulative moving average, factor 1 / num_batches_tracked -- a per-step value the fused finalize does not take
-        raise L.P4CError("ops_gemm.batch_norm_act: BatchNorm2d(momentum=None) (cumulative average) is not served; give a momentum")
-    mom = 0.1 if bn.momentum is None else bn.momentum
-    nbt = None
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        # incremented by the statistics kernel itself (p4c_bnorm_finalize; round 6 -- a launch of its own before: 42 per model call):
-        # on the device, so captured into a HIP graph like the kernels around it (replays advance it)
-        nbt = bn.num_batches_tracked
-        if nbt.dtype != torch.int64 or nbt.device != y.device:
-            raise L.P4CError("ops_gemm.batch_norm_act: num_batches_tracked must be an int64 tensor on the map's device")
-    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
-    out, rp = _BatchNormAct.apply(y, stats if training else None, bn.weight, bn.bias, res, rm, rv, training, mom, bn.eps, float(slope), nbt,
-                                  bool(res_passthrough), mul, float(mul_factor))
+    out, rp = _BatchNormAct.apply(y, stats if training else None, bn.weight, bn.bias, res, bn, training, float(slope), bool(res_passthrough), mul,
+                                  float(mul_factor))
     return (out, rp) if res_passthrough else out
 
 

@@ -20,8 +20,8 @@ What runs where, bf16 (``compute_dtype`` / ``activation_dtype`` "bf16"):
 * every 1x1 convolution: the GEMMs of csrc/gemm.hip (``ops_gemm.linear`` / ``ops_gemm.mlp``: the pointwise half of DsConv2d, GELU and
   the second FFN convolution are ONE node, GELU in the epilogue, GELU' in the data gradient's epilogue); the residual adds: forward in
   the epilogues of to_out / fc2, backward inside the LayerNorm's backward launch (the residual takes x from the norm's passthrough);
-* the strided convolutions (downsampler, patch embeddings, the key / value reduction): a patch gather (csrc/segformer.hip) in nn.Unfold's
-  column order, so the GEMM takes the parameter's own (D, C k^2) view; data gradient: the gather-form adjoint;
+* the strided convolutions (downsampler, patch embeddings, the key / value reduction): ``ops_patch.patch_conv``, a patch gather
+  (csrc/segformer.hip) in nn.Unfold's column order, so the GEMM takes the parameter's own (D, C k^2) view; data gradient: the gather-form adjoint;
 * LayerNorm, the depthwise 3x3 convolution, the spatial-reduction attention core and the decoder's nearest up-sampling sum: csrc/segformer.hip;
 * the decoder applies to_segmentation.0 per stage at the stage's resolution (its column block of the weight) and sums the nearest
   up-sampled results -- the same linear map as up-sampling, concatenating and convolving, without the 4 x decoder_dim buffer;
@@ -38,7 +38,9 @@ from torch import nn
 
 from . import _lib as L
 from . import ops_gemm as G
-from .base import ModelABC, ModelType
+from .base import ModelType
+from .conv_model import ConvModelMI355X, cast_out, crop_channels, pad_head, pad_rows, pad_weight_in
+from .ops_patch import patch_conv
 
 try:
     from dataclasses_json import dataclass_json
@@ -185,40 +187,6 @@ def _reduce_into(partial, nb, outs, sinks, dev):
     o2 = torch.empty(outs[1].shape, dtype=torch.float32, device=dev)
     L.call("p4c_seg_reduce_partials", L.ptr(partial), nb, n1, L.ptr(o1), n2, L.ptr(o2), 0, L.stream(dev))
     return o1, o2
-
-
-class _PatchGather(torch.autograd.Function):
-    """cols (B, Ho, Wo, C k^2) = nn.Unfold(k, stride, pad) of a features-last map, columns in Unfold's order c k^2 + ky k + kx"""
-
-    @staticmethod
-    def forward(ctx, x, k, stride, pad):
-        xc = x.contiguous()
-        B, H, W, C = xc.shape
-        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        cols = torch.empty(B, Ho, Wo, C * k * k, dtype=xc.dtype, device=xc.device)
-        L.call("p4c_seg_patch_gather", L.ptr(xc), L.ptr(cols), B, H, W, C, k, stride, pad, L.stream(xc.device),
-               alg_bytes=2 * (xc.numel() + cols.numel()))
-        ctx.geom = (B, H, W, C, k, stride, pad)
-        return cols
-
-    @staticmethod
-    def backward(ctx, dcols):
-        B, H, W, C, k, stride, pad = ctx.geom
-        dcols = dcols.contiguous()
-        dx = torch.empty(B, H, W, C, dtype=dcols.dtype, device=dcols.device)
-        L.call("p4c_seg_patch_scatter", L.ptr(dcols), L.ptr(dx), B, H, W, C, k, stride, pad, C, L.stream(dcols.device),
-               alg_bytes=2 * (dx.numel() + dcols.numel()))
-        return dx, None, None, None
-
-
-def patch_conv(x: torch.Tensor, w2d: torch.Tensor, b: Optional[torch.Tensor], k: int, stride: int, pad: int) -> torch.Tensor:
-    """Conv2d(C, D, k, stride, pad) of a features-last bf16 map with the weight given as its (D, C k^2) view (Unfold's column order)"""
-    L.require_cuda(x)
-    if x.dtype != torch.bfloat16 or x.dim() != 4 or w2d.shape[1] != x.shape[-1] * k * k:
-        raise L.P4CError(f"segformer.patch_conv: unsupported operands (x {tuple(x.shape)} {x.dtype}, w {tuple(w2d.shape)}, k {k})")
-    if k == 1 and stride == 1 and pad == 0:
-        return G.linear(x, w2d, b)
-    return G.linear(_PatchGather.apply(x, k, stride, pad), w2d, b)
 
 
 class _ChanLayerNorm(torch.autograd.Function):
@@ -399,36 +367,22 @@ def up_sum(z0, z1, z2, z3) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------- the model
-class SegformerMI355X(ModelABC, nn.Module):
+class SegformerMI355X(ConvModelMI355X):
     """mfai's Segformer (module docstring) on the native kernels of this package."""
 
     settings_kls = SegformerSettings
-    onnx_supported = False
-    supported_num_spatial_dims = (2,)
-    num_spatial_dims = 2
-    features_last = True
     model_type = ModelType.VISION_TRANSFORMER
-    register = True
-    is_native_hip = True
-    rollout_padded_output = False
 
     def __init__(self, in_channels: int, out_channels: int, input_shape: tuple = None, settings: SegformerSettings = SegformerSettings(),
                  *args, **kwargs):
-        super().__init__()
-        self.in_channels, self.out_channels, self.input_shape = in_channels, out_channels, input_shape
-        self.num_output_features = out_channels
-        self._settings = s = settings
-        act = s.activation_dtype or s.compute_dtype
-        if s.compute_dtype not in ("f32", "bf16") or act not in ("f32", "bf16"):
-            raise ValueError(f"SegformerMI355X: compute_dtype / activation_dtype must be 'f32' or 'bf16', got {s.compute_dtype} / {act}")
-        if act != s.compute_dtype:
-            raise ValueError(f"SegformerMI355X: compute_dtype {s.compute_dtype} with activation_dtype {act} is not served")
+        super().__init__(in_channels, out_channels, input_shape, settings)
+        s = settings
+        self._resolve_dtypes(s)
         dims, heads, ffx, rr = tuple(s.dims), tuple(s.heads), tuple(s.ff_expansion), tuple(s.reduction_ratio)
         if not (len(dims) == len(heads) == len(ffx) == len(rr) == 4):
             raise ValueError("SegformerMI355X: dims, heads, ff_expansion and reduction_ratio need four entries (four stages)")
         if any(d % h for d, h in zip(dims, heads)):
             raise ValueError(f"SegformerMI355X: every dim must be divisible by its head count, got dims {dims} heads {heads}")
-        self.act_dtype = torch.bfloat16 if act == "bf16" else torch.float32
         if self.native:
             if any(d // h != NATIVE_HEAD_DIM for d, h in zip(dims, heads)):
                 raise ValueError(f"SegformerMI355X: the bf16 route serves head_dim {NATIVE_HEAD_DIM} only, got dims {dims} heads {heads}")
@@ -451,33 +405,6 @@ class SegformerMI355X(ModelABC, nn.Module):
                                    "p4c_seg_sra_bwd", "p4c_seg_upsum_fwd", "p4c_seg_upsum_bwd")
         self.prefers_hip_graph = True            # ~10^3 small launches per training step: replayed from a HIP graph (profiles/segformer_*)
         self.check_required_attributes()
-
-    roofline_from_entry_points = True
-
-    @property
-    def settings(self):
-        return self._settings
-
-    def roofline(self, ktimes, B, H, W):
-        from .unetrpp import UNetRPPMI355X
-
-        return UNetRPPMI355X.roofline(self, ktimes, B, H, W)
-
-    @property
-    def native(self) -> bool:
-        """the bf16 route (csrc/segformer.hip + csrc/gemm.hip); fp32 runs on the library"""
-        return self.act_dtype == torch.bfloat16
-
-    @property
-    def cin_pad(self) -> int:
-        return (self.in_channels + 7) // 8 * 8
-
-    @property
-    def rollout_input_format(self):
-        """(dtype, channel count) of the rows the rollout's build_x should emit: bf16, zero-padded to the GEMM's 8-channel granularity"""
-        if not self.native:
-            return None
-        return torch.bfloat16, self.cin_pad
 
     def check_grid(self, H: int, W: int) -> None:
         """raise ValueError unless every stride and every r x r key reduction divides the (H, W) grid exactly (multiples of 64 with
@@ -523,12 +450,8 @@ class SegformerMI355X(ModelABC, nn.Module):
         return G.mlp(h2, pw.weight.view(Hd, Hd), pw.bias, fc2.weight.view(D, Hd), fc2.bias, res=xr)
 
     def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
-        if x.shape[-1] % 8:
-            x = F.pad(x, (0, self.cin_pad - x.shape[-1]))
-        x = x.contiguous()
-        wd = self.downsampler.weight
-        if wd.shape[1] != x.shape[-1]:      # zero weight columns for the rows' padding channels
-            wd = F.pad(wd, (0, 0, 0, 0, 0, x.shape[-1] - wd.shape[1]))
+        x = pad_rows(x, self.cin_pad).contiguous()
+        wd = pad_weight_in(self.downsampler.weight, x.shape[-1])
         x = patch_conv(x, wd.reshape(wd.shape[0], -1), self.downsampler.bias, 3, 2, 1)
         feats = []
         for (k, st, p), (_, embed, layers) in zip(STAGE_KSP, self.mit.stages):
@@ -547,11 +470,8 @@ class SegformerMI355X(ModelABC, nn.Module):
             zs.append(G.linear(fi, w0[:, i * dd: (i + 1) * dd], seg0.bias if i == 0 else None))
         y = up_sum(*zs)
         O = seg1.out_channels
-        w1, b1 = seg1.weight.view(O, dd), seg1.bias
-        if O % 8:      # the head: zero output rows up to the 8-channel granularity, sliced off after the up-sampling
-            w1, b1 = F.pad(w1, (0, 0, 0, (-O) % 8)), F.pad(b1, (0, (-O) % 8))
-        y = G.upsample_add(G.linear(y, w1, b1), None, 8)
-        return y[..., :O] if y.shape[-1] != O else y
+        w1, b1 = pad_head(seg1.weight.view(O, dd), seg1.bias)      # (8-channel granularity: sliced off after the up-sampling)
+        return crop_channels(G.upsample_add(G.linear(y, w1, b1), None, 8), O)
 
     # ---------------------------------------------------------------- nn.Module API
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -569,4 +489,4 @@ class SegformerMI355X(ModelABC, nn.Module):
         out_dtype = x.dtype
         x = x.to(self.act_dtype)
         y = self._forward_native(x) if self.native else self._forward_library(x)
-        return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)
+        return cast_out(y, out_dtype)

@@ -408,17 +408,4 @@ class SwinUNetRMI355X(ModelABC, nn.Module):
     def roofline(self, ktimes, B, H, W):
         """Achieved HBM rate of the native entry point that takes the most time (algorithmic bytes stated by the wrappers:
         window attention forward = read qkv + write out, backward = read qkv and dout + write dqkv)."""
-        from . import _lib as L
-
-        nbytes = L.kernel_bytes()
-        names = [k for k in ktimes if k in nbytes]
-        if not names:
-            return None
-        name = max(names, key=lambda k: ktimes[k][0] * ktimes[k][1])
-        calls, avg_ms = ktimes[name]
-        gbs = nbytes[name] / (calls * avg_ms * 1e-3) / 1e9
-        return {"bound": "hbm", "kernel": f"{name} (all launches)", "achieved": gbs, "peak": 8000.0, "unit": "GB/s",
-                "frac": gbs / 8000.0, "traffic": None, "algorithmic_bytes_per_launch": nbytes[name] / calls,
-                "avg_launch_ms": avg_ms, "launches": calls,
-                "all": {k: {"calls": ktimes[k][0], "avg_ms": round(ktimes[k][1], 4),
-                            "GBps": round(nbytes[k] / (ktimes[k][0] * ktimes[k][1] * 1e-3) / 1e9, 1)} for k in names}}
+        return L.entry_point_roofline(ktimes)

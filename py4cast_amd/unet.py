@@ -31,7 +31,8 @@ from torch import nn
 
 from . import _lib as L
 from . import ops_gemm as G
-from .base import ModelABC, ModelType
+from .base import ModelType
+from .conv_model import ConvModelMI355X, cast_out, crop_channels, pad_head, pad_rows, pad_weight_in
 
 try:
     from dataclasses_json import dataclass_json
@@ -69,35 +70,6 @@ def _alias(t: torch.Tensor) -> torch.Tensor:
     return torch.empty(0, dtype=t.dtype, device=t.device).set_(t.untyped_storage(), t.storage_offset(), t.shape, t.stride())
 
 
-def _bn_stats(yc, stats, bn: nn.BatchNorm2d, training: bool):
-    """(mean, rstd, scale, shift) (4, C) fp32 of a BatchNorm2d over the rows of yc (N, C): from the producer's sums, one reduction pass,
-    or the running statistics (eval); updates the running statistics and num_batches_tracked in training"""
-    C = yc.shape[-1]
-    N = yc.numel() // C
-    dev = yc.device
-    st = torch.empty(4, C, dtype=torch.float32, device=dev)
-    g32, b32 = G._f32(bn.weight), G._f32(bn.bias)
-    if training:
-        if bn.momentum is None and bn.track_running_stats:
-            # the same rule as ops_gemm.batch_norm_act: torch's cumulative moving average is not served
-            raise L.P4CError("unet: BatchNorm2d(momentum=None) (cumulative average) is not served; give a momentum")
-        if stats is None:
-            nb = L.lib().p4c_inorm_blocks(N, C)
-            stats = torch.empty(nb, 2, C, dtype=torch.float32, device=dev)
-            L.call("p4c_inorm_reduce", L.ptr(yc), None, None, None, None, 1.0, L.ptr(stats), L.dtype_code(yc.dtype), 1, N, C, L.stream(dev))
-        track = bn.track_running_stats and bn.running_mean is not None
-        nbt = bn.num_batches_tracked if track else None
-        L.call("p4c_bnorm_finalize", L.ptr(stats), stats.shape[0], float(N), C, L.ptr(g32), L.ptr(b32), float(bn.eps),
-               float(0.1 if bn.momentum is None else bn.momentum), L.ptr(bn.running_mean if track else None),
-               L.ptr(bn.running_var if track else None), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), L.ptr(nbt), L.stream(dev))
-    else:
-        st[0] = bn.running_mean
-        st[1] = torch.rsqrt(bn.running_var.float() + bn.eps)
-        st[2] = st[1] * (1.0 if g32 is None else g32)
-        st[3] = (0.0 if b32 is None else b32) - st[0] * st[2]
-    return st
-
-
 class _EncTail(torch.autograd.Function):
     """(buf, pool) = the encoder block's last BN + ReLU written into buf[..., C:] (buf (B, H, W, 2C), its first half left for the
     transposed convolution) and the 2x2 max-pool of it; one native pass each way (csrc/unet.hip) + the batch norm's finalize / apply."""
@@ -107,7 +79,7 @@ class _EncTail(torch.autograd.Function):
         yc = y.contiguous()
         B, H, W, C = yc.shape
         dev = yc.device
-        st = _bn_stats(yc, stats, bn, training)
+        st = G.bn_statistics(yc, stats, bn, training)
         buf = torch.empty(B, H, W, 2 * C, dtype=yc.dtype, device=dev)
         pool = torch.empty(B, H // 2, W // 2, C, dtype=yc.dtype, device=dev)
         es = yc.element_size()
@@ -124,7 +96,6 @@ class _EncTail(torch.autograd.Function):
         yc, st, buf = ctx.saved_tensors
         B, H, W, C = yc.shape
         dev = yc.device
-        N = B * H * W
         dbuf = torch.zeros_like(buf) if dbuf is None else dbuf.contiguous()
         dpool = torch.zeros(B, H // 2, W // 2, C, dtype=yc.dtype, device=dev) if dpool is None else dpool.contiguous()
         nb = L.lib().p4c_unet_enc_tail_bwd_blocks(B, H, W, C)
@@ -133,17 +104,7 @@ class _EncTail(torch.autograd.Function):
         es = yc.element_size()
         L.call("p4c_unet_enc_tail_bwd", L.ptr(yc), L.ptr(buf[..., C:]), 2 * C, L.ptr(dbuf[..., C:]), 2 * C, L.ptr(dpool), L.ptr(st[0]), L.ptr(st[1]),
                L.ptr(dz), L.ptr(part), L.dtype_code(yc.dtype), B, H, W, C, L.stream(dev), alg_bytes=es * (yc.numel() * 4 + dpool.numel()))
-        co = torch.empty(2, C, dtype=torch.float32, device=dev)
-        dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
-        L.call("p4c_inorm_finalize_bwd", L.ptr(part), nb, 1, N, C, 0, None, None, L.ptr(co[0]), L.ptr(co[1]), L.ptr(dgb[0]), L.ptr(dgb[1]),
-               L.stream(dev))
-        if not ctx.training:
-            co.zero_()          # running statistics are constants
-        dy = torch.empty_like(yc)
-        L.call("p4c_inorm_apply", L.ptr(yc), None, L.ptr(dz), L.ptr(dz), L.ptr(st[2]), None, L.ptr(st[0]), L.ptr(st[1]), L.ptr(co[0]),
-               L.ptr(co[1]), 1.0, L.ptr(dy), None, L.dtype_code(yc.dtype), 1, N, C, L.stream(dev), alg_bytes=es * yc.numel() * 3)
-        dg = dgb[0] if ctx.has_affine else None
-        db = dgb[1] if ctx.has_affine else None
+        dy, dg, db = G.bn_tail_backward(yc, dz, part, nb, st, ctx.training, ctx.has_affine)
         return dy, None, dg, db, None, None
 
 
@@ -240,35 +201,20 @@ def upconv_into(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], buf
     return _UpConvInto.apply(x, w, b, buf, bool(grad_owned))
 
 
-class UNetMI355X(ModelABC, nn.Module):
+class UNetMI355X(ConvModelMI355X):
     """mfai's UNet (module docstring) on the native kernels of this package."""
 
     settings_kls = UNetSettings
-    onnx_supported = False
-    supported_num_spatial_dims = (2,)
-    num_spatial_dims = 2
-    features_last = True
     model_type = ModelType.CONVOLUTIONAL
-    register = True
-    is_native_hip = True
-    rollout_padded_output = False
 
     def __init__(self, in_channels: int, out_channels: int, input_shape: tuple = None, settings: UNetSettings = UNetSettings(),
                  *args, **kwargs):
-        super().__init__()
-        self.in_channels, self.out_channels, self.input_shape = in_channels, out_channels, input_shape
-        self.num_output_features = out_channels
-        self._settings = s = settings
-        act = s.activation_dtype or s.compute_dtype
-        if s.compute_dtype not in ("f32", "bf16") or act not in ("f32", "bf16"):
-            raise ValueError(f"UNetMI355X: compute_dtype / activation_dtype must be 'f32' or 'bf16', got {s.compute_dtype} / {act}")
-        if act != s.compute_dtype:
-            raise ValueError(f"UNetMI355X: compute_dtype {s.compute_dtype} with activation_dtype {act} is not served: the bf16 route keeps "
-                             "bf16 activations, the fp32 route fp32 ones")
+        super().__init__(in_channels, out_channels, input_shape, settings)
+        s = settings
+        self._resolve_dtypes(s)
         if s.compute_dtype == "bf16" and s.init_features % 8:
             raise ValueError(f"UNetMI355X: the bf16 route needs init_features a multiple of 8 (the GEMM's channel granularity), got "
                              f"{s.init_features}")
-        self.act_dtype = torch.bfloat16 if act == "bf16" else torch.float32
         f = s.init_features
         self.encoder1 = _block(in_channels, f, "enc1")
         self.pool1 = nn.MaxPool2d(kernel_size=2, stride=2)
@@ -292,35 +238,6 @@ class UNetMI355X(ModelABC, nn.Module):
                                    "p4c_gemm_upconv_dgrad", "p4c_gemm_upconv_wgrad", "p4c_inorm_apply")
         self.check_required_attributes()
 
-    roofline_from_entry_points = True    # bench.py: time every call of the native entry points above
-
-    @property
-    def settings(self):
-        return self._settings
-
-    def roofline(self, ktimes, B, H, W):
-        """bench.py: achieved HBM rate of the native entry point that takes the most time (the UNETR++ accounting: algorithmic bytes
-        stated by the wrappers next to each call, over HIP-event durations of every call)"""
-        from .unetrpp import UNetRPPMI355X
-
-        return UNetRPPMI355X.roofline(self, ktimes, B, H, W)
-
-    @property
-    def native(self) -> bool:
-        """the bf16 route (every convolution on csrc/gemm.hip); fp32 runs the convolutions on the library"""
-        return self.act_dtype == torch.bfloat16
-
-    @property
-    def cin_pad(self) -> int:
-        return (self.in_channels + 7) // 8 * 8
-
-    @property
-    def rollout_input_format(self):
-        """(dtype, channel count) of the rows the rollout's build_x should emit: bf16, zero-padded to the GEMM's 8-channel granularity"""
-        if not self.native:
-            return None
-        return torch.bfloat16, self.cin_pad
-
     def padding_for(self, H: int, W: int):
         """(top, bottom, left, right) zero padding that takes (H, W) to the next multiple of 16 (four 2x2 poolings), centred as mfai's
         AutoPaddingModel does (extra row / column at the end); all zeros when the grid already fits."""
@@ -332,16 +249,12 @@ class UNetMI355X(ModelABC, nn.Module):
         """features-last conv of x; returns (y, stats or None)"""
         if self.native:
             w = m.weight
-            if w.shape[1] % 8:          # encoder1 on zero-padded input rows: zero weight columns for the padding channels
-                w = F.pad(w, (0, 0, 0, 0, 0, x.shape[-1] - w.shape[1]))
-            b = m.bias
-            if w.shape[0] % 8:          # the head: zero output rows up to the 8-channel granularity, sliced off (a view)
-                pad = (-w.shape[0]) % 8
-                w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, pad))
-                b = None if b is None else F.pad(b, (0, pad))
+            if w.shape[1] % 8:          # encoder1 on zero-padded input rows
+                w = pad_weight_in(w, x.shape[-1])
+            w, b = pad_head(w, m.bias)  # (the head: 8-channel granularity, sliced off below)
             out = G.conv2d_nhwc(x, w, b, want_stats=want_stats)
             y, st = out if want_stats else (out, None)
-            return (y[..., : m.out_channels] if y.shape[-1] != m.out_channels else y), st
+            return crop_channels(y, m.out_channels), st
         xin = x[..., : m.in_channels] if x.shape[-1] > m.in_channels else x
         y = F.conv2d(xin.permute(0, 3, 1, 2), m.weight, m.bias, padding=m.padding)
         return y.permute(0, 2, 3, 1), None
@@ -383,8 +296,8 @@ class UNetMI355X(ModelABC, nn.Module):
         if x.shape[-1] < self.in_channels:
             raise L.P4CError(f"UNetMI355X: expected {self.in_channels} input channels, got {x.shape[-1]}")
         x = x.to(self.act_dtype)
-        if self.native and x.shape[-1] % 8:
-            x = F.pad(x, (0, self.cin_pad - x.shape[-1]))
+        if self.native:
+            x = pad_rows(x, self.cin_pad)
         x = x.contiguous()
         buf1, p = self._enc(self.encoder1, x)
         buf2, p = self._enc(self.encoder2, p)
@@ -396,4 +309,4 @@ class UNetMI355X(ModelABC, nn.Module):
         h = self._block(self.decoder2, self._up(self.upconv2, h, buf2))
         h = self._block(self.decoder1, self._up(self.upconv1, h, buf1))
         y, _ = self._conv(self.conv, h, False)
-        return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)
+        return cast_out(y, out_dtype)

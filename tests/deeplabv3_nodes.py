@@ -4,7 +4,7 @@ each node -- the helpers of tests/test_deeplabv3_nodes_gpu.py (the device) and t
 themselves, composed into the whole network against tests/deeplabv3_reference.py).
 
 Recorder: wraps the six entry points DeepLabV3MI355X._forward_native reaches (ops_gemm.conv2d_nhwc with its dilation / passthrough /
-bias, ops_gemm.batch_norm_act with its residual and multiplier, DeepLabV3MI355X._patch -- the strided convolutions as _PatchConv --,
+bias, ops_gemm.batch_norm_act with its residual and multiplier, DeepLabV3MI355X._patch -- the strided convolutions as ops_patch._PatchConv --,
 deeplabv3.stem_tail, deeplabv3.aspp_assemble, deeplabv3.upsample_bilinear_ac) and the ``backward`` of their autograd Functions.  Per call,
 in order: clones of the inputs, deep copies of the node's batch norm taken before and right after the call, the outputs, the gradient
 each output receives in the backward (cloned on entry) together with the gradients the node returns, and which recorded output each
@@ -197,7 +197,7 @@ def upsample_node(x, scale=8, dout=None):
 
 # ------------------------------------------------------------------------------------------------ the recorder
 
-# node kinds: "patch" (DeepLabV3MI355X._patch: _PatchConv), "conv" (conv2d_nhwc), "bn" (batch_norm_act), "stem" (stem_tail),
+# node kinds: "patch" (DeepLabV3MI355X._patch: ops_patch._PatchConv), "conv" (conv2d_nhwc), "bn" (batch_norm_act), "stem" (stem_tail),
 # "aspp" (aspp_assemble), "up" (upsample_bilinear_ac)
 KINDS = ("patch", "conv", "bn", "stem", "aspp", "up")
 
@@ -342,6 +342,7 @@ class Recorder:
     def __enter__(self):
         from py4cast_amd import deeplabv3 as D
         from py4cast_amd import ops_gemm as G
+        from py4cast_amd import ops_patch as P
 
         rec = self
         conv0, bn0, patch0 = G.conv2d_nhwc, G.batch_norm_act, D.DeepLabV3MI355X._patch
@@ -401,7 +402,7 @@ class Recorder:
         self._mp.setattr(D, "stem_tail", stem_tail)
         self._mp.setattr(D, "aspp_assemble", aspp_assemble)
         self._mp.setattr(D, "upsample_bilinear_ac", upsample_bilinear_ac)
-        for fn_cls in (G._Conv, G._BatchNormAct, D._PatchConv, D._StemTail, D._AsppAssemble, D._UpsampleAC):
+        for fn_cls in (G._Conv, G._BatchNormAct, P._PatchConv, D._StemTail, D._AsppAssemble, D._UpsampleAC):
             self._wrap_backward(fn_cls)
         return self
 

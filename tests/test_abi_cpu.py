@@ -157,3 +157,78 @@ def test_mask_tensor_matches_reference_loop():
         idx = torch.randperm(H * W)[: int((1 - Holder.mask_ratio) * H * W)]
         ref = orollout.mask_tensor(x, Holder.mask_ratio, idx)
         assert torch.equal(got, ref), (H, W)
+
+
+def test_entry_point_roofline_by_hand(monkeypatch):
+    """_lib.entry_point_roofline: the entry point with the largest calls x avg_ms among those whose calls all state their bytes;
+    achieved rate = its bytes over its time, against 8 TB/s.  Values below are worked out by hand from that formula."""
+    from py4cast_amd import _lib as L
+    from py4cast_amd.unet import UNetMI355X, UNetSettings
+
+    # (start event, end event, algorithmic bytes) per recorded call; k2 has a call without stated bytes and drops out
+    monkeypatch.setattr(L, "_TIMED", {"k1": [(None, None, 1e6), (None, None, 3e6)], "k2": [(None, None, 5e6), (None, None, None)],
+                                      "k3": [(None, None, 2e6)] * 4, "k5": []})
+    assert L.kernel_bytes() == {"k1": 4e6, "k3": 8e6}
+    ktimes = {"k1": (2, 0.5), "k2": (2, 10.0), "k3": (4, 0.1), "k4": (1, 99.0)}     # k4 is not a timed entry point
+    want = {"bound": "hbm", "kernel": "k1 (all launches)", "achieved": 4.0, "peak": 8000.0, "unit": "GB/s", "frac": 0.0005, "traffic": None,
+            "algorithmic_bytes_per_launch": 2e6, "avg_launch_ms": 0.5, "launches": 2,
+            "all": {"k1": {"calls": 2, "avg_ms": 0.5, "GBps": 4.0}, "k3": {"calls": 4, "avg_ms": 0.1, "GBps": 20.0}}}
+    got = L.entry_point_roofline(ktimes)
+    assert set(got) == set(want) and got["all"] == want["all"]
+    for k, v in want.items():
+        assert got[k] == (pytest.approx(v, rel=1e-12) if isinstance(v, float) else v), k
+    assert L.entry_point_roofline({"k2": (2, 10.0), "k4": (1, 99.0)}) is None and L.entry_point_roofline({}) is None
+    # the models' bench.py hook is that function
+    m = UNetMI355X(2, 1, (64, 64), UNetSettings())
+    assert m.roofline(ktimes, 2, 64, 64) == got and m.roofline({}, 2, 64, 64) is None and m.roofline_from_entry_points
+
+
+def _modules_after(code):
+    """the py4cast_amd modules a fresh interpreter holds after running `code`"""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prog = f"import sys; sys.path.insert(0, {root!r})\n{code}\nprint(' '.join(sorted(m for m in sys.modules if m.startswith('py4cast_amd.'))))"
+    out = subprocess.run([sys.executable, "-c", prog], cwd=root, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    return set(out.stdout.split())
+
+
+def test_conv_models_import_no_other_model():
+    """each of the three convolutional models stands on the ops layer and the shared base alone: importing one (and asking for its
+    roofline) pulls in neither of the others nor UNETR++"""
+    mods = _modules_after("import py4cast_amd.deeplabv3")
+    assert "py4cast_amd.deeplabv3" in mods and "py4cast_amd.ops_patch" in mods
+    assert not mods & {"py4cast_amd.segformer", "py4cast_amd.unet", "py4cast_amd.unetrpp"}
+    for mod, kls in (("unet", "UNetMI355X"), ("segformer", "SegformerMI355X"), ("deeplabv3", "DeepLabV3MI355X")):
+        mods = _modules_after(f"import py4cast_amd.{mod} as M\nm = M.{kls}(3, 2, (64, 64))\nassert m.roofline({{}}, 2, 64, 64) is None")
+        others = {"py4cast_amd.unet", "py4cast_amd.segformer", "py4cast_amd.deeplabv3", "py4cast_amd.unetrpp"} - {f"py4cast_amd.{mod}"}
+        assert f"py4cast_amd.{mod}" in mods and not mods & others, (mod, mods & others)
+
+
+@pytest.mark.parametrize("mod,kls,skls", [("unet", "UNetMI355X", "UNetSettings"), ("segformer", "SegformerMI355X", "SegformerSettings"),
+                                          ("deeplabv3", "DeepLabV3MI355X", "DeepLabV3Settings")])
+def test_conv_model_dtype_settings_name_the_concrete_class(mod, kls, skls):
+    import importlib
+
+    M = importlib.import_module(f"py4cast_amd.{mod}")
+    model, settings = getattr(M, kls), getattr(M, skls)
+    kw = {"encoder_weights": False} if mod == "deeplabv3" else {}
+    for bad in (dict(compute_dtype="f16"), dict(compute_dtype="bf16", activation_dtype="f64")):
+        with pytest.raises(ValueError, match=f"^{kls}: compute_dtype / activation_dtype must be 'f32' or 'bf16'"):
+            model(3, 2, (64, 64), settings(**bad, **kw))
+    for c, a in (("bf16", "f32"), ("f32", "bf16")):
+        with pytest.raises(ValueError, match=f"^{kls}: compute_dtype {c} with activation_dtype {a} is not served"):
+            model(3, 2, (64, 64), settings(compute_dtype=c, activation_dtype=a, **kw))
+
+    class Derived(model):       # (the plugin's registry aliases are subclasses: the message follows the class in use)
+        pass
+
+    with pytest.raises(ValueError, match="^Derived: compute_dtype"):
+        Derived(3, 2, (64, 64), settings(compute_dtype="f16", **kw))
+    for c in ("f32", "bf16"):
+        m = model(8, 8, (64, 64), settings(compute_dtype=c, **kw))
+        assert m.native == (c == "bf16") and m.cin_pad == 8 and m.rollout_input_format == ((torch.bfloat16, 8) if c == "bf16" else None)
+        assert m.settings.compute_dtype == c and m.features_last and m.is_native_hip and m.register and not m.rollout_padded_output
