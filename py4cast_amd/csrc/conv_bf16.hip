@@ -2274,9 +2274,6 @@ int conv_fwd_bf16(const void* in, int storage, int CI, const void* wp, int ks, c
                                   B, H, W, m_blocks, stream);
 }
 
-int wgrad_reduce(const float* partial, int nslots, int ks, int CI_pad, int ci_lo, int ci_hi, int CO, int CI, float* grad,
-                 hipStream_t stream);
-
 template <typename T>
 static int conv_wgrad_bf16_t(const T* in, int CI, int ks, const float* in_scale, const float* in_shift, int in_relu,
                              const T* dout, float* partial, int G, int B, int H, int W, int CO, int CIreal, float* grad,
@@ -2289,6 +2286,17 @@ static int conv_wgrad_bf16_t(const T* in, int CI, int ks, const float* in_scale,
     for (int off = 0; off < CI;) {
         const int chunk = (CI - off >= 64) ? 64 : 32;
         int rc;
+        if (std::is_same<T, __bf16>::value && off == 64 && !in_scale && !in_relu && !nb &&
+            conv_wgrad_thin_ok(P4C_BF16, CI, CIreal, 64, ks, B, H, W)) {
+            // the first convolution's real channels beyond 64 (one octet at 69 inputs): the streaming kernel of conv_thin.hip instead of
+            // a THIN chunk of the row-streaming kernel; compact slabs [9][8][64] behind the full chunk's G slots, their own reduction job
+            int nslots = 0;
+            float* thin = partial + (int64_t)G * 9 * CI * 64;
+            P4C_TRY(launch_conv3x3_wgrad_thin_bf16(in, CI, dout, thin, G, B, H, W, stream, &nslots));
+            if (!diag_skip(8)) P4C_TRY(wgrad_reduce(thin, nslots, 3, 8, 64, 72, CO, CIreal, grad, stream, 64));
+            off += chunk;
+            continue;
+        }
         if (std::is_same<T, __bf16>::value && conv_wgrad_rows_ok(P4C_BF16, CI, off, 64, ks, G, B, H, W)) {
             // maps at least 64 pixels wide: the row-streaming kernel (conv_wgrad_rows.hip), one launch per chunk -- the 96-channel
             // first convolution as a full chunk and a THIN one (its real channels beyond 64: one octet at 69 inputs); same partial

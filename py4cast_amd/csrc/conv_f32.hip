@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(256, 1)
 // (the 1x1 convolution has 64 (tap, ci) pairs only -- 64 workgroups walking 256 slots each took 41 us at 2 x 512 x 512).
 template <int QL>
 __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ partial, int nslots, int ntaps, int CI_pad, int ci_lo,
-                                                   int ci_hi, int CO, int CI, float* __restrict__ grad, int block) {
+                                                   int ci_hi, int CO, int CI, float* __restrict__ grad, int block, int ci_base) {
     constexpr int NS = 256 / QL, NCO = 4 * QL, NG = 64 / NCO;
     __shared__ float red[NS][NCO];
     const int nci = ci_hi - ci_lo;
@@ -353,7 +353,7 @@ __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ par
     const int tap = rest / nci, ci = ci_lo + (rest - tap * nci);
     const int q = threadIdx.x % QL, sl = threadIdx.x / QL;
     const int64_t stride = (int64_t)ntaps * CI_pad * 64;
-    const float* p = partial + ((int64_t)tap * CI_pad + ci) * 64 + cg * NCO + 4 * q;
+    const float* p = partial + ((int64_t)tap * CI_pad + (ci - ci_base)) * 64 + cg * NCO + 4 * q;
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
     for (int g = sl; g < nslots; g += NS) s += *reinterpret_cast<const f32x4*>(p + g * stride);
@@ -371,8 +371,8 @@ __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ par
 
 template <int QL>
 __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restrict__ partial, int nslots, int ntaps, int CI_pad,
-                                                           int ci_lo, int ci_hi, int CO, int CI, float* __restrict__ grad) {
-    wgrad_reduce_block<QL>(partial, nslots, ntaps, CI_pad, ci_lo, ci_hi, CO, CI, grad, blockIdx.x);
+                                                           int ci_lo, int ci_hi, int CO, int CI, float* __restrict__ grad, int ci_base) {
+    wgrad_reduce_block<QL>(partial, nslots, ntaps, CI_pad, ci_lo, ci_hi, CO, CI, grad, blockIdx.x, ci_base);
 }
 
 // every recorded job in one launch: block -> (job, block of that job) through the prefix table in the kernel arguments; each job
@@ -389,7 +389,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_batch_kernel(WgradBatchArgs 
     int j = 0;
     while (j + 1 < a.n && (int)blockIdx.x >= a.first[j + 1]) ++j;
     const WgradReduceJob& J = a.job[j];
-    wgrad_reduce_block<16>(J.partial, J.nslots, J.ntaps, J.CI_pad, J.ci_lo, J.ci_hi, J.CO, J.CI, J.grad, (int)blockIdx.x - a.first[j]);
+    wgrad_reduce_block<16>(J.partial, J.nslots, J.ntaps, J.CI_pad, J.ci_lo, J.ci_hi, J.CO, J.CI, J.grad, (int)blockIdx.x - a.first[j], J.ci_base);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -597,21 +597,21 @@ int wgrad_reduce_batch(const WgradCollect& c, hipStream_t stream) {
 }
 
 int wgrad_reduce(const float* partial, int nslots, int ks, int CI_pad, int ci_lo, int ci_hi, int CO, int CI, float* grad,
-                        hipStream_t stream) {
+                        hipStream_t stream, int ci_base) {
     if (ci_hi > CI) ci_hi = CI;
     if (ci_hi <= ci_lo) return P4C_OK;
     if (WgradCollect* c = g_wgrad_collect) {
         if (c->n == WGRAD_BATCH_MAX) return fail(P4C_ERR_INVALID, "wgrad_reduce: more than %d deferred reductions in one batch", WGRAD_BATCH_MAX);
-        c->job[c->n++] = WgradReduceJob{partial, grad, nslots, ks * ks, CI_pad, ci_lo, ci_hi, CO, CI};
+        c->job[c->n++] = WgradReduceJob{partial, grad, nslots, ks * ks, CI_pad, ci_lo, ci_hi, CO, CI, ci_base};
         return P4C_OK;
     }
     const int pairs = ks * ks * (ci_hi - ci_lo);
     if (pairs < 256 && nslots >= 64)
         hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(pairs * 4), dim3(256), 0, stream, partial, nslots, ks * ks, CI_pad, ci_lo,
-                           ci_hi, CO, CI, grad);
+                           ci_hi, CO, CI, grad, ci_base);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3(pairs), dim3(256), 0, stream, partial, nslots, ks * ks, CI_pad, ci_lo, ci_hi,
-                           CO, CI, grad);
+                           CO, CI, grad, ci_base);
     P4C_CHECK_LAUNCH("wgrad_reduce");
     return P4C_OK;
 }

@@ -155,7 +155,9 @@ void make_layout(const p4c_halfunet_desc& d, Layout& L) {
         L.statp = off; off += (int64_t)d.B * slots * 128;
     }
     // per-workgroup weight-gradient partials, one region per convolution (NCONV: the 1x1 output convolution): the reductions of a
-    // backward call run as ONE launch at its end (wgrad_reduce_batch), so every launch's partials live until then
+    // backward call run as ONE launch at its end (wgrad_reduce_batch), so every launch's partials live until then.  (The first
+    // convolution at 65..72 inputs: its full chunk fills at most g slots of [9][96][64]; the thin job's compact slabs -- conv_thin.hip,
+    // [9][8][64] each, at most 12 g of them -- lie behind those in the second half of the same region, which two-slot kernels use.)
     for (int i = 0; i <= NCONV; ++i) {
         const int lev = i < NCONV ? conv_level(i) : 0;
         int64_t tiles = (int64_t)d.B * conv_tiles_per_sample(L.Hk[lev], L.Wk[lev]);

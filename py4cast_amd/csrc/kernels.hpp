@@ -16,8 +16,10 @@ int conv_wgrad_f32(const float* in, int CI, int ks, const float* in_scale, const
 // floats of scratch needed by conv_wgrad_f32 (per-workgroup partials; 32-channel chunks use two slots per workgroup)
 static inline int64_t wgrad_partial_floats(int CI_pad, int ks, int G) { return (int64_t)2 * G * ks * ks * CI_pad * 64; }
 
+// ci_base: the input channel at row 0 of a slab's [tap][CI_pad][64] (0: the slab holds every channel of the gradient; 64 with CI_pad = 8:
+// the compact slabs of the first convolution's thin weight-gradient job, conv_thin.hip)
 int wgrad_reduce(const float* partial, int nslots, int ks, int CI_pad, int ci_lo, int ci_hi, int CO, int CI, float* grad,
-                 hipStream_t stream);
+                 hipStream_t stream, int ci_base = 0);
 // Deferred reductions: while a collector is installed on the calling thread (WgradCollect), wgrad_reduce() records its job instead
 // of launching, and wgrad_reduce_batch() reduces all of them in ONE launch -- every weight gradient of a network call (the HalfUNet
 // backward plan: 14 dependent ~8 us launches per call on the weight-gradient stream otherwise).  Each job must own its partial
@@ -26,6 +28,7 @@ struct WgradReduceJob {
     const float* partial;
     float* grad;
     int nslots, ntaps, CI_pad, ci_lo, ci_hi, CO, CI;
+    int ci_base = 0;   // channel at row 0 of the slab (rows ci - ci_base)
 };
 constexpr int WGRAD_BATCH_MAX = 24;
 struct WgradCollect {
@@ -169,6 +172,12 @@ int first_conv_tail_slots(int B, int H, int W);     // statistics slots ([2][64]
 int launch_first_conv_tail(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W, hipStream_t stream);
 // conv_rows.hip: plain 3x3 convolution 64 -> 64 whose input pixels are `pixel_channels` (> 64, multiple of 8) channels apart (the
 // first 64 channels of each are read)
+// the same convolution's weight gradient of the channels beyond 64 (rows 64..71): one streaming launch that leaves compact partials
+// [*nslots_out][9][8][64] for wgrad_reduce (CI_pad = 8, ci_base = 64).  G: workgroups of the full chunk (the slab count follows it)
+bool conv_wgrad_thin_ok(int storage, int in_cs, int ci_real, int dout_cs, int ks, int B, int H, int W);
+int conv_wgrad_thin_slots(int G, int B, int H, int W, int* nseg_out = nullptr);
+int launch_conv3x3_wgrad_thin_bf16(const void* x, int in_cs, const void* dout, float* partial, int G, int B, int H, int W, hipStream_t stream,
+                                   int* nslots_out);
 int launch_conv_bf16_rows_wide_pixels(const void* in, int pixel_channels, const void* wp, void* out, int B, int H, int W, hipStream_t stream);
 
 // norm_pool.hip
