@@ -147,6 +147,40 @@ CASES = [
 ]
 
 
+# Past the first pass of the kernels' window loop.  Each of a workgroup's 4 waves walks `for (w = gw*4 + wave; w < nwin; w += GW*4)`
+# with GW capped at ceil(3 CUs / heads): in CASES above GW <= 7 and no wave ever takes a second window.  Here nwin > 8 GW, so some
+# wave does >= 3 passes over the reused LDS images, the bias-gradient registers accumulate across passes and the partial-sum reduce
+# walks GW > 8 slices.  Sizes for 256 CUs (GW = 32 / 64 / 256 / 128 / 86 / 154; the last two are no multiples of 8: uneven slices);
+# on another CU count `_multipass` grows B until the precondition holds.
+MULTIPASS = [
+    # B, Hp, Wp, heads, d, ws, shift
+    (3, 84, 77, 24, 8, 7, 3),       # 396 windows, GW 32: three full passes and a ragged 12 (stage 4's heads)
+    (2, 112, 119, 12, 8, 7, 3),     # 544 windows, GW 64: two passes and a tail of 32 (some waves of a workgroup go on, some do not)
+    (2, 259, 259, 3, 8, 7, 3),      # 2 738 windows, GW 256: stage 1's own padded grid at 2 x 512 x 512
+    (3, 176, 184, 6, 16, 8, 4),     # 1 518 windows, GW 128: head_dim 16, window 8
+    (2, 133, 133, 9, 8, 7, 0),      # 722 windows, GW 86: no shift
+    (2, 175, 182, 5, 8, 7, 3),      # 1 300 windows, GW 154
+]
+
+
+def _attn_gw(B, Hp, Wp, heads, ws):
+    """workgroups per head of the attention launches, from the library's own workspace query (heads x GW slices of 4 096 floats)"""
+    from py4cast_amd import _lib as L
+
+    return int(L.lib().p4c_window_attn_bwd_workspace_bytes(B, Hp, Wp, heads, ws)) // (heads * 4096 * 4)
+
+
+def _multipass(case):
+    """the case with B grown until nwin > 8 GW (some wave does >= 3 passes); asserts that precondition and GW > 8"""
+    B, Hp, Wp, heads, d, ws, shift = case
+    per = (Hp // ws) * (Wp // ws)
+    while B * per <= 8 * _attn_gw(B, Hp, Wp, heads, ws) and B < 64:
+        B += 1
+    GW = _attn_gw(B, Hp, Wp, heads, ws)
+    assert B * per > 8 * GW and GW > 8, f"{case}: {B * per} windows, GW {GW}: no third pass"
+    return (B, Hp, Wp, heads, d, ws, shift)
+
+
 def _attn_inputs(B, Hp, Wp, heads, d, ws, seed, dtype):
     torch.manual_seed(seed)
     qkv = (torch.randn(B, Hp, Wp, 3 * heads * d) * 1.5).to(dtype)
@@ -156,31 +190,35 @@ def _attn_inputs(B, Hp, Wp, heads, d, ws, seed, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + MULTIPASS)
 def test_window_attention_forward(gpu_device, case, dtype):
     from py4cast_amd.ops_attention import window_attention
 
-    B, Hp, Wp, heads, d, ws, shift = case
+    # (the multi-pass cases: asserted to be that, and their float64 oracle runs on the device -- seconds on the host at these sizes)
+    rd = gpu_device if case in MULTIPASS else "cpu"
+    B, Hp, Wp, heads, d, ws, shift = _multipass(case) if case in MULTIPASS else case
     qkv, bias = _attn_inputs(B, Hp, Wp, heads, d, ws, 11, dtype)
     got = window_attention(qkv.to(gpu_device), bias.to(gpu_device), heads, ws, shift).float().cpu()
     no_bias = window_attention(qkv.to(gpu_device), None, heads, ws, shift).float().cpu()
+    qkv, bias = qkv.to(rd), bias.to(rd)
     if dtype == torch.float32:
         # fp32 activations run the fp32-exact kernels (round 3): held to the float64 oracle on the SAME operands
-        assert _rel(got, owa.window_attention(qkv.double(), bias.double(), heads, ws, shift)) < 2e-6
-        assert _rel(no_bias, owa.window_attention(qkv.double(), None, heads, ws, shift)) < 2e-6
+        assert _rel(got, owa.window_attention(qkv.double(), bias.double(), heads, ws, shift).cpu()) < 2e-6
+        assert _rel(no_bias, owa.window_attention(qkv.double(), None, heads, ws, shift).cpu()) < 2e-6
         return
-    ref = owa.window_attention(qkv.bfloat16().double(), bias.double(), heads, ws, shift)  # the operands the MFMAs see
+    ref = owa.window_attention(qkv.bfloat16().double(), bias.double(), heads, ws, shift).cpu()  # the operands the MFMAs see
     # P is rounded to bf16 before P @ V (2^-9 relative per element), bf16 outputs add one more rounding
     assert _rel(got, ref) < 6e-3
-    assert _rel(no_bias, owa.window_attention(qkv.bfloat16().double(), None, heads, ws, shift)) < 6e-3
+    assert _rel(no_bias, owa.window_attention(qkv.bfloat16().double(), None, heads, ws, shift).cpu()) < 6e-3
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + MULTIPASS)
 def test_window_attention_backward(gpu_device, case, dtype):
     from py4cast_amd.ops_attention import window_attention
 
-    B, Hp, Wp, heads, d, ws, shift = case
+    rd = gpu_device if case in MULTIPASS else "cpu"     # (as in the forward test)
+    B, Hp, Wp, heads, d, ws, shift = _multipass(case) if case in MULTIPASS else case
     qkv, bias = _attn_inputs(B, Hp, Wp, heads, d, ws, 12, dtype)
     torch.manual_seed(13)
     dout = torch.randn(B, Hp, Wp, heads * d).to(dtype)
@@ -189,22 +227,76 @@ def test_window_attention_backward(gpu_device, case, dtype):
     out = window_attention(q_g, b_g, heads, ws, shift)
     out.backward(dout.to(gpu_device))
     exact = dtype == torch.float32     # fp32 activations: the fp32-exact kernels, float64 oracle on the same operands
-    q_r = (qkv.double() if exact else qkv.bfloat16().double()).requires_grad_(True)
-    b_r = bias.double().requires_grad_(True)
-    owa.window_attention(q_r, b_r, heads, ws, shift).backward(dout.double() if exact else dout.bfloat16().double())
+    q_r = (qkv.to(rd).double() if exact else qkv.to(rd).bfloat16().double()).requires_grad_(True)
+    b_r = bias.to(rd).double().requires_grad_(True)
+    owa.window_attention(q_r, b_r, heads, ws, shift).backward(dout.to(rd).double() if exact else dout.to(rd).bfloat16().double())
+    dq_ref, db_ref = q_r.grad.cpu(), b_r.grad.cpu()
     # bf16-rounded P / dS operands: ~1e-2 on individual gradients
-    assert _rel(q_g.grad.float().cpu(), q_r.grad) < (5e-6 if exact else 1.5e-2)
-    assert _rel(b_g.grad.float().cpu(), b_r.grad) < (5e-6 if exact else 1.5e-2)
+    assert _rel(q_g.grad.float().cpu(), dq_ref) < (5e-6 if exact else 1.5e-2)
+    assert _rel(b_g.grad.float().cpu(), db_ref) < (5e-6 if exact else 1.5e-2)
     # each of dq, dk, dv on its own (a wrong block would hide in the norm of the others)
     C = heads * d
     for part in range(3):
         sl = slice(part * C, (part + 1) * C)
-        assert _rel(q_g.grad.float().cpu()[..., sl], q_r.grad[..., sl]) < (5e-6 if exact else 2e-2)
+        assert _rel(q_g.grad.float().cpu()[..., sl], dq_ref[..., sl]) < (5e-6 if exact else 2e-2)
     # deterministic bias gradient (fixed reduction order)
     q2 = qkv.to(gpu_device).requires_grad_(True)
     b2 = bias.to(gpu_device).requires_grad_(True)
     window_attention(q2, b2, heads, ws, shift).backward(dout.to(gpu_device))
     assert torch.equal(b2.grad, b_g.grad) and torch.equal(q2.grad, q_g.grad)
+
+
+# Per sample <= 4 x (the GW cap at 256 CUs) windows -- one call per sample is single-pass -- and with all of B more than 8 GW
+SPLIT = [
+    # B, Hp, Wp, heads, d, ws, shift, with bias
+    (3, 77, 77, 24, 8, 7, 3, True),       # 121 windows per sample, 363 in all, GW 32
+    (3, 105, 112, 12, 8, 7, 3, True),     # 240 / 720, GW 64
+    (3, 217, 224, 3, 8, 7, 3, False),     # 992 / 2 976, GW 256; no bias
+    (3, 176, 184, 6, 16, 8, 4, True),     # 506 / 1 518, GW 128
+    (3, 119, 126, 9, 8, 7, 0, True),      # 306 / 918, GW 86; no shift
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("case", SPLIT)
+def test_window_attention_multipass_equals_single_pass(gpu_device, case, dtype):
+    """One call over B samples (nwin > 8 GW: up to three passes per wave) against one call per sample (nwin <= 4 GW: every wave takes
+    at most one window).  A window's arithmetic does not depend on the pass it runs in, so `out` and `dqkv` must agree BIT FOR BIT: a
+    difference is a hazard between passes (an LDS image read before the next pass overwrote it, a stale statistic).  The bias gradient
+    sums the windows in another order by construction: it is held to float64 at the bars of test_window_attention_backward, and so is
+    the backward without a bias."""
+    from py4cast_amd.ops_attention import window_attention
+
+    *geo, with_bias = case
+    B, Hp, Wp, heads, d, ws, shift = _multipass(tuple(geo))
+    per = (Hp // ws) * (Wp // ws)
+    assert per <= 4 * _attn_gw(1, Hp, Wp, heads, ws), f"{case}: a one-sample call is not single-pass on this device"
+    qkv, bias = _attn_inputs(B, Hp, Wp, heads, d, ws, 14, dtype)
+    qkv, bias = qkv.to(gpu_device), (bias.to(gpu_device) if with_bias else None)
+    dout = torch.randn(B, Hp, Wp, heads * d, device=gpu_device, generator=torch.Generator(device=gpu_device).manual_seed(15)).to(dtype)
+
+    def run(q, do):
+        ql = q.clone().requires_grad_(True)
+        bl = None if bias is None else bias.clone().requires_grad_(True)
+        out = window_attention(ql, bl, heads, ws, shift)
+        out.backward(do)
+        return out.detach(), ql.grad, None if bl is None else bl.grad
+
+    out, dqkv, dbias = run(qkv, dout)
+    parts = [run(qkv[b:b + 1], dout[b:b + 1]) for b in range(B)]
+    for b, (o, dq, _) in enumerate(parts):
+        assert torch.equal(out[b:b + 1], o), f"out, sample {b}: {int((out[b:b + 1] != o).sum())} elements differ from the single-pass call"
+        assert torch.equal(dqkv[b:b + 1], dq), f"dqkv, sample {b}: {int((dqkv[b:b + 1] != dq).sum())} elements differ from the single-pass call"
+    exact = dtype == torch.float32
+    q_r = qkv.double().requires_grad_(True)          # (bf16: already the rounded operands)
+    b_r = None if bias is None else bias.double().requires_grad_(True)
+    ref = owa.window_attention(q_r, b_r, heads, ws, shift)
+    ref.backward(dout.double())
+    assert _rel(out, ref.detach()) < (2e-6 if exact else 6e-3)
+    assert _rel(dqkv, q_r.grad) < (5e-6 if exact else 1.5e-2)
+    if with_bias:
+        assert _rel(dbias, b_r.grad) < (5e-6 if exact else 1.5e-2)
+        assert _rel(sum(p[2].double() for p in parts), b_r.grad) < (5e-6 if exact else 1.5e-2)
 
 
 def test_window_attention_masks_are_exact(gpu_device):
