@@ -200,6 +200,19 @@ int p4c_acc_sums(const float* pred, int64_t pred_bs, int64_t pred_ts, const floa
                  const void* mask, int mask_mode, const float* climate_means, float* out, void* workspace, int B, int T,
                  int64_t N, int F, p4c_stream_t stream);
 
+/* Power spectral density of MetricPSDK / MetricPSDVar (metrics.py:13-352) for prediction and target at ONE time step:
+ * out (2,F,rmax) fp32, prediction first.  pred / target / mask point at that time step: (B,H,W,F) views with batch strides
+ * (elements) and a dense inner (H,W,F) block; mask per p4c_mask_mode (FROM_NAN reads the raw target, masks both tensors with
+ * !isnan(target) and takes the NaN as 0).  The reference's radial binning reads only row 0 of the 2-D DCT and its last
+ * coefficient ("Power spectrum"), so one streaming pass forms two weighted sums over H per (b,w,f) and a small finish
+ * does the rest in double.  col_weights: (H) floats cos(pi (2h+1)(H-1) / (2H)); bin_count: (rmax) int32 pixels per radial bin
+ * (an empty bin gives NaN, the reference's 0/0); rmax = Rmax of radial_bin_dct for (H,W).  Limits: F <= 256, 1 <= rmax,
+ * 2*rmax < W, W <= 4095.  workspace: p4c_psd_workspace_bytes(B,H,W,F), 16-byte aligned. */
+size_t p4c_psd_workspace_bytes(int B, int H, int W, int F);
+int p4c_psd(const float* pred, int64_t pred_bs, const float* target, int64_t tgt_bs, const void* mask, int64_t mask_bs,
+            int mask_mode, const float* col_weights, const int32_t* bin_count, int rmax, float* out, void* workspace, int B,
+            int H, int W, int F, p4c_stream_t stream);
+
 /* NaN-aware moments for the dataset statistics (compute_dataset_stats.py:11-127): out (5,B,F) = per (sample, feature)
  * sum, sum of squares, count of non-NaN values, min, max over `rows` rows of F features (sample b starts at
  * x + b*batch_stride).  With x_next != NULL the value is x_next[i] - x[i] (time-step differences: pass the views

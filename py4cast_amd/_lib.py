@@ -41,6 +41,7 @@ SIGNATURES = {
     "p4c_weighted_loss_bwd": [P, P, L, L, P, L, L, P, I, P, P, F, P, I, P, L, L, I, I, L, I, P],
     "p4c_scaled_loss_fwd": [P, L, L, P, L, L, P, I, P, P, F, P, I, P, P, I, I, L, I, P],
     "p4c_acc_sums": [P, L, L, P, L, L, P, I, P, P, P, I, I, L, I, P],
+    "p4c_psd": [P, L, P, L, P, L, I, P, P, I, P, P, I, I, I, I, P],
     "p4c_unnormalize": [P, P, P, P, L, I, P],
     "p4c_unnormalize_planes": [P, P, P, P, L, L, I, P],
     "p4c_adamw_step": [P, P, P, P, L, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, L, P],
@@ -65,6 +66,7 @@ OTHER = {
     "p4c_last_error": ([], c_char_p),
     "p4c_num_cus": ([], c_int),
     "p4c_loss_workspace_bytes": ([I, I, L, I], c_size_t),
+    "p4c_psd_workspace_bytes": ([I, I, I, I], c_size_t),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

@@ -629,9 +629,10 @@ class AutoRegressiveLightning(_Base):
         return OrderedDict((k.replace("model.", ""), v) for k, v in weights.items())
 
     # ------------------------------------------------------------------ observers (plots / metrics of the reference)
-    # The plotters and the PSD metrics are py4cast's own host-side code (matplotlib, out of the hot-path scope): when the
-    # `py4cast` package is importable they are attached and notified exactly where the reference notifies them
-    # (lightning.py:868-1065); when it is not, the hooks are no-ops.  They receive the lazy mask / target of get_mask_on_nan.
+    # The plotters are py4cast's own host-side code (matplotlib, out of the hot-path scope): when the `py4cast` package is
+    # importable they are attached and notified exactly where the reference notifies them (lightning.py:868-1065); when it is
+    # not, the hooks are no-ops.  They receive the lazy mask / target of get_mask_on_nan.  The three metrics are native
+    # (metrics.py) and always attached.
     @staticmethod
     def _reference_observers():
         try:
@@ -652,16 +653,13 @@ class AutoRegressiveLightning(_Base):
         if not self.logging_enabled:
             return
         self.save_path = Path(self.trainer.logger.log_dir)
-        from .metrics import MetricACC   # device-side sums (p4c_acc_sums)
+        from .metrics import MetricACC, MetricPSDK, MetricPSDVar   # device-side sums (p4c_acc_sums, p4c_psd)
 
         self.acc_metric = MetricACC(self.dataset_info)
-        self.list_metrics = [self.acc_metric]
-        _, ref_metrics = self._reference_observers()
-        if ref_metrics is not None:
-            max_pred_step = self.num_pred_steps_val_test - 1
-            self.rmse_psd_plot_metric = ref_metrics.MetricPSDVar(pred_step=max_pred_step)
-            self.psd_plot_metric = ref_metrics.MetricPSDK(self.save_path, pred_step=max_pred_step)
-            self.list_metrics += [self.psd_plot_metric, self.rmse_psd_plot_metric]
+        max_pred_step = self.num_pred_steps_val_test - 1
+        self.rmse_psd_plot_metric = MetricPSDVar(pred_step=max_pred_step)
+        self.psd_plot_metric = MetricPSDK(self.save_path, pred_step=max_pred_step)
+        self.list_metrics = [self.acc_metric, self.psd_plot_metric, self.rmse_psd_plot_metric]
 
     def on_validation_start(self):
         """lightning.py:864-886."""

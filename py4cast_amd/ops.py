@@ -6,8 +6,10 @@ HIP stream through the C ABI and wire the matching backward entry point.  They a
 outputs with the PyTorch caching allocator (the library owns no memory).
 """
 
+import functools
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -392,6 +394,72 @@ def acc_sums(pred: torch.Tensor, target: torch.Tensor, spec: "MaskSpec", climate
     ws = torch.empty(3 * L.lib().p4c_loss_workspace_bytes(B, T, N, F) // 4, dtype=torch.float32, device=p.device)
     L.call("p4c_acc_sums", L.ptr(p), T * N * F, N * F, L.ptr(g), T * N * F, N * F, L.ptr(spec.tensor), spec.mode,
            L.ptr(climate_means.to(p).contiguous()), L.ptr(out), L.ptr(ws), B, T, N, F, L.stream(p.device))
+    return out
+
+
+@functools.lru_cache(maxsize=32)
+def _psd_bins(H: int, W: int):
+    """(Rmax, pixels per radial bin) of ``radial_bin_dct`` (metrics.py:300-318) for an (H, W) spectrum, as the reference has it:
+    the centre (H//2, W//2) is used as (x0, y0) -- swapped for non-square grids -- and Rmax = min(W-1, H-1, r.max()) // 2."""
+    y, x = np.indices((H, W))
+    r = np.sqrt((x - H // 2) ** 2 + (y - W // 2) ** 2).astype(int)
+    rmax = min(W - 1, H - 1, int(r.max())) // 2
+    counts = np.bincount(r.ravel()[r.ravel() < rmax], minlength=rmax)[:rmax].astype(np.int32)
+    counts.setflags(write=False)
+    return rmax, counts
+
+
+def psd_rmax(H: int, W: int) -> int:
+    """Number of wave-number bins of the reference's power spectrum on an (H, W) grid."""
+    return _psd_bins(int(H), int(W))[0]
+
+
+def psd_bin_counts(H: int, W: int) -> np.ndarray:
+    """(Rmax,) int32: pixels per radial bin; a bin with none is NaN in the spectrum (the reference's 0/0)."""
+    return _psd_bins(int(H), int(W))[1]
+
+
+@functools.lru_cache(maxsize=32)
+def _psd_tables(H: int, W: int, device):
+    h = np.arange(H, dtype=np.float64)
+    col = np.cos(np.pi * (2 * h + 1) * (H - 1) / (2 * H)).astype(np.float32)   # row H-1 of the DCT-II basis along H
+    return torch.from_numpy(col).to(device), torch.from_numpy(psd_bin_counts(H, W).copy()).to(device)
+
+
+def psd(pred: torch.Tensor, target: torch.Tensor, spec: "MaskSpec", pred_step: int, grid=None) -> torch.Tensor:
+    """Radially binned power spectral density of prediction and target at time step ``pred_step`` as the reference computes it
+    (``power_spectral_density`` of metrics.py:324-352 on ``tensor * mask``, per feature) -> (2, F, Rmax), prediction first.
+    (B,T,H,W,F) tensors, or (B,T,N,F) with ``grid=(H, W)``; one pass of ``p4c_psd`` over both tensors, nothing goes to the host."""
+    L.require_cuda(pred, target)
+    if pred.shape != target.shape:
+        raise L.P4CError(f"psd: prediction {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+    if pred.dim() == 5 and grid is None:
+        H, W = int(pred.shape[2]), int(pred.shape[3])
+    elif pred.dim() == 4 and grid is not None:
+        H, W = int(grid[0]), int(grid[1])
+        if H * W != pred.shape[2]:
+            raise L.P4CError(f"psd: grid {H}x{W} does not match {pred.shape[2]} grid points")
+    else:
+        raise L.P4CError("psd: needs (B,T,H,W,F) tensors, or (B,T,N,F) tensors with grid=(H, W)")
+    B, T, F = pred.shape[0], pred.shape[1], pred.shape[-1]
+    if not 0 <= pred_step < T:
+        raise L.P4CError(f"psd: pred_step {pred_step} outside the {T} time steps")
+    rmax = psd_rmax(H, W)
+    if rmax < 1:
+        raise L.P4CError(f"psd: a {H}x{W} grid has no wave-number bin (Rmax = 0)")
+    p, (pbs, _) = _rows(pred.detach().float(), 2)
+    g, (gbs, _) = _rows(target.detach().float(), 2)
+    m, mbs = None, 0
+    if spec.tensor is not None:
+        m = spec.tensor
+        if m.shape != pred.shape:
+            m = m.expand(pred.shape).contiguous()
+        m, mbs = m[:, pred_step], T * H * W * F
+    col, counts = _psd_tables(H, W, p.device)
+    out = torch.empty(2, F, rmax, dtype=torch.float32, device=p.device)
+    ws = torch.empty(L.lib().p4c_psd_workspace_bytes(B, H, W, F) // 4, dtype=torch.float32, device=p.device)
+    L.call("p4c_psd", L.ptr(p[:, pred_step]), pbs, L.ptr(g[:, pred_step]), gbs, L.ptr(m), mbs, spec.mode, L.ptr(col), L.ptr(counts),
+           rmax, L.ptr(out), L.ptr(ws), B, H, W, F, L.stream(p.device), alg_bytes=2 * 4 * B * H * W * F)
     return out
 
 

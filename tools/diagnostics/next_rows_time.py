@@ -16,4 +16,6 @@ raw = torch.randn(F, B, T + 1, H, W, device=dev)
 nb = x.numel() * 4
 us = t(lambda: ops.unnormalize(x, std, mean, out=x)); print("unnormalize (B,T,512,512,60): %.1f us, %.2f TB/s" % (us, 2 * nb / us / 1e6))
 us = t(lambda: ops.acc_sums(x, y, ops.MaskSpec(0), mean)); print("acc_sums: %.1f us, %.2f TB/s" % (us, 2 * nb / us / 1e6))
+# one time step of prediction and target (2 x 512^2 x 60 each): the bytes p4c_psd reads; against 8 TB/s
+us = t(lambda: ops.psd(x, y, ops.MaskSpec(0), T - 1)); print("psd (one step of B,512,512,60 x 2 tensors): %.1f us, %.2f TB/s, %.1f%% of 8 TB/s" % (us, 2 * nb / T / us / 1e6, 100 * 2 * nb / T / us / 1e6 / 8))
 us = t(lambda: ops.pack_standardize(raw, mean, std)); print("pack_standardize (60 planes x B x 4 steps): %.1f us, %.2f TB/s" % (us, 2 * raw.numel() * 4 / us / 1e6))
