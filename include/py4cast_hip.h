@@ -243,6 +243,19 @@ int p4c_unnormalize_planes(const float* x, const float* std, const float* mean, 
 int p4c_pack_standardize(const float* raw, int64_t plane_stride, const float* mean, const float* std, float* out,
                          int64_t rows, int F, p4c_stream_t stream);
 
+/* The whole forcing batch of Sample.load (datasets/base.py:455-527) in one pass: out (B,T,HW,Fe+5) features-last =
+ * the Fe external forcing planes raw[f*plane_stride + r] standardised and packed exactly as p4c_pack_standardize does
+ * (bit-equal), then the five channels of generate_forcings (base.py:233-274, forcingutils.py): four date values and the
+ * top-of-atmosphere irradiance max(0, 1366 * (sin_lat*sin_dec + cos_lat*cos_dec*cos(15 deg * (hour + lon_hours - 12)))).
+ * r = (b*T + t)*HW + pixel.  raw / mean / std may be NULL when Fe == 0.
+ * sin_lat, cos_lat, lon_hours: (HW) planes, sine and cosine of the latitude and the longitude in hours (degrees / 15).
+ * time_table: (B,T,8) floats per (b, t): the four date values already rescaled to [0, 1] in output order, sin and cos of
+ *   the solar declination, the UTC hour of day, one pad (py4cast_amd/forcings.py builds both tables).
+ * Limit: Fe + 5 <= 144 (the LDS tile of p4c_pack_standardize), refused before any launch. */
+int p4c_build_forcing(const float* raw, int64_t plane_stride, const float* mean, const float* std, const float* sin_lat,
+                      const float* cos_lat, const float* lon_hours, const float* time_table, float* out, int B, int T,
+                      int64_t HW, int Fe, p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

@@ -47,6 +47,7 @@ SIGNATURES = {
     "p4c_adamw_step": [P, P, P, P, L, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, L, P],
     "p4c_nan_moments": [P, P, L, P, P, I, L, I, P],
     "p4c_pack_standardize": [P, L, P, P, P, L, I, P],
+    "p4c_build_forcing": [P, L, P, P, P, P, P, P, P, I, I, L, I, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],

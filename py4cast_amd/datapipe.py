@@ -6,11 +6,12 @@ device as they come from disk (one plane per parameter) and ONE kernel standardi
 features-last batch layout the rollout consumes.
 """
 
-from typing import Dict, List, Sequence
+from datetime import datetime, timedelta
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import ops
+from . import forcings, ops
 from .base import ItemBatch
 from .namedtensor import NamedTensor
 
@@ -37,3 +38,46 @@ def load_batch(raw_io: torch.Tensor, io_names: List[str], forcing: NamedTensor, 
     inputs = NamedTensor(t[:, :num_input_steps], DIMS.copy(), list(io_names))
     outputs = NamedTensor(t[:, num_input_steps:], DIMS.copy(), list(io_names))
     return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
+
+
+def build_forcing(raw: Optional[torch.Tensor], ext_names: Sequence[str], stats, dates: Sequence[datetime],
+                  timedeltas: Sequence[timedelta], lat, lon, standardize: bool = True, device=None) -> NamedTensor:
+    """Device-side forcing of ``Sample.load`` (base.py:455-527): the ``kind == "input"`` parameters standardised, then the five
+    channels of ``generate_forcings`` (base.py:233-274) -- date values and top-of-atmosphere irradiance -- computed in the
+    kernel from B run dates, T lead times and the grid's coordinates.
+
+    raw: (Ff_ext, B, T, H, W) device tensor of un-normalised planes, or None (the dummy dataset: the five channels only);
+    lat, lon: (H, W) in degrees.  -> NamedTensor (B, T, H, W, Ff_ext + 5) fp32, features ``ext_names + FORCING_NAMES`` (the
+    concatenation order of base.py:509-515): what ``load_batch`` and ``diskio.load_titan_batch`` take as ``forcing``."""
+    ext_names = list(ext_names)
+    B, T = len(dates), len(timedeltas)
+    lat_shape, lon_shape = tuple(getattr(lat, "shape", ())), tuple(getattr(lon, "shape", ()))
+    if len(lat_shape) != 2 or lon_shape != lat_shape:
+        raise ValueError(f"build_forcing: lat {lat_shape} and lon {lon_shape} must be the same (H, W)")
+    H, W = lat_shape
+    if B == 0 or T == 0:
+        raise ValueError("build_forcing: needs at least one date and one lead time")
+    if raw is None:
+        if ext_names:
+            raise ValueError(f"build_forcing: {len(ext_names)} external feature names and no raw planes")
+    else:
+        if raw.dim() != 5 or raw.shape[0] != len(ext_names):
+            raise ValueError(f"build_forcing: raw {tuple(raw.shape)} is not (Ff_ext, B, T, H, W) with Ff_ext = {len(ext_names)} names")
+        if raw.shape[1] != B or raw.shape[2] != T:
+            raise ValueError(f"build_forcing: {B} dates x {T} lead times for raw planes of batch {raw.shape[1]} x {raw.shape[2]} steps")
+        if tuple(raw.shape[3:]) != (H, W):
+            raise ValueError(f"build_forcing: lat / lon {lat_shape} do not match the planes' grid {tuple(raw.shape[3:])}")
+        if device is None:
+            device = raw.device
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    mean = std = None
+    if raw is not None and raw.shape[0] > 0:
+        if standardize:
+            mean, std = stats.to_list("mean", ext_names).to(device), stats.to_list("std", ext_names).to(device)
+        else:
+            mean, std = torch.zeros(len(ext_names), device=device), torch.ones(len(ext_names), device=device)
+    table = forcings.time_table(dates, timedeltas).to(device)
+    planes = forcings.grid_tables(lat, lon, device)
+    out = ops.build_forcing(raw, mean, std, table, planes, B, T, H, W)
+    return NamedTensor(out, DIMS.copy(), ext_names + forcings.FORCING_NAMES)

@@ -473,3 +473,33 @@ def pack_standardize(raw: torch.Tensor, mean: torch.Tensor, std: torch.Tensor) -
     L.call("p4c_pack_standardize", L.ptr(raw), rows, L.ptr(mean.to(raw).contiguous()), L.ptr(std.to(raw).contiguous()),
            L.ptr(out), rows, F, L.stream(raw.device))
     return out
+
+
+def build_forcing(raw, mean, std, table: torch.Tensor, grid_planes: torch.Tensor, B: int, T: int, H: int, W: int) -> torch.Tensor:
+    """The forcing batch of ``Sample.load`` (base.py:455-527) in one pass of ``p4c_build_forcing`` -> (B, T, H, W, Fe + 5) fp32:
+    ``raw`` (Fe, B, T, H, W) external forcing planes (or None: Fe = 0) standardised and packed as ``pack_standardize`` does,
+    then the reference's five generated channels (``forcings.FORCING_NAMES``).  ``table``: (B, T, 8) of ``forcings.time_table``,
+    ``grid_planes``: (3, H, W) of ``forcings.grid_tables``, both on the device."""
+    L.require_cuda(raw, table, grid_planes)
+    B, T, H, W = int(B), int(T), int(H), int(W)
+    if tuple(table.shape) != (B, T, 8) or tuple(grid_planes.shape) != (3, H, W):
+        raise L.P4CError(f"build_forcing: table {tuple(table.shape)} / grid planes {tuple(grid_planes.shape)} do not match "
+                         f"(B, T, 8) = {(B, T, 8)} and (3, H, W) = {(3, H, W)}")
+    dev = table.device
+    table = table.contiguous().float()
+    planes = grid_planes.to(dev).contiguous().float()
+    Fe, rows = 0, B * T * H * W
+    if raw is not None:
+        if raw.dim() != 5 or tuple(raw.shape[1:]) != (B, T, H, W):
+            raise L.P4CError(f"build_forcing: raw {tuple(raw.shape)} is not (Fe, B, T, H, W) = (Fe, {B}, {T}, {H}, {W})")
+        raw = raw.to(dev).contiguous().float()
+        Fe = raw.shape[0]
+        if mean.numel() != Fe or std.numel() != Fe:
+            raise L.P4CError(f"build_forcing: {Fe} external features, {mean.numel()} means, {std.numel()} standard deviations")
+        mean, std = mean.to(raw).contiguous(), std.to(raw).contiguous()
+    if Fe == 0:
+        raw = mean = std = None
+    out = torch.empty(B, T, H, W, Fe + 5, dtype=torch.float32, device=dev)
+    L.call("p4c_build_forcing", L.ptr(raw), rows, L.ptr(mean), L.ptr(std), L.ptr(planes[0]), L.ptr(planes[1]), L.ptr(planes[2]),
+           L.ptr(table), L.ptr(out), B, T, H * W, Fe, L.stream(dev), alg_bytes=4 * rows * (2 * Fe + 5))
+    return out
