@@ -200,6 +200,25 @@ int p4c_acc_sums(const float* pred, int64_t pred_bs, int64_t pred_ts, const floa
                  const void* mask, int mask_mode, const float* climate_means, float* out, void* workspace, int B, int T,
                  int64_t N, int F, p4c_stream_t stream);
 
+/* Evaluation sums of a validation / test step in ONE pass over prediction and target: what the score-card and spatial-error
+ * observers (plots.py:488-651) otherwise take from two p4c_scaled_loss_fwd calls, p4c_weighted_loss_map and
+ * p4c_mask_all_zero_count.  Inputs as for the losses above (mask per p4c_mask_mode, explicit masks dense (B,T,N,F)).
+ *   scores (2,B,T,F): [0] what p4c_scaled_loss_fwd gives for P4C_LOSS_L1, [1] for P4C_LOSS_MSE (sqrt of the mean, times std[f]);
+ *                     the denominator is num_interior - *masked_count with the count formed by this call.
+ *   masked_count (1): grid points (interior or not) whose mask is 0 for every (b,t,f); equals p4c_mask_all_zero_count.
+ *   map_acc (T,N) or NULL: map_acc[t,n] (+)= sum_b sum_f weights[f] * l(pred*m, tgt*m), l per map_kind (P4C_LOSS_MSE, P4C_LOSS_L1;
+ *                     P4C_EVAL_MAP_NONE: no map), b ascending -- the batch sum of p4c_weighted_loss_map.  accumulate = 0
+ *                     overwrites, 1 adds to what is there.
+ * No float atomics, fixed summation order: two calls on the same inputs give the same bits.  16-byte path: F <= 64,
+ * N*F % 4 == 0, 16-byte aligned bases and strides; anything else with F <= 256 takes a scalar path.
+ * workspace: p4c_eval_sums_workspace_bytes(B,T,N,F). */
+#define P4C_EVAL_MAP_NONE (-1)
+size_t p4c_eval_sums_workspace_bytes(int B, int T, int64_t N, int F);
+int p4c_eval_sums(const float* pred, int64_t pred_bs, int64_t pred_ts, const float* target, int64_t tgt_bs, int64_t tgt_ts,
+                  const void* mask, int mask_mode, const float* interior_mask, float num_interior, const float* std,
+                  const float* weights, int map_kind, float* map_acc, int accumulate, float* scores, int32_t* masked_count,
+                  void* workspace, int B, int T, int64_t N, int F, p4c_stream_t stream);
+
 /* Power spectral density of MetricPSDK / MetricPSDVar (metrics.py:13-352) for prediction and target at ONE time step:
  * out (2,F,rmax) fp32, prediction first.  pred / target / mask point at that time step: (B,H,W,F) views with batch strides
  * (elements) and a dense inner (H,W,F) block; mask per p4c_mask_mode (FROM_NAN reads the raw target, masks both tensors with

@@ -20,6 +20,7 @@ F32, BF16 = 0, 1
 PROF_CONV3X3_C64, PROF_WGRAD3X3_C64, PROF_CONV3X3_C64_BWD = 1, 2, 4
 LOSS_MSE, LOSS_L1 = 0, 1
 MASK_NONE, MASK_FROM_NAN, MASK_F32, MASK_U8 = 0, 1, 2, 3
+EVAL_MAP_NONE = -1
 
 P = c_void_p
 I = c_int
@@ -41,6 +42,9 @@ SIGNATURES = {
     "p4c_weighted_loss_bwd": [P, P, L, L, P, L, L, P, I, P, P, F, P, I, P, L, L, I, I, L, I, P],
     "p4c_scaled_loss_fwd": [P, L, L, P, L, L, P, I, P, P, F, P, I, P, P, I, I, L, I, P],
     "p4c_acc_sums": [P, L, L, P, L, L, P, I, P, P, P, I, I, L, I, P],
+    # pred, bs, ts, target, bs, ts, mask, mode, interior, num_interior, std, weights, map_kind, map_acc, accumulate, scores, count, ws,
+    # B, T, N, F, stream
+    "p4c_eval_sums": [P, L, L, P, L, L, P, I, P, F, P, P, I, P, I, P, P, P, I, I, L, I, P],
     "p4c_psd": [P, L, P, L, P, L, I, P, P, I, P, P, I, I, I, I, P],
     "p4c_unnormalize": [P, P, P, P, L, I, P],
     "p4c_unnormalize_planes": [P, P, P, P, L, L, I, P],
@@ -68,6 +72,7 @@ OTHER = {
     "p4c_num_cus": ([], c_int),
     "p4c_loss_workspace_bytes": ([I, I, L, I], c_size_t),
     "p4c_psd_workspace_bytes": ([I, I, I, I], c_size_t),
+    "p4c_eval_sums_workspace_bytes": ([I, I, L, I], c_size_t),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

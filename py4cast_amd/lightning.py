@@ -629,10 +629,10 @@ class AutoRegressiveLightning(_Base):
         return OrderedDict((k.replace("model.", ""), v) for k, v in weights.items())
 
     # ------------------------------------------------------------------ observers (plots / metrics of the reference)
-    # The plotters are py4cast's own host-side code (matplotlib, out of the hot-path scope): when the `py4cast` package is
-    # importable they are attached and notified exactly where the reference notifies them (lightning.py:868-1065); when it is
-    # not, the hooks are no-ops.  They receive the lazy mask / target of get_mask_on_nan.  The three metrics are native
-    # (metrics.py) and always attached.
+    # The score-card and spatial-error plotters and the three metrics are native (observers.py, metrics.py) and always attached;
+    # one ops.eval_sums pass per step feeds both plotters.  PredictionTimestepPlot and PredictionEpochPlot need cartopy projections:
+    # they are py4cast's own host-side code and are attached when the `py4cast` package is importable, where the reference has them
+    # (lightning.py:868-1065).  They receive the lazy mask / target of get_mask_on_nan.
     @staticmethod
     def _reference_observers():
         try:
@@ -664,34 +664,40 @@ class AutoRegressiveLightning(_Base):
     def on_validation_start(self):
         """lightning.py:864-886."""
         self.valid_plotters = []
-        ref_plots, _ = self._reference_observers()
-        if self.logging_enabled and ref_plots is not None:
+        if self.logging_enabled:
+            from .observers import StateErrorPlot
+
             l1_loss = ScaledLoss("L1Loss", reduction="none")
             l1_loss.prepare(self, self.interior_mask, self.dataset_info)
-            sp = getattr(self, "save_path", None)
-            self.valid_plotters = [
-                ref_plots.StateErrorPlot({"mae": l1_loss}, prefix="Validation"),
-                ref_plots.PredictionTimestepPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
-                ref_plots.PredictionEpochPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
-            ]
+            self.valid_plotters = [StateErrorPlot({"mae": l1_loss}, prefix="Validation")]
+            ref_plots, _ = self._reference_observers()
+            if ref_plots is not None:
+                sp = getattr(self, "save_path", None)
+                self.valid_plotters += [
+                    ref_plots.PredictionTimestepPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
+                    ref_plots.PredictionEpochPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
+                ]
 
     def on_test_start(self):
         """lightning.py:986-1008."""
         self.test_plotters = []
-        ref_plots, _ = self._reference_observers()
-        if self.logging_enabled and ref_plots is not None:
+        if self.logging_enabled:
+            from .observers import SpatialErrorPlot, StateErrorPlot
+
             metrics = {}
             for torch_loss, alias in ("L1Loss", "mae"), ("MSELoss", "rmse"):
                 loss = ScaledLoss(torch_loss, reduction="none")
                 loss.prepare(self, self.interior_mask, self.dataset_info)
                 metrics[alias] = loss
             sp = getattr(self, "save_path", None)
-            self.test_plotters = [
-                ref_plots.StateErrorPlot(metrics, save_path=sp),
-                ref_plots.SpatialErrorPlot(),
-                ref_plots.PredictionTimestepPlot(num_samples_to_plot=self.num_samples_to_plot, num_features_to_plot=4,
-                                                 prefix="Test", save_path=sp),
-            ]
+            state, spatial = StateErrorPlot(metrics, save_path=sp), SpatialErrorPlot()
+            state.map_consumer = spatial   # notified one after the other with the same objects: one pass for both
+            self.test_plotters = [state, spatial]
+            ref_plots, _ = self._reference_observers()
+            if ref_plots is not None:
+                self.test_plotters.append(
+                    ref_plots.PredictionTimestepPlot(num_samples_to_plot=self.num_samples_to_plot, num_features_to_plot=4,
+                                                     prefix="Test", save_path=sp))
 
     def _notify(self, plotters, batch, prediction, target, mask):
         for plotter in plotters:

@@ -292,6 +292,35 @@ def scaled_loss(pred, target, spec: MaskSpec, std, interior, num_interior, kind,
     return out
 
 
+def eval_sums(pred, target, spec: MaskSpec, std, interior, num_interior, weights, map_kind, map_acc=None, accumulate=False):
+    """What the score-card and spatial-error observers need of one validation / test step, in one pass over prediction and target
+    (p4c_eval_sums): returns ``(scores, masked_count)`` with ``scores`` (2,B,T,F) -- [0] = ``scaled_loss(..., L1)``, [1] =
+    ``scaled_loss(..., MSE)`` -- and ``masked_count`` (1,) int32 = ``masked_count(spec, target)`` (0 without a mask).  With
+    ``map_acc`` (T,*S) and ``map_kind`` (LOSS_MSE / LOSS_L1) the batch sum of ``weighted_loss_map`` is written to it
+    (``accumulate=False``) or added to it (``accumulate=True``); ``map_kind=None`` forms no map.  Not differentiable."""
+    L.require_cuda(pred, target)
+    B, T, F = pred.shape[0], pred.shape[1], pred.shape[-1]
+    N = _numel_spatial(pred, 2)
+    p, (pbs, pts) = _rows(pred.detach().float(), 2)
+    g, (gbs, gts) = _rows(target.detach().float(), 2)
+    if map_kind is None:
+        map_kind, map_acc = L.EVAL_MAP_NONE, None
+    if map_acc is not None:
+        if map_acc.dtype != torch.float32 or not map_acc.is_contiguous() or map_acc.numel() != T * N or map_acc.device != p.device:
+            raise L.P4CError("eval_sums: map_acc must be a contiguous fp32 (T, *spatial) tensor on the prediction's device")
+        if weights is None:
+            raise L.P4CError("eval_sums: the map needs the per-feature weights")
+    scores = torch.empty(2, B, T, F, dtype=torch.float32, device=p.device)
+    count = torch.empty(1, dtype=torch.int32, device=p.device)
+    ws = torch.empty(L.lib().p4c_eval_sums_workspace_bytes(B, T, N, F) // 4, dtype=torch.float32, device=p.device)
+    L.call(
+        "p4c_eval_sums", L.ptr(p), pbs, pts, L.ptr(g), gbs, gts, L.ptr(spec.tensor), spec.mode, L.ptr(interior), float(num_interior),
+        L.ptr(std), L.ptr(weights), int(map_kind), L.ptr(map_acc), int(bool(accumulate)), L.ptr(scores), L.ptr(count), L.ptr(ws),
+        B, T, N, F, L.stream(p.device),
+    )
+    return scores, count
+
+
 # ------------------------------------------------------------------------------ K2+K3 fused training step
 class _ARStepLoss(torch.autograd.Function):
     """
