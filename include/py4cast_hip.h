@@ -353,6 +353,36 @@ int p4c_ar_update_loss_bwd_saved(const float* g_next, int64_t g_next_bs, const v
                                  const int32_t* masked_count, int kind, int mask_mode, void* dy, int dy_dtype, int y_cs,
                                  float* dprev, int64_t dprev_bs, int B, int64_t N, int F, float keep_prev, p4c_stream_t stream);
 
+/* The FREE step: an AR step without a loss term -- an intermediary step of num_inter_steps >= 2 (its border is forced to the target,
+ * it has no loss and is not part of the prediction: lightning.py:583-658) or an inference step (no target, nothing forced: :627).
+ *   new_state = [ border * nan_to_num?(target) + interior * ] ( keep_prev * nan_to_num?(prev) + y * std + mean )
+ * std / mean are NULL together (diff_ar); target / border_mask / interior_mask are NULL together when nothing is forced.  x_next is
+ * optional: the next network input in the layout of p4c_ar_update_loss_fwd_next (state | statics | forcing | zeros to c_pad, dtype of
+ * y); it needs the 16-byte or the flat path of that function and nan_to_num == 0 (P4C_ERR_UNSUPPORTED / _INVALID otherwise), without
+ * it any shape runs (scalar path).  These are compile-time variants of the loss-carrying kernels with the target-error, weight and
+ * reduction code removed: new_state and x_next are bit-identical to p4c_ar_update_loss_fwd[_next]'s for equal inputs; nothing else is
+ * written, no weights, workspace or loss column are read. */
+int p4c_ar_update_next(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs, const float* target,
+                       int64_t tgt_bs, const float* std, const float* mean, const float* border_mask,
+                       const float* interior_mask, float* new_state, int64_t new_bs, int nan_to_num, int B, int64_t N, int F,
+                       float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
+                       const float* forcing_next, int64_t forcing_bs, int Ff, p4c_stream_t stream);
+/* The free step behind the network's fused 1x1 output convolution: p4c_out_conv_update_loss_fwd without the loss (same forms, same
+ * conditions, same new_state / x_next bit for bit).  target / border_mask / interior_mask are NULL together when nothing is forced. */
+int p4c_out_conv_update_fwd(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
+                            const float* prev, int64_t prev_bs, const float* target, int64_t tgt_bs, const float* std,
+                            const float* mean, const float* border_mask, const float* interior_mask, float* new_state,
+                            int64_t new_bs, int B, int64_t N, int F, float keep_prev, void* x_next, int c_pad,
+                            const float* statics, int64_t statics_bs, int Fs, const float* forcing_next, int64_t forcing_bs,
+                            int Ff, p4c_stream_t stream);
+/* Backward of a free step: with g = g_next + g_next2 (either may be NULL; g_next2 has channel stride g2_cs and the dtype of dy),
+ *   dy = (g * interior) * std  (dtype of dy, channels F .. y_cs-1 zero),   dprev = (g * interior) * keep_prev  (may be NULL),
+ * without the interior factor when force_border == 0 (interior_mask may then be NULL).  Reads nothing of the forward step: no new
+ * state, no target.  (p4c_ar_update_loss_bwd with a NULL gloss is not this adjoint: it still reads both.) */
+int p4c_ar_update_next_bwd(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype, int g2_cs,
+                           const float* std, const float* interior_mask, int force_border, void* dy, int dy_dtype, int y_cs,
+                           float* dprev, int64_t dprev_bs, int B, int64_t N, int F, float keep_prev, p4c_stream_t stream);
+
 /* ====================================================================================
  * Model kernels -- the network arithmetic the reference obtains from mfai v5.0.1
  * (py4cast/models.py:10-20; model forward at py4cast/lightning.py:591-596) and, underneath,

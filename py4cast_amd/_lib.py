@@ -64,6 +64,14 @@ SIGNATURES = {
     "p4c_ar_update_loss_fwd_next_saved": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                           P, I, P, L, I, P, L, I, P, L, P],
     "p4c_ar_update_loss_bwd_saved": [P, L, P, I, I, P, L, P, L, P, P, I, P, F, P, I, I, P, I, I, P, L, I, L, I, F, P],
+    # the free step (no loss term): prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border, interior, new_state, new_bs,
+    # nan_to_num, B, N, F, keep_prev | x_next, c_pad, statics, statics_bs, Fs, forcing, forcing_bs, Ff, stream
+    "p4c_ar_update_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, I, I, L, I, F, P, I, P, L, I, P, L, I, P],
+    # a, a_scale, a_shift, wout, cout | prev, prev_bs, target, tgt_bs, std, mean, border, interior, new_state, new_bs, B, N, F, keep_prev |
+    # x_next, c_pad, statics, statics_bs, Fs, forcing, forcing_bs, Ff, stream
+    "p4c_out_conv_update_fwd": [P, P, P, P, I, P, L, P, L, P, P, P, P, P, L, I, L, I, F, P, I, P, L, I, P, L, I, P],
+    # g_next, g_next_bs, g_next2, g2_dtype, g2_cs, std, interior, force_border, dy, dy_dtype, y_cs, dprev, dprev_bs, B, N, F, keep_prev, stream
+    "p4c_ar_update_next_bwd": [P, L, P, I, I, P, P, I, P, I, I, P, L, I, L, I, F, P],
 }
 OTHER = {
     "p4c_version": ([], c_int),

@@ -502,7 +502,10 @@ struct NextX {
 };
 typedef float v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
-template <typename TY, bool NEXT>
+// LOSS = false: the FREE step (an intermediary step of num_inter_steps >= 2, an inference step) -- the same update, border forcing
+// and next input with the target-error, weight and reduction code compiled out: `weights` / `partial` are not touched, `target`
+// and `interior_mask` are read only where a border is forced (both may be NULL otherwise)
+template <typename TY, bool NEXT, bool LOSS = true>
 __global__ void __launch_bounds__(256)
     ar_update_loss_fwd_v4_kernel(const float* __restrict__ prev, int64_t prev_bs, const TY* __restrict__ y, int y_cs,
                                  const float* __restrict__ target, int64_t tgt_bs, const float* __restrict__ std,
@@ -519,7 +522,7 @@ __global__ void __launch_bounds__(256)
     const bool from_nan = mask_mode == P4C_MASK_FROM_NAN;
     v4f w = {0, 0, 0, 0}, sd = {1, 1, 1, 1}, mn = {0, 0, 0, 0};
     if (act) {
-        w = *reinterpret_cast<const v4f*>(weights + 4 * q);
+        if (LOSS) w = *reinterpret_cast<const v4f*>(weights + 4 * q);
         if (std) {
             sd = *reinterpret_cast<const v4f*>(std + 4 * q);
             mn = *reinterpret_cast<const v4f*>(mean + 4 * q);
@@ -533,7 +536,7 @@ __global__ void __launch_bounds__(256)
     int64_t tstride = 0;
     TY* xn = nullptr;
     bf16* lgr = nullptr;
-    if (NEXT && nx.lgrad) lgr = reinterpret_cast<bf16*>(nx.lgrad) + (int64_t)b * nx.lgrad_bs;
+    if (LOSS && NEXT && nx.lgrad) lgr = reinterpret_cast<bf16*>(nx.lgrad) + (int64_t)b * nx.lgrad_bs;
     if (NEXT && nx.x) {
         xn = reinterpret_cast<TY*>(nx.x) + (int64_t)b * N * nx.c_pad;
         const int c0 = F + 4 * q, o_forc = F + nx.Fs, c_in = F + nx.Fs + nx.Ff;
@@ -562,13 +565,14 @@ __global__ void __launch_bounds__(256)
             store4f(xn + n * nx.c_pad + F + 4 * q, tq);
         }
         if (!act) continue;
-        const float im = interior_mask[n];
+        const float im = (LOSS || border_mask) ? interior_mask[n] : 1.0f;
         const float bm = border_mask ? border_mask[n] : 0.0f;
         const int64_t e = n * F + 4 * q;
         const v4f yv = load4f(y + ((int64_t)b * N + n) * y_cs + 4 * q);
         v4f pv = {0, 0, 0, 0};
         if (prev) pv = *reinterpret_cast<const v4f*>(prev + (int64_t)b * prev_bs + e);
-        v4f tg = *reinterpret_cast<const v4f*>(target + (int64_t)b * tgt_bs + e);
+        v4f tg = {0, 0, 0, 0};
+        if (LOSS || border_mask) tg = *reinterpret_cast<const v4f*>(target + (int64_t)b * tgt_bs + e);
         v4f o, lg;
         float s = 0.0f;
 #pragma unroll
@@ -588,14 +592,17 @@ __global__ void __launch_bounds__(256)
             }
             if (border_mask) pr = bm * t0 + im * pr;
             o[j] = pr;
-            s += loss_elem(pr, t0, m, kind) * w[j];
-            if (NEXT) lg[j] = loss_elem_grad(pr, t0, m, kind);
+            if (LOSS) {
+                s += loss_elem(pr, t0, m, kind) * w[j];
+                if (NEXT) lg[j] = loss_elem_grad(pr, t0, m, kind);
+            }
         }
         *reinterpret_cast<v4f*>(new_state + (int64_t)b * new_bs + e) = o;
         if (NEXT && xn) store4f(xn + n * nx.c_pad + 4 * q, o);
-        if (NEXT && lgr) store4f(lgr + e, lg);
-        acc += s * im;
+        if (LOSS && NEXT && lgr) store4f(lgr + e, lg);
+        if (LOSS) acc += s * im;
     }
+    if (!LOSS) return;
     acc = wave_sum(acc);
     if (lane == 0) red[wv] = acc;
     __syncthreads();
@@ -603,7 +610,9 @@ __global__ void __launch_bounds__(256)
 }
 
 // SAVED: `new_state` holds bf16 rows of d loss_elem / d pred written by the forward (NextX::lgrad; stride new_bs), `target` is unused
-template <typename TY, bool SAVED = false>
+// LOSS = false: the adjoint of a free step -- dy = ((g_next + g_next2) * blend) * std, dprev = (..) * keep_prev; nothing of the loss
+// (gloss, new_state, target, weights) is read, interior_mask only where a border was forced
+template <typename TY, bool SAVED = false, bool LOSS = true>
 __global__ void __launch_bounds__(256)
     ar_update_loss_bwd_v4_kernel(const float* __restrict__ g_next, int64_t g_next_bs, const TY* __restrict__ g_next2,
                                  int g2_cs, const float* __restrict__ gloss, int64_t gloss_stride,
@@ -618,11 +627,11 @@ __global__ void __launch_bounds__(256)
     const int pp = lane / FP4, q = lane % FP4;
     const bool act = 4 * q < F, wr = 4 * q < y_cs;
     const bool from_nan = mask_mode == P4C_MASK_FROM_NAN;
-    const float denom = num_interior - (masked_count ? (float)(*masked_count) : 0.0f);
-    const float scale = gloss ? gloss[(int64_t)b * gloss_stride] / denom : 0.0f;
+    const float denom = num_interior - ((LOSS && masked_count) ? (float)(*masked_count) : 0.0f);
+    const float scale = (LOSS && gloss) ? gloss[(int64_t)b * gloss_stride] / denom : 0.0f;
     v4f w = {0, 0, 0, 0}, sd = {1, 1, 1, 1};
     if (act) {
-        w = *reinterpret_cast<const v4f*>(weights + 4 * q);
+        if (LOSS) w = *reinterpret_cast<const v4f*>(weights + 4 * q);
         if (std) sd = *reinterpret_cast<const v4f*>(std + 4 * q);
     }
     const int64_t stride = (int64_t)gridDim.x * 4 * PP;
@@ -630,12 +639,13 @@ __global__ void __launch_bounds__(256)
         if (!wr) continue;
         v4f gy = {0, 0, 0, 0};
         if (act) {
-            const float im = interior_mask[n];
+            const float im = (LOSS || force_border) ? interior_mask[n] : 1.0f;
             const float sc = scale * im;
             const float blend = force_border ? im : 1.0f;
             const int64_t e = n * F + 4 * q;
             v4f ns = {0, 0, 0, 0}, tg = {0, 0, 0, 0}, lgv = {0, 0, 0, 0};
-            if (SAVED) {
+            if (!LOSS) {
+            } else if (SAVED) {
                 lgv = load4f(reinterpret_cast<const bf16*>(new_state) + (int64_t)b * new_bs + e);
             } else {
                 ns = *reinterpret_cast<const v4f*>(new_state + (int64_t)b * new_bs + e);
@@ -652,7 +662,7 @@ __global__ void __launch_bounds__(256)
                     m = (t0 != t0) ? 0.0f : 1.0f;
                     t0 = nan_to_zero(t0);
                 }
-                float g = sc * w[j] * (SAVED ? lgv[j] : loss_elem_grad(ns[j], t0, m, kind));
+                float g = LOSS ? sc * w[j] * (SAVED ? lgv[j] : loss_elem_grad(ns[j], t0, m, kind)) : 0.0f;
                 if (g_next) g += g1[j];
                 if (g_next2) g += g2[j];
                 gp[j] = g * blend;
@@ -705,7 +715,8 @@ __device__ __forceinline__ unsigned int pack_bf16(float lo, float hi) {
     return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2_t));
 }
 
-template <typename TY, bool FRONT = false>
+// LOSS = false: the free step (see ar_update_loss_fwd_v4_kernel)
+template <typename TY, bool FRONT = false, bool LOSS = true>
 __global__ void __launch_bounds__(256)
     ar_update_loss_fwd_flat_kernel(const float* __restrict__ prev, int64_t prev_bs, const TY* __restrict__ y, int y_cs,
                                    const float* __restrict__ target, int64_t tgt_bs, const float* __restrict__ std,
@@ -749,16 +760,16 @@ __global__ void __launch_bounds__(256)
     const unsigned rcp = ((1u << 20) + F - 1) / F;
     if (tid < 64) {
         const bool ok = tid < F;
-        cst[tid] = ok ? weights[tid] : 0.f;
+        cst[tid] = (LOSS && ok) ? weights[tid] : 0.f;
         cst[64 + tid] = (ok && std) ? std[tid] : 1.f;
         cst[128 + tid] = (ok && mean) ? mean[tid] : 0.f;
     }
     const float* prevb = prev ? prev + (int64_t)b * prev_bs : nullptr;
-    const float* tgtb = target + (int64_t)b * tgt_bs;
+    const float* tgtb = (LOSS || border_mask) ? target + (int64_t)b * tgt_bs : nullptr;
     float* newb = new_state + (int64_t)b * new_bs;
     const TY* yb = y + (int64_t)b * N * y_cs;
     TY* xn = nx.x ? reinterpret_cast<TY*>(nx.x) + (int64_t)b * N * nx.c_pad : nullptr;
-    bf16* lgr = nx.lgrad ? reinterpret_cast<bf16*>(nx.lgrad) + (int64_t)b * nx.lgrad_bs : nullptr;
+    bf16* lgr = (LOSS && nx.lgrad) ? reinterpret_cast<bf16*>(nx.lgrad) + (int64_t)b * nx.lgrad_bs : nullptr;
     const float* stat = xn ? nx.statics + (int64_t)b * nx.statics_bs : nullptr;
     const float* forc = xn ? nx.forcing + (int64_t)b * nx.forcing_bs : nullptr;
     const int yslots = y_cs * (int)sizeof(TY) / 16, xslots = xn ? nx.c_pad * (int)sizeof(TY) / 16 : 0;
@@ -828,7 +839,7 @@ __global__ void __launch_bounds__(256)
         }
         if (tid < 64) {
             const bool ok = tid < np;
-            msk[tid] = ok ? interior_mask[n0 + tid] : 0.f;
+            msk[tid] = (ok && (LOSS || border_mask)) ? interior_mask[n0 + tid] : 0.f;
             msk[64 + tid] = (ok && border_mask) ? border_mask[n0 + tid] : 0.f;
         }
         // ---- the next input's channels F .. c_pad - 1: statics | next forcing | zeros (lightning.py:760-765)
@@ -872,7 +883,8 @@ __global__ void __launch_bounds__(256)
             const int64_t E = n0 * F + e0;
             v4f pv = {0, 0, 0, 0};
             if (prevb) pv = *reinterpret_cast<const v4f*>(prevb + E);
-            const v4f tg = *reinterpret_cast<const v4f*>(tgtb + E);
+            v4f tg = {0, 0, 0, 0};
+            if (LOSS || border_mask) tg = *reinterpret_cast<const v4f*>(tgtb + E);
             int pl, f;
             flat_pf(e0, F, rcp, pl, f);
             v4f o, lg;
@@ -890,13 +902,15 @@ __global__ void __launch_bounds__(256)
                 }
                 if (border_mask) pr = bm * t0 + im * pr;
                 o[j] = pr;
-                acc += (loss_elem(pr, t0, 1.0f, kind) * cst[f]) * im;
-                lg[j] = loss_elem_grad(pr, t0, 1.0f, kind);
+                if (LOSS) {
+                    acc += (loss_elem(pr, t0, 1.0f, kind) * cst[f]) * im;
+                    lg[j] = loss_elem_grad(pr, t0, 1.0f, kind);
+                }
                 if (xn) xtile[pl * nx.c_pad + f] = from_f32<TY>(pr);
                 if (++f == F) { f = 0; ++pl; }
             }
             *reinterpret_cast<v4f*>(newb + E) = o;
-            if (lgr) store4f(lgr + E, lg);
+            if (LOSS && lgr) store4f(lgr + E, lg);
         }
         if (xn) {
             __syncthreads();
@@ -904,6 +918,7 @@ __global__ void __launch_bounds__(256)
                 reinterpret_cast<norm4u*>(xn + n0 * nx.c_pad)[sl] = reinterpret_cast<const norm4u*>(xtile)[sl];
         }
     }
+    if (!LOSS) return;
     acc = wave_sum(acc);
     if (lane == 0) red[wv] = acc;
     __syncthreads();
@@ -911,7 +926,8 @@ __global__ void __launch_bounds__(256)
 }
 
 // SAVED: `new_state` holds the bf16 rows of d loss_elem / d pred the forward saved (stride new_bs), `target` is unused
-template <typename TY, bool SAVED>
+// LOSS = false: the adjoint of a free step (see ar_update_loss_bwd_v4_kernel)
+template <typename TY, bool SAVED, bool LOSS = true>
 __global__ void __launch_bounds__(256)
     ar_update_loss_bwd_flat_kernel(const float* __restrict__ g_next, int64_t g_next_bs, const TY* __restrict__ g_next2, int g2_cs,
                                    const float* __restrict__ gloss, int64_t gloss_stride, const float* __restrict__ new_state,
@@ -928,20 +944,20 @@ __global__ void __launch_bounds__(256)
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
     const unsigned rcp = ((1u << 20) + F - 1) / F;
-    const float denom = num_interior - (masked_count ? (float)(*masked_count) : 0.0f);
-    const float scale = gloss ? gloss[(int64_t)b * gloss_stride] / denom : 0.0f;
+    const float denom = num_interior - ((LOSS && masked_count) ? (float)(*masked_count) : 0.0f);
+    const float scale = (LOSS && gloss) ? gloss[(int64_t)b * gloss_stride] / denom : 0.0f;
     if (tid < 64) {
         const bool ok = tid < F;
-        cst[tid] = ok ? weights[tid] : 0.f;
+        cst[tid] = (LOSS && ok) ? weights[tid] : 0.f;
         cst[64 + tid] = (ok && std) ? std[tid] : 1.f;
     }
     // channels F .. y_cs - 1 of dy are zero: cleared once, the flat phase only ever writes channels < F
     for (int i = tid; i < FLAT_P * y_cs; i += 256) dytile[i] = from_f32<TY>(0.f);
     const float* g1b = g_next ? g_next + (int64_t)b * g_next_bs : nullptr;
     const TY* g2b = g_next2 ? g_next2 + (int64_t)b * N * g2_cs : nullptr;
-    const float* nsb = SAVED ? nullptr : new_state + (int64_t)b * new_bs;
-    const bf16* lgb = SAVED ? reinterpret_cast<const bf16*>(new_state) + (int64_t)b * new_bs : nullptr;
-    const float* tgtb = SAVED ? nullptr : target + (int64_t)b * tgt_bs;
+    const float* nsb = (SAVED || !LOSS) ? nullptr : new_state + (int64_t)b * new_bs;
+    const bf16* lgb = (SAVED && LOSS) ? reinterpret_cast<const bf16*>(new_state) + (int64_t)b * new_bs : nullptr;
+    const float* tgtb = (SAVED || !LOSS) ? nullptr : target + (int64_t)b * tgt_bs;
     TY* dyb = dy + (int64_t)b * N * y_cs;
     float* dpb = dprev ? dprev + (int64_t)b * dprev_bs : nullptr;
     const int gslots = g2_cs * (int)sizeof(TY) / 16, yslots = y_cs * (int)sizeof(TY) / 16;
@@ -953,13 +969,14 @@ __global__ void __launch_bounds__(256)
         if (g2b)
             for (int sl = tid; sl < np * gslots; sl += 256)
                 reinterpret_cast<norm4u*>(g2tile)[sl] = reinterpret_cast<const norm4u*>(g2b + n0 * g2_cs)[sl];
-        if (tid < 64) msk[tid] = tid < np ? interior_mask[n0 + tid] : 0.f;
+        if (tid < 64) msk[tid] = (tid < np && (LOSS || force_border)) ? interior_mask[n0 + tid] : 0.f;
         __syncthreads();
         const int nel = np * F;
         for (int e0 = 4 * tid; e0 < nel; e0 += 4 * 256) {
             const int64_t E = n0 * F + e0;
             v4f ns = {0, 0, 0, 0}, tg = {0, 0, 0, 0}, lgv = {0, 0, 0, 0}, g1 = {0, 0, 0, 0};
-            if (SAVED) {
+            if (!LOSS) {
+            } else if (SAVED) {
                 lgv = load4f(lgb + E);
             } else {
                 ns = *reinterpret_cast<const v4f*>(nsb + E);
@@ -974,7 +991,7 @@ __global__ void __launch_bounds__(256)
                 const float im = msk[pl];
                 const float sc = scale * im;
                 const float blend = force_border ? im : 1.0f;
-                float g = sc * cst[f] * (SAVED ? lgv[j] : loss_elem_grad(ns[j], tg[j], 1.0f, kind));
+                float g = LOSS ? sc * cst[f] * (SAVED ? lgv[j] : loss_elem_grad(ns[j], tg[j], 1.0f, kind)) : 0.0f;
                 if (g1b) g += g1[j];
                 if (g2b) g += to_f32<TY>(g2tile[pl * g2_cs + f]);
                 gp[j] = g * blend;
@@ -1006,7 +1023,8 @@ static inline bool flat_ok(int F, int64_t N, int row_cs, int esz) {
 
 // ------------------------------------------------------------------ fused AR update + loss (training path)
 // grid: (nblk, B).  One (b, t=i) column of the loss.
-template <typename TY>
+// LOSS = false: the free step (see ar_update_loss_fwd_v4_kernel); mask_mode FROM_NAN then only means nan_to_num of prev / target
+template <typename TY, bool LOSS = true>
 __global__ void __launch_bounds__(256)
     ar_update_loss_fwd_kernel(const float* __restrict__ prev, int64_t prev_bs, const TY* __restrict__ y, int y_cs,
                               const float* __restrict__ target, int64_t tgt_bs, const float* __restrict__ std,
@@ -1025,14 +1043,14 @@ __global__ void __launch_bounds__(256)
     for (int it = 0; it < LOSS_MAX_ITERS; ++it) {
         const int f = c0 + it * FP;
         const bool ok = it < iters && f < F;
-        w[it] = ok ? weights[f] : 0.0f;
+        w[it] = (LOSS && ok) ? weights[f] : 0.0f;
         sd[it] = (ok && std) ? std[f] : 1.0f;
         mn[it] = (ok && mean) ? mean[f] : 0.0f;
     }
     float acc = 0.0f;
     const int64_t stride = (int64_t)gridDim.x * 4 * PP;
     for (int64_t n = ((int64_t)blockIdx.x * 4 + wv) * PP + pp; n < N; n += stride) {
-        const float im = interior_mask[n];
+        const float im = (LOSS || border_mask) ? interior_mask[n] : 1.0f;
         const float bm = border_mask ? border_mask[n] : 0.0f;
         float s = 0.0f;
 #pragma unroll
@@ -1046,7 +1064,7 @@ __global__ void __launch_bounds__(256)
                     pv = prev[(int64_t)b * prev_bs + e];
                     if (from_nan) pv = nan_to_zero(pv);
                 }
-                float tg = target[(int64_t)b * tgt_bs + e];
+                float tg = (LOSS || border_mask) ? target[(int64_t)b * tgt_bs + e] : 0.0f;
                 float m = 1.0f;
                 if (from_nan) {
                     m = (tg != tg) ? 0.0f : 1.0f;
@@ -1061,18 +1079,20 @@ __global__ void __launch_bounds__(256)
                 }
                 if (border_mask) pr = bm * tg + im * pr;
                 new_state[(int64_t)b * new_bs + e] = pr;
-                s += loss_elem(pr, tg, m, kind) * w[it];
+                if (LOSS) s += loss_elem(pr, tg, m, kind) * w[it];
             }
         }
-        acc += s * im;
+        if (LOSS) acc += s * im;
     }
+    if (!LOSS) return;
     acc = wave_sum(acc);
     if (lane == 0) red[wv] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[(int64_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <typename TY, typename TG>
+// LOSS = false: the adjoint of a free step (see ar_update_loss_bwd_v4_kernel)
+template <typename TY, typename TG, bool LOSS = true>
 __global__ void __launch_bounds__(256)
     ar_update_loss_bwd_kernel(const float* __restrict__ g_next, int64_t g_next_bs, const TG* __restrict__ g_next2,
                               int g2_cs, const float* __restrict__ gloss, int64_t gloss_stride,
@@ -1087,11 +1107,11 @@ __global__ void __launch_bounds__(256)
     const int PP = 64 / FP;
     const int pp = lane / FP, c0 = lane % FP;
     const bool from_nan = mask_mode == P4C_MASK_FROM_NAN;
-    const float denom = num_interior - (masked_count ? (float)(*masked_count) : 0.0f);
-    const float scale = gloss ? gloss[(int64_t)b * gloss_stride] / denom : 0.0f;
+    const float denom = num_interior - ((LOSS && masked_count) ? (float)(*masked_count) : 0.0f);
+    const float scale = (LOSS && gloss) ? gloss[(int64_t)b * gloss_stride] / denom : 0.0f;
     const int64_t stride = (int64_t)gridDim.x * 4 * PP;
     for (int64_t n = ((int64_t)blockIdx.x * 4 + wv) * PP + pp; n < N; n += stride) {
-        const float im = interior_mask[n];
+        const float im = (LOSS || force_border) ? interior_mask[n] : 1.0f;
         const float sc = scale * im;
         const float blend = force_border ? im : 1.0f;
         for (int it = 0; it < iters; ++it) {
@@ -1100,13 +1120,16 @@ __global__ void __launch_bounds__(256)
             float gy = 0.0f;
             if (f < F) {
                 const int64_t e = n * F + f;
-                float tg = target[(int64_t)b * tgt_bs + e];
-                float m = 1.0f;
-                if (from_nan) {
-                    m = (tg != tg) ? 0.0f : 1.0f;
-                    tg = nan_to_zero(tg);
+                float g = 0.0f;
+                if (LOSS) {
+                    float tg = target[(int64_t)b * tgt_bs + e];
+                    float m = 1.0f;
+                    if (from_nan) {
+                        m = (tg != tg) ? 0.0f : 1.0f;
+                        tg = nan_to_zero(tg);
+                    }
+                    g = sc * weights[f] * loss_elem_grad(new_state[(int64_t)b * new_bs + e], tg, m, kind);
                 }
-                float g = sc * weights[f] * loss_elem_grad(new_state[(int64_t)b * new_bs + e], tg, m, kind);
                 if (g_next) g += g_next[(int64_t)b * g_next_bs + e];
                 if (g_next2) g += to_f32<TG>(g_next2[((int64_t)b * N + n) * g2_cs + f]);
                 const float gp = g * blend;
@@ -1302,16 +1325,21 @@ static int ar_update_loss_fwd_impl(const float* prev, int64_t prev_bs, const voi
                                    int64_t new_bs, const float* weights, float num_interior,
                                    const int32_t* masked_count, int kind, int mask_mode, float* loss_out,
                                    int64_t loss_stride, void* workspace, int B, int64_t N, int F, float keep_prev,
-                                   const NextX* next, p4c_stream_t stream) {
-    P4C_CHECK_ARG(y && target && interior_mask && new_state && weights && loss_out && workspace,
-                  "p4c_ar_update_loss_fwd: null pointer");
+                                   const NextX* next, p4c_stream_t stream, bool loss = true) {
+    // loss == false: the free step (p4c_ar_update_next) -- the LOSS = false instantiations, same path conditions, no final kernel
+    if (loss)
+        P4C_CHECK_ARG(y && target && interior_mask && new_state && weights && loss_out && workspace,
+                      "p4c_ar_update_loss_fwd: null pointer");
+    else
+        P4C_CHECK_ARG(y && new_state && (!border_mask || (target && interior_mask)),
+                      "p4c_ar_update_next: null pointer (border forcing needs border_mask, interior_mask and target)");
     P4C_CHECK_ARG(prev || keep_prev == 0.0f, "p4c_ar_update_loss_fwd: prev is null but keep_prev != 0");
     P4C_CHECK_ARG((std == nullptr) == (mean == nullptr), "p4c_ar_update_loss_fwd: std and mean go together");
     P4C_CHECK_ARG(mask_mode == P4C_MASK_NONE || mask_mode == P4C_MASK_FROM_NAN,
                   "p4c_ar_update_loss_fwd: only MASK_NONE / MASK_FROM_NAN are fused");
     P4C_CHECK_ARG(F > 0 && F <= 64 * LOSS_MAX_ITERS && y_cs >= F, "p4c_ar_update_loss_fwd: bad F / y_cs");
     if (!force_flat() && (y_dtype == P4C_F32 || y_dtype == P4C_BF16) && F % 4 == 0 && F <= 64 && y_cs % 4 == 0 && prev_bs % 4 == 0 && tgt_bs % 4 == 0 && new_bs % 4 == 0 &&
-        aligned16(prev) && aligned16(y) && aligned16(target) && aligned16(new_state) && aligned16(weights) && aligned16(std) &&
+        aligned16(prev) && aligned16(y) && aligned16(target) && aligned16(new_state) && (!loss || aligned16(weights)) && aligned16(std) &&
         aligned16(mean) &&
         (!next || !next->x || (next->c_pad % 4 == 0 && next->Fs % 4 == 0 && next->c_pad / 4 - F / 4 <= pow2_ge64(F / 4))) &&
         (!next || !next->lgrad || (next->lgrad_bs % 4 == 0 && aligned16(next->lgrad)))) {
@@ -1319,14 +1347,23 @@ static int ar_update_loss_fwd_impl(const float* prev, int64_t prev_bs, const voi
         const int nblk4 = loss_blocks(N, 64 / FP4, B);
         NextX nx{};
         if (next) nx = *next;
-#define P4C_LAUNCH_V4(TY, NEXTF)                                                                                              \
-    hipLaunchKernelGGL((ar_update_loss_fwd_v4_kernel<TY, NEXTF>), dim3(nblk4, B), dim3(256), 0, as_stream(stream), prev, prev_bs, \
+#define P4C_LAUNCH_V4(TY, NEXTF, LOSSF)                                                                                       \
+    hipLaunchKernelGGL((ar_update_loss_fwd_v4_kernel<TY, NEXTF, LOSSF>), dim3(nblk4, B), dim3(256), 0, as_stream(stream), prev, prev_bs, \
                        (const TY*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs, weights,  \
                        kind, mask_mode, (float*)workspace, N, F, keep_prev, FP4, nx)
+        if (!loss) {
+            if (y_dtype == P4C_F32) {
+                if (next) P4C_LAUNCH_V4(float, true, false); else P4C_LAUNCH_V4(float, false, false);
+            } else {
+                if (next) P4C_LAUNCH_V4(bf16, true, false); else P4C_LAUNCH_V4(bf16, false, false);
+            }
+            P4C_CHECK_LAUNCH("p4c_ar_update_next(v4)");
+            return P4C_OK;
+        }
         if (y_dtype == P4C_F32) {
-            if (next) P4C_LAUNCH_V4(float, true); else P4C_LAUNCH_V4(float, false);
+            if (next) P4C_LAUNCH_V4(float, true, true); else P4C_LAUNCH_V4(float, false, true);
         } else {
-            if (next) P4C_LAUNCH_V4(bf16, true); else P4C_LAUNCH_V4(bf16, false);
+            if (next) P4C_LAUNCH_V4(bf16, true, true); else P4C_LAUNCH_V4(bf16, false, true);
         }
 #undef P4C_LAUNCH_V4
         P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd(v4)");
@@ -1350,6 +1387,21 @@ static int ar_update_loss_fwd_impl(const float* prev, int64_t prev_bs, const voi
             int nblk = loss_blocks(N, FLAT_P / 4, B);
             if (nblk > ntiles) nblk = (int)ntiles;
             const size_t smem = (size_t)FLAT_P * y_cs * esz + (nx.x ? (size_t)FLAT_P * nx.c_pad * esz : 0) + 5 * 64 * sizeof(float);
+            if (!loss) {
+                if (y_dtype == P4C_F32) {
+                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<float, false, false>, (int)smem));
+                    hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<float, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
+                                       prev, prev_bs, (const float*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                       new_bs, weights, kind, (float*)workspace, N, F, keep_prev, nx, FlatFront{});
+                } else {
+                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16, false, false>, (int)smem));
+                    hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<bf16, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
+                                       prev, prev_bs, (const bf16*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                       new_bs, weights, kind, (float*)workspace, N, F, keep_prev, nx, FlatFront{});
+                }
+                P4C_CHECK_LAUNCH("p4c_ar_update_next(flat)");
+                return P4C_OK;
+            }
             if (y_dtype == P4C_F32) {
                 P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<float>, (int)smem));
                 hipLaunchKernelGGL(ar_update_loss_fwd_flat_kernel<float>, dim3(nblk, B), dim3(256), smem, as_stream(stream), prev, prev_bs,
@@ -1372,16 +1424,17 @@ static int ar_update_loss_fwd_impl(const float* prev, int64_t prev_bs, const voi
                                                "flat path (F <= 64, N * F %% 4 == 0, whole 16-byte slots per row, aligned rows, no NaN masks)");
     const int FP = pow2_ge64(F), iters = (F + FP - 1) / FP;
     const int nblk = loss_blocks(N, 64 / FP, B);
-#define P4C_LAUNCH_FWD(TY)                                                                                              \
-    hipLaunchKernelGGL(ar_update_loss_fwd_kernel<TY>, dim3(nblk, B), dim3(256), 0, as_stream(stream), prev, prev_bs,      \
+#define P4C_LAUNCH_FWD(TY, LOSSF)                                                                                       \
+    hipLaunchKernelGGL((ar_update_loss_fwd_kernel<TY, LOSSF>), dim3(nblk, B), dim3(256), 0, as_stream(stream), prev, prev_bs, \
                        (const TY*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs,    \
                        weights, kind, mask_mode, (float*)workspace, N, F, keep_prev, FP, iters)
-    if (y_dtype == P4C_F32)
-        P4C_LAUNCH_FWD(float);
-    else if (y_dtype == P4C_BF16)
-        P4C_LAUNCH_FWD(bf16);
-    else
-        return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_fwd: bad dtype %d", y_dtype);
+    if (y_dtype != P4C_F32 && y_dtype != P4C_BF16) return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_fwd: bad dtype %d", y_dtype);
+    if (!loss) {
+        if (y_dtype == P4C_F32) P4C_LAUNCH_FWD(float, false); else P4C_LAUNCH_FWD(bf16, false);
+        P4C_CHECK_LAUNCH("p4c_ar_update_next");
+        return P4C_OK;
+    }
+    if (y_dtype == P4C_F32) P4C_LAUNCH_FWD(float, true); else P4C_LAUNCH_FWD(bf16, true);
 #undef P4C_LAUNCH_FWD
     P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd");
     hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream),
@@ -1442,6 +1495,29 @@ extern "C" int p4c_ar_update_loss_fwd_next_saved(const float* prev, int64_t prev
                                    loss_stride, workspace, B, N, F, keep_prev, &nx, stream);
 }
 
+// The FREE step: an AR step without a loss term -- an intermediary step of num_inter_steps >= 2 (border forced to the target, no
+// loss: lightning.py:583-658) or an inference step (no target, nothing forced: :627).  The LOSS = false instantiations of the kernels
+// above: new state and next input are the loss-carrying step's bit for bit; no weights, no partials, no workspace.  target, border_mask
+// and interior_mask are NULL together when nothing is forced; x_next is optional (16-byte or flat path only, no nan_to_num).
+extern "C" int p4c_ar_update_next(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs, const float* target,
+                                  int64_t tgt_bs, const float* std, const float* mean, const float* border_mask,
+                                  const float* interior_mask, float* new_state, int64_t new_bs, int nan_to_num, int B, int64_t N, int F,
+                                  float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
+                                  const float* forcing_next, int64_t forcing_bs, int Ff, p4c_stream_t stream) {
+    P4C_CHECK_ARG(B > 0 && N > 0, "p4c_ar_update_next: bad dims");
+    P4C_CHECK_ARG((target == nullptr) == (border_mask == nullptr), "p4c_ar_update_next: target and border_mask go together");
+    const int mask_mode = nan_to_num ? P4C_MASK_FROM_NAN : P4C_MASK_NONE;
+    NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0};
+    if (x_next) {
+        P4C_CHECK_ARG(statics && forcing_next, "p4c_ar_update_next: null pointer");
+        P4C_CHECK_ARG(c_pad >= F + Fs + Ff && Fs >= 0 && Ff >= 0, "p4c_ar_update_next: c_pad must be >= F + Fs + Ff");
+        P4C_CHECK_ARG(!nan_to_num, "p4c_ar_update_next: the NaN-mask input channel is built by p4c_build_x");
+    }
+    return ar_update_loss_fwd_impl(prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                   new_bs, nullptr, 0.0f, nullptr, P4C_LOSS_MSE, mask_mode, nullptr, 0, nullptr, B, N, F, keep_prev,
+                                   x_next ? &nx : nullptr, stream, false);
+}
+
 // ------------------------------------------------------------------ output convolution + state update + loss in ONE pass
 // The network's last layer -- mfai's HalfUNet ends in a 1x1 convolution on relu(norm(a)) (py4cast/lightning.py:591-596) -- and the rest
 // of the AR step (residual / scaled-residual update, border forcing, weighted loss, next step's network input, saved loss gradient:
@@ -1467,6 +1543,8 @@ struct OutConvArgs {
 //     grid point per register quad: rounded to bf16 they go to a per-wave LDS tile [32 points][64 features] as 8-byte pieces;
 //   back end: the loop body of ar_update_loss_fwd_v4_kernel, unchanged -- a lane owns 4 consecutive features of a grid point, 16-byte
 //     accesses to prev / target / new state / next input / saved loss gradients -- with y read from the LDS tile instead of HBM.
+// LOSS = false: the free step behind the same front end (see ar_update_loss_fwd_v4_kernel)
+template <bool LOSS = true>
 __global__ void __launch_bounds__(256) out_conv_update_loss_fwd_kernel(OutConvArgs g, int FP4) {
     __shared__ float red[4];
     __shared__ bf16x8_t wimg[2 * 4 * 64];                   // A fragments: (T, ks, lane) = W[32 T + (l & 31)][16 ks + 8 (l >> 5) .. + 7]
@@ -1501,7 +1579,7 @@ __global__ void __launch_bounds__(256) out_conv_update_loss_fwd_kernel(OutConvAr
     const bool act = 4 * q < F;
     v4f w = {0, 0, 0, 0}, sd = {1, 1, 1, 1}, mn = {0, 0, 0, 0};
     if (act) {
-        w = *reinterpret_cast<const v4f*>(g.weights + 4 * q);
+        if (LOSS) w = *reinterpret_cast<const v4f*>(g.weights + 4 * q);
         if (g.std) {
             sd = *reinterpret_cast<const v4f*>(g.std + 4 * q);
             mn = *reinterpret_cast<const v4f*>(g.mean + 4 * q);
@@ -1514,7 +1592,7 @@ __global__ void __launch_bounds__(256) out_conv_update_loss_fwd_kernel(OutConvAr
     int64_t tstride = 0;
     bf16* xn = nullptr;
     bf16* lgr = nullptr;
-    if (nx.lgrad) lgr = reinterpret_cast<bf16*>(nx.lgrad) + (int64_t)b * nx.lgrad_bs;
+    if (LOSS && nx.lgrad) lgr = reinterpret_cast<bf16*>(nx.lgrad) + (int64_t)b * nx.lgrad_bs;
     if (nx.x) {
         xn = reinterpret_cast<bf16*>(nx.x) + (int64_t)b * N * nx.c_pad;
         const int c0 = F + 4 * q, o_forc = F + nx.Fs, c_in = F + nx.Fs + nx.Ff;
@@ -1600,13 +1678,14 @@ __global__ void __launch_bounds__(256) out_conv_update_loss_fwd_kernel(OutConvAr
                 store4f(xn + n * nx.c_pad + F + 4 * q, tq);
             }
             if (!act) continue;
-            const float im = g.interior_mask[n];
+            const float im = (LOSS || g.border_mask) ? g.interior_mask[n] : 1.0f;
             const float bm = g.border_mask ? g.border_mask[n] : 0.0f;
             const int64_t e = n * F + 4 * q;
             const v4f yv = load4f(yt + pl * 64 + 4 * (q ^ (pl & 15)));
             v4f pv = {0, 0, 0, 0};
             if (g.prev) pv = *reinterpret_cast<const v4f*>(g.prev + (int64_t)b * g.prev_bs + e);
-            const v4f tg = *reinterpret_cast<const v4f*>(g.target + (int64_t)b * g.tgt_bs + e);
+            v4f tg = {0, 0, 0, 0};
+            if (LOSS || g.border_mask) tg = *reinterpret_cast<const v4f*>(g.target + (int64_t)b * g.tgt_bs + e);
             v4f o, lg;
             float s = 0.0f;
 #pragma unroll
@@ -1621,32 +1700,41 @@ __global__ void __launch_bounds__(256) out_conv_update_loss_fwd_kernel(OutConvAr
                 }
                 if (g.border_mask) pr = bm * t0 + im * pr;
                 o[j] = pr;
-                s += loss_elem(pr, t0, 1.0f, g.kind) * w[j];
-                lg[j] = loss_elem_grad(pr, t0, 1.0f, g.kind);
+                if (LOSS) {
+                    s += loss_elem(pr, t0, 1.0f, g.kind) * w[j];
+                    lg[j] = loss_elem_grad(pr, t0, 1.0f, g.kind);
+                }
             }
             *reinterpret_cast<v4f*>(g.new_state + (int64_t)b * g.new_bs + e) = o;
             if (xn) store4f(xn + n * nx.c_pad + 4 * q, o);
-            if (lgr) store4f(lgr + e, lg);
-            acc += s * im;
+            if (LOSS && lgr) store4f(lgr + e, lg);
+            if (LOSS) acc += s * im;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the tile's reads are done before the next tile overwrites it)
     }
+    if (!LOSS) return;
     acc = wave_sum(acc);
     if (lane == 0) red[wv] = acc;
     __syncthreads();
     if (threadIdx.x == 0) g.partial[(int64_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
-                                            const float* prev, int64_t prev_bs, const float* target, int64_t tgt_bs, const float* std,
-                                            const float* mean, const float* border_mask, const float* interior_mask, float* new_state,
-                                            int64_t new_bs, const float* weights, float num_interior, const int32_t* masked_count,
-                                            int kind, float* loss_out, int64_t loss_stride, void* workspace, int B, int64_t N, int F,
-                                            float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
-                                            const float* forcing_next, int64_t forcing_bs, int Ff, void* lgrad, int64_t lgrad_bs,
-                                            p4c_stream_t stream) {
-    P4C_CHECK_ARG(a && a_scale && a_shift && wout && target && interior_mask && new_state && weights && loss_out && workspace,
-                  "p4c_out_conv_update_loss_fwd: null pointer");
+// loss == false: the free step (p4c_out_conv_update_fwd) -- the LOSS = false instantiations, same form selection, no final kernel
+static int out_conv_update_impl(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
+                                const float* prev, int64_t prev_bs, const float* target, int64_t tgt_bs, const float* std,
+                                const float* mean, const float* border_mask, const float* interior_mask, float* new_state,
+                                int64_t new_bs, const float* weights, float num_interior, const int32_t* masked_count,
+                                int kind, float* loss_out, int64_t loss_stride, void* workspace, int B, int64_t N, int F,
+                                float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
+                                const float* forcing_next, int64_t forcing_bs, int Ff, void* lgrad, int64_t lgrad_bs,
+                                p4c_stream_t stream, bool loss) {
+    if (loss)
+        P4C_CHECK_ARG(a && a_scale && a_shift && wout && target && interior_mask && new_state && weights && loss_out && workspace,
+                      "p4c_out_conv_update_loss_fwd: null pointer");
+    else
+        P4C_CHECK_ARG(a && a_scale && a_shift && wout && new_state && (target == nullptr) == (border_mask == nullptr) &&
+                          (!border_mask || interior_mask) && B > 0 && N > 0,
+                      "p4c_out_conv_update_fwd: null pointer (target, border_mask and interior_mask go together)");
     P4C_CHECK_ARG(prev || keep_prev == 0.0f, "p4c_out_conv_update_loss_fwd: prev is null but keep_prev != 0");
     P4C_CHECK_ARG((std == nullptr) == (mean == nullptr), "p4c_out_conv_update_loss_fwd: std and mean go together");
     P4C_CHECK_ARG(cout >= F && cout <= 64 && F > 0, "p4c_out_conv_update_loss_fwd: needs 0 < F <= cout <= 64");
@@ -1673,6 +1761,14 @@ extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale,
         if (nblk > ntiles) nblk = (int)ntiles;
         const size_t smem = (size_t)FLAT_P * 64 * 2 + (x_next ? (size_t)FLAT_P * c_pad * 2 : 0) + 5 * 64 * sizeof(float) + 2 * 4 * 64 * 16 +
                             2 * 64 * sizeof(float);
+        if (!loss) {
+            P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16, true, false>, (int)smem));
+            hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<bf16, true, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream), prev,
+                               prev_bs, (const bf16*)nullptr, 64, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs,
+                               weights, kind, (float*)workspace, N, F, keep_prev, nx, fa);
+            P4C_CHECK_LAUNCH("p4c_out_conv_update_fwd(flat)");
+            return P4C_OK;
+        }
         P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16, true>, (int)smem));
         hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<bf16, true>), dim3(nblk, B), dim3(256), smem, as_stream(stream), prev, prev_bs,
                            (const bf16*)nullptr, 64, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs, weights, kind,
@@ -1685,7 +1781,7 @@ extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale,
         }
     }
     P4C_CHECK_ARG(prev_bs % 4 == 0 && tgt_bs % 4 == 0 && new_bs % 4 == 0 && aligned16(prev) && aligned16(target) && aligned16(new_state) &&
-                      aligned16(weights) && aligned16(std) && aligned16(mean),
+                      (!loss || aligned16(weights)) && aligned16(std) && aligned16(mean),
                   "p4c_out_conv_update_loss_fwd: rows must be 16-byte aligned (as p4c_ar_update_loss_fwd_next)");
     if (x_next) {
         P4C_CHECK_ARG(statics && forcing_next, "p4c_out_conv_update_loss_fwd: null pointer");
@@ -1699,12 +1795,44 @@ extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale,
     OutConvArgs g{(const bf16*)a, a_scale, a_shift, wout, cout, prev, prev_bs, target, tgt_bs, std, mean, border_mask, interior_mask,
                   new_state, new_bs, weights, kind, (float*)workspace, N, F, keep_prev,
                   NextX{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs}};
-    hipLaunchKernelGGL(out_conv_update_loss_fwd_kernel, dim3(nblk, B), dim3(256), 0, as_stream(stream), g, FP4);
+    if (!loss) {
+        hipLaunchKernelGGL(out_conv_update_loss_fwd_kernel<false>, dim3(nblk, B), dim3(256), 0, as_stream(stream), g, FP4);
+        P4C_CHECK_LAUNCH("p4c_out_conv_update_fwd");
+        return P4C_OK;
+    }
+    hipLaunchKernelGGL(out_conv_update_loss_fwd_kernel<true>, dim3(nblk, B), dim3(256), 0, as_stream(stream), g, FP4);
     P4C_CHECK_LAUNCH("p4c_out_conv_update_loss_fwd");
     hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream), (const float*)workspace, nblk, num_interior,
                        masked_count, loss_out, loss_stride, B);
     P4C_CHECK_LAUNCH("p4c_out_conv_update_loss_fwd(final)");
     return P4C_OK;
+}
+
+extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
+                                            const float* prev, int64_t prev_bs, const float* target, int64_t tgt_bs, const float* std,
+                                            const float* mean, const float* border_mask, const float* interior_mask, float* new_state,
+                                            int64_t new_bs, const float* weights, float num_interior, const int32_t* masked_count,
+                                            int kind, float* loss_out, int64_t loss_stride, void* workspace, int B, int64_t N, int F,
+                                            float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
+                                            const float* forcing_next, int64_t forcing_bs, int Ff, void* lgrad, int64_t lgrad_bs,
+                                            p4c_stream_t stream) {
+    return out_conv_update_impl(a, a_scale, a_shift, wout, cout, prev, prev_bs, target, tgt_bs, std, mean, border_mask, interior_mask,
+                                new_state, new_bs, weights, num_interior, masked_count, kind, loss_out, loss_stride, workspace, B, N, F,
+                                keep_prev, x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs, stream,
+                                true);
+}
+
+// The free step behind the fused 1x1 output convolution (see p4c_ar_update_next): same form selection and conditions as
+// p4c_out_conv_update_loss_fwd, same new state and next input bit for bit.
+extern "C" int p4c_out_conv_update_fwd(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
+                                       const float* prev, int64_t prev_bs, const float* target, int64_t tgt_bs, const float* std,
+                                       const float* mean, const float* border_mask, const float* interior_mask, float* new_state,
+                                       int64_t new_bs, int B, int64_t N, int F, float keep_prev, void* x_next, int c_pad,
+                                       const float* statics, int64_t statics_bs, int Fs, const float* forcing_next, int64_t forcing_bs,
+                                       int Ff, p4c_stream_t stream) {
+    return out_conv_update_impl(a, a_scale, a_shift, wout, cout, prev, prev_bs, target, tgt_bs, std, mean, border_mask, interior_mask,
+                                new_state, new_bs, nullptr, 0.0f, nullptr, P4C_LOSS_MSE, nullptr, 0, nullptr, B, N, F, keep_prev, x_next,
+                                c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0, stream, false);
 }
 
 // Backward of the fused step from the saved loss gradients (bf16 rows written by p4c_ar_update_loss_fwd_next_saved) instead of the
@@ -1763,25 +1891,44 @@ extern "C" int p4c_ar_update_loss_bwd_saved(const float* g_next, int64_t g_next_
     return P4C_OK;
 }
 
-extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype,
-                                      int g2_cs, const float* gloss, int64_t gloss_stride, const float* new_state,
-                                      int64_t new_bs, const float* target, int64_t tgt_bs, const float* std,
-                                      const float* interior_mask, int force_border, const float* weights,
-                                      float num_interior, const int32_t* masked_count, int kind, int mask_mode,
-                                      void* dy, int dy_dtype, int y_cs, float* dprev, int64_t dprev_bs, int B,
-                                      int64_t N, int F, float keep_prev, p4c_stream_t stream) {
-    P4C_CHECK_ARG(new_state && target && interior_mask && weights && dy, "p4c_ar_update_loss_bwd: null pointer");
+// loss == false: the adjoint of a free step (p4c_ar_update_next_bwd) -- the LOSS = false instantiations, same path conditions
+static int ar_update_loss_bwd_impl(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype,
+                                   int g2_cs, const float* gloss, int64_t gloss_stride, const float* new_state,
+                                   int64_t new_bs, const float* target, int64_t tgt_bs, const float* std,
+                                   const float* interior_mask, int force_border, const float* weights,
+                                   float num_interior, const int32_t* masked_count, int kind, int mask_mode,
+                                   void* dy, int dy_dtype, int y_cs, float* dprev, int64_t dprev_bs, int B,
+                                   int64_t N, int F, float keep_prev, p4c_stream_t stream, bool loss) {
+    if (loss)
+        P4C_CHECK_ARG(new_state && target && interior_mask && weights && dy, "p4c_ar_update_loss_bwd: null pointer");
+    else
+        P4C_CHECK_ARG(dy && (!force_border || interior_mask) && B > 0 && N > 0,
+                      "p4c_ar_update_next_bwd: null pointer (a forced border needs interior_mask)");
     P4C_CHECK_ARG(mask_mode == P4C_MASK_NONE || mask_mode == P4C_MASK_FROM_NAN,
                   "p4c_ar_update_loss_bwd: only MASK_NONE / MASK_FROM_NAN are fused");
     P4C_CHECK_ARG(F > 0 && F <= 64 * LOSS_MAX_ITERS && y_cs >= F, "p4c_ar_update_loss_bwd: bad F / y_cs");
     P4C_CHECK_ARG(dy_dtype == g2_dtype || !g_next2, "p4c_ar_update_loss_bwd: g_next2 dtype must equal dy dtype");
     if (!force_flat() && (dy_dtype == P4C_F32 || dy_dtype == P4C_BF16) && F % 4 == 0 && y_cs % 4 == 0 && y_cs <= 256 && g_next_bs % 4 == 0 && new_bs % 4 == 0 &&
         tgt_bs % 4 == 0 && dprev_bs % 4 == 0 && g2_cs % 4 == 0 && aligned16(g_next) && aligned16(g_next2) &&
-        aligned16(new_state) && aligned16(target) && aligned16(dy) && aligned16(dprev) && aligned16(weights) &&
+        aligned16(new_state) && aligned16(target) && aligned16(dy) && aligned16(dprev) && (!loss || aligned16(weights)) &&
         aligned16(std)) {
         const int FP4 = pow2_ge64(y_cs / 4);
         if (y_cs / 4 <= 64) {
             const int nblk4 = loss_blocks(N, 64 / FP4, B);
+            if (!loss) {
+                if (dy_dtype == P4C_F32)
+                    hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<float, false, false>), dim3(nblk4, B), dim3(256), 0, as_stream(stream),
+                                       g_next, g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
+                                       tgt_bs, std, interior_mask, force_border, weights, num_interior, masked_count, kind,
+                                       mask_mode, (float*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev, FP4);
+                else
+                    hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<bf16, false, false>), dim3(nblk4, B), dim3(256), 0, as_stream(stream),
+                                       g_next, g_next_bs, (const bf16*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
+                                       tgt_bs, std, interior_mask, force_border, weights, num_interior, masked_count, kind,
+                                       mask_mode, (bf16*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev, FP4);
+                P4C_CHECK_LAUNCH("p4c_ar_update_next_bwd(v4)");
+                return P4C_OK;
+            }
             if (dy_dtype == P4C_F32)
                 hipLaunchKernelGGL(ar_update_loss_bwd_v4_kernel<float>, dim3(nblk4, B), dim3(256), 0, as_stream(stream), g_next,
                                    g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
@@ -1805,6 +1952,23 @@ extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, co
             int nblk = loss_blocks(N, FLAT_P / 4, B);
             if (nblk > ntiles) nblk = (int)ntiles;
             const size_t smem = (size_t)FLAT_P * y_cs * esz + (g_next2 ? (size_t)FLAT_P * g2_cs * esz : 0) + 3 * 64 * sizeof(float);
+            if (!loss) {
+                if (dy_dtype == P4C_F32) {
+                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<float, false, false>, (int)smem));
+                    hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<float, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
+                                       g_next, g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,
+                                       std, interior_mask, force_border, weights, num_interior, masked_count, kind, (float*)dy, y_cs, dprev,
+                                       dprev_bs, N, F, keep_prev);
+                } else {
+                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<bf16, false, false>, (int)smem));
+                    hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<bf16, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
+                                       g_next, g_next_bs, (const bf16*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,
+                                       std, interior_mask, force_border, weights, num_interior, masked_count, kind, (bf16*)dy, y_cs, dprev,
+                                       dprev_bs, N, F, keep_prev);
+                }
+                P4C_CHECK_LAUNCH("p4c_ar_update_next_bwd(flat)");
+                return P4C_OK;
+            }
             if (dy_dtype == P4C_F32) {
                 P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<float, false>, (int)smem));
                 hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<float, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream), g_next,
@@ -1825,18 +1989,43 @@ extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, co
     const int FP = pow2_ge64(y_cs), iters = (y_cs + FP - 1) / FP;
     P4C_CHECK_ARG(iters <= LOSS_MAX_ITERS, "p4c_ar_update_loss_bwd: y_cs too large");
     const int nblk = loss_blocks(N, 64 / FP, B);
-#define P4C_LAUNCH_BWD(TY)                                                                                              \
-    hipLaunchKernelGGL((ar_update_loss_bwd_kernel<TY, TY>), dim3(nblk, B), dim3(256), 0, as_stream(stream), g_next,       \
+#define P4C_LAUNCH_BWD(TY, LOSSF)                                                                                       \
+    hipLaunchKernelGGL((ar_update_loss_bwd_kernel<TY, TY, LOSSF>), dim3(nblk, B), dim3(256), 0, as_stream(stream), g_next, \
                        g_next_bs, (const TY*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,    \
                        std, interior_mask, force_border, weights, num_interior, masked_count, kind, mask_mode, (TY*)dy, \
                        y_cs, dprev, dprev_bs, N, F, keep_prev, FP, iters)
-    if (dy_dtype == P4C_F32)
-        P4C_LAUNCH_BWD(float);
-    else if (dy_dtype == P4C_BF16)
-        P4C_LAUNCH_BWD(bf16);
-    else
-        return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_bwd: bad dtype %d", dy_dtype);
+    if (dy_dtype != P4C_F32 && dy_dtype != P4C_BF16) return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_bwd: bad dtype %d", dy_dtype);
+    if (!loss) {
+        if (dy_dtype == P4C_F32) P4C_LAUNCH_BWD(float, false); else P4C_LAUNCH_BWD(bf16, false);
+        P4C_CHECK_LAUNCH("p4c_ar_update_next_bwd");
+        return P4C_OK;
+    }
+    if (dy_dtype == P4C_F32) P4C_LAUNCH_BWD(float, true); else P4C_LAUNCH_BWD(bf16, true);
 #undef P4C_LAUNCH_BWD
     P4C_CHECK_LAUNCH("p4c_ar_update_loss_bwd");
     return P4C_OK;
+}
+
+extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype,
+                                      int g2_cs, const float* gloss, int64_t gloss_stride, const float* new_state,
+                                      int64_t new_bs, const float* target, int64_t tgt_bs, const float* std,
+                                      const float* interior_mask, int force_border, const float* weights,
+                                      float num_interior, const int32_t* masked_count, int kind, int mask_mode,
+                                      void* dy, int dy_dtype, int y_cs, float* dprev, int64_t dprev_bs, int B,
+                                      int64_t N, int F, float keep_prev, p4c_stream_t stream) {
+    return ar_update_loss_bwd_impl(g_next, g_next_bs, g_next2, g2_dtype, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs, std,
+                                   interior_mask, force_border, weights, num_interior, masked_count, kind, mask_mode, dy, dy_dtype, y_cs,
+                                   dprev, dprev_bs, B, N, F, keep_prev, stream, true);
+}
+
+// Backward of the free step (p4c_ar_update_next / p4c_out_conv_update_fwd): with g = g_next + g_next2 the gradient arriving at the
+// step's new state, dy = (g * interior) * std in the dtype of dy (channels F .. y_cs - 1 zero) and dprev = (g * interior) * keep_prev,
+// without the interior factor when no border was forced.  p4c_ar_update_loss_bwd with a NULL loss gradient is NOT this: it still
+// reads the new state and the target (0 * d loss / d pred, NaN where either holds one), which a free step does not keep.
+extern "C" int p4c_ar_update_next_bwd(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype, int g2_cs,
+                                      const float* std, const float* interior_mask, int force_border, void* dy, int dy_dtype, int y_cs,
+                                      float* dprev, int64_t dprev_bs, int B, int64_t N, int F, float keep_prev, p4c_stream_t stream) {
+    return ar_update_loss_bwd_impl(g_next, g_next_bs, g_next2, g2_dtype, g2_cs, nullptr, 0, nullptr, 0, nullptr, 0, std, interior_mask,
+                                   force_border, nullptr, 1.0f, nullptr, P4C_LOSS_MSE, P4C_MASK_NONE, dy, dy_dtype, y_cs, dprev, dprev_bs, B,
+                                   N, F, keep_prev, stream, false);
 }

@@ -146,7 +146,7 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         self.act_dtype = torch.float32 if act == "f32" else torch.bfloat16  # dtype of x / y / dy / dx handed to the plan
         self.timed_entry_points = ("p4c_halfunet_forward", "p4c_halfunet_backward", "p4c_build_x",
                                    "p4c_ar_update_loss_fwd", "p4c_ar_update_loss_fwd_next", "p4c_ar_update_loss_bwd",
-                                   "p4c_sum_state_grads")
+                                   "p4c_sum_state_grads", "p4c_ar_update_next", "p4c_out_conv_update_fwd", "p4c_ar_update_next_bwd")
 
         self.use_ghost = bool(settings.use_ghost)
         if self.module_path:
@@ -474,7 +474,7 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)
 
     # ---------------------------------------------------------------- native rollout (one autograd node)
-    def native_rollout(self, lm, batch, std, mean, border_flat, interior_flat, force_border):
+    def native_rollout(self, lm, batch, std, mean, border_flat, interior_flat, force_border, num_inter_steps=1, phase="train"):
         """
         Whole training/validation rollout of AutoRegressiveLightning._common_step (lightning.py:565-662) as ONE
         autograd node: per AR step K1 (build x, padded layout) -> HalfUNet plan -> fused state update + border
@@ -484,17 +484,24 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         path, the matching block of the input gradient of the next T_in steps) in HIP.  Returns the (B,T,*S,F) prediction, with ``fused_loss`` (B,T) attached
         when the configured loss is a single WeightedLoss.  Returns None when the configuration is not covered
         (the caller then takes the generic per-op path).
+        ``num_inter_steps`` = K >= 2 (scaled_ar): K model calls per target step; the first K - 1 are FREE steps (border forced to the
+        target, no loss, state kept in scratch: p4c_ar_update_next / p4c_out_conv_update_fwd), the K-th is the loss step above.
+        ``phase == "inference"``: a forward-only forecast of free steps without border forcing (``_native_forecast``), a plain tensor.
         """
         from .losses import WeightedLoss
 
         if batch.inputs.tensor.dim() != 5:
             return None
+        if phase == "inference":
+            return self._native_forecast(lm, batch, std, mean, int(num_inter_steps))
         T_in, F = batch.inputs.tensor.shape[1], batch.inputs.tensor.shape[-1]
         if T_in > 1 and (T_in * F + lm.grid_static_features.shape[-1] + batch.forcing.tensor.shape[-1] + int(lm.mask_on_nan)
                          != self.in_channels):
             return None
         if any(self.padding_for(batch.inputs.tensor.shape[2], batch.inputs.tensor.shape[3])):
             return None   # auto-padded grids take the generic per-step path (forward pads and crops around the plan)
+        if num_inter_steps > 1 and T_in > 1:
+            return None   # (AutoRegressiveLightning raises for this pair before it gets here)
         members = getattr(lm.loss, "losses", [])
         if len(members) != 1 or not isinstance(members[0][0], WeightedLoss) or not members[0][0].fused_capable:
             return None
@@ -504,13 +511,97 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         self._running = self._running_stats(batch.inputs.tensor.device)
         training = self.training
         if training and self._settings.norm == "batch":
-            torch._foreach_add_([nb.num_batches_tracked for nb in self._norms], batch.num_pred_steps)
+            torch._foreach_add_([nb.num_batches_tracked for nb in self._norms], batch.num_pred_steps * int(num_inter_steps))
         pred, loss = _NativeRolloutFn.apply(
             self, lm, batch.inputs.tensor, batch.forcing.tensor, batch.outputs.tensor,
             lm.grid_static_features[: batch.batch_size], std, mean, border_flat, interior_flat, bool(force_border),
-            weights, float(wl.num_interior), wl.kind, mode, training, torch.is_grad_enabled(), *self._ordered_params())
+            weights, float(wl.num_interior), wl.kind, mode, training, torch.is_grad_enabled(), int(num_inter_steps),
+            *self._ordered_params())
         pred.fused_loss = loss * wl_weight
         return pred
+
+    def _native_forecast(self, lm, batch, std, mean, K):
+        """Forward-only native forecast (phase "inference", lightning.py:565-662 with ``inference``): T * K model calls, every one a
+        free step without border forcing (:627) -- no autograd node, one ``saved`` buffer for all calls, states written straight into
+        the (B,T,H,W,F) result (intermediary states of K >= 2 through two scratch buffers).  T comes from the forcing tensor
+        (``batch.outputs`` is None).  T_in >= 2: the window buffer of the training rollout with p4c_build_x per call.  Returns None
+        where ``native_rollout`` does (padded grids, channel mismatch)."""
+        inputs, forcing = batch.inputs.tensor, batch.forcing.tensor
+        if forcing.dim() != 5:
+            return None
+        B, T_in, H, W, F = inputs.shape
+        T = forcing.shape[1]
+        statics = lm.grid_static_features[: batch.batch_size]
+        Fs, Ff = statics.shape[-1], forcing.shape[-1]
+        mask_on_nan = int(bool(lm.mask_on_nan))
+        if T_in * F + Fs + Ff + mask_on_nan != self.in_channels or F > self.out_channels or (K > 1 and T_in > 1):
+            return None
+        if any(self.padding_for(H, W)):
+            return None
+        L.require_cuda(inputs, forcing)
+        dev = inputs.device
+        N = H * W
+        with torch.no_grad():
+            self._running = self._running_stats(dev)
+            training = self.training
+            if training and self._settings.norm == "batch":
+                torch._foreach_add_([nb.num_batches_tracked for nb in self._norms], T * K)
+            inputs, forcing = inputs.float().contiguous(), forcing.float().contiguous()
+            st = statics.float()
+            sbs = 0 if st.stride(0) == 0 else N * Fs
+            st = st[0].contiguous() if sbs == 0 else st.contiguous()
+            desc = self._desc(B, H, W)
+            flat = self._flat_params()
+            saved_bytes, scratch = self._workspaces(desc, dev)
+            cpad = self.cin_pad
+            adt, acode = self.act_dtype, L.dtype_code(self.act_dtype)
+            stream = L.stream(dev)
+            L.call("p4c_halfunet_prepare_weights", ctypes.byref(desc), L.ptr(flat), L.ptr(scratch), stream)
+            desc.weights_prepared = 1
+            feed, v4_next, flat_next = _step_paths(self, T_in, N, F, Fs, mask_on_nan)
+            fuse_next = feed and (v4_next or flat_next)
+            fused_tail = _fused_tail(self, v4_next, flat_next, F, mask_on_nan)
+            if fused_tail:
+                desc.skip_out_conv = 1
+            if feed:
+                pred, sbs_state = torch.empty(B, T, H, W, F, dtype=torch.float32, device=dev), T * N * F
+                states = None
+            else:
+                states = torch.empty(B, T_in + T, H, W, F, dtype=torch.float32, device=dev)
+                states[:, :T_in].copy_(inputs)
+                pred, sbs_state = states[:, T_in:], (T_in + T) * N * F
+            inter = [torch.empty(B, H, W, F, dtype=torch.float32, device=dev) for _ in range(min(2, K - 1))]
+            saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+            y = None if fused_tail else torch.empty(B, H, W, NF, dtype=adt, device=dev)
+            xbuf = [torch.empty(B, H, W, cpad, dtype=adt, device=dev) for _ in range(2 if fuse_next else 1)]
+            x_next = None
+            ncalls = T * K
+            for c in range(ncalls):
+                i, k = divmod(c, K)
+                if not feed:
+                    prev, sbs_prev = states[:, i + T_in - 1], sbs_state
+                elif c == 0:
+                    prev, sbs_prev = inputs[:, 0], T_in * N * F
+                elif k == 0:
+                    prev, sbs_prev = pred[:, i - 1], sbs_state
+                else:
+                    prev, sbs_prev = inter[(k - 1) % 2], N * F
+                new, sbs_new = (pred[:, i], sbs_state) if k == K - 1 else (inter[k % 2], N * F)
+                if x_next is not None:
+                    x = x_next
+                else:
+                    x = xbuf[c % len(xbuf)]
+                    win, sbs_win = (prev, sbs_prev) if feed else (states[:, i], sbs_state)
+                    L.call("p4c_build_x", L.ptr(win), sbs_win, N * F, L.ptr(st), sbs, L.ptr(forcing[:, i]), T * N * Ff,
+                           L.ptr(x), acode, cpad, B, T_in, N, F, Fs, Ff, mask_on_nan, 0, stream)
+                L.call("p4c_halfunet_forward", ctypes.byref(desc), L.ptr(x), L.ptr(flat), L.ptr(self._running), L.ptr(y),
+                       L.ptr(saved), L.ptr(scratch), int(training), stream)
+                # the next call's input: the same forcing step for an intermediary call, the next one after the K-th
+                x_next = xbuf[(c + 1) % 2] if (fuse_next and c + 1 < ncalls) else None
+                nf = forcing[:, i if k < K - 1 else i + 1] if x_next is not None else None
+                _free_step(self, desc, flat, saved, y, fused_tail, prev, sbs_prev, None, 0, std, mean, None, None, new, sbs_new,
+                           mask_on_nan, B, N, F, x_next, cpad, st, sbs, Fs, nf, T * N * Ff, Ff, stream)
+            return pred if feed else pred.contiguous()
 
     def roofline(self, ktimes, B, H, W):
         """bench.py: achieved rate of the dominant kernel (conv 3x3 64->64 at full resolution) from the per-launch
@@ -619,10 +710,56 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         return out
 
 
+def _step_paths(model, T_in, N, F, Fs, mask_on_nan):
+    """(feed, v4_next, flat_next): whether the AR step's kernel also writes the next network input ("feed next step": one input
+    state, otherwise p4c_build_x builds the window), and which of the step kernels' two fast paths the shape takes -- the conditions
+    of csrc/losses.hip, stated once for the training rollout and the forecast."""
+    cpad = model.cin_pad
+    feed = T_in == 1
+    lanes = 1
+    while lanes < F // 4:
+        lanes *= 2  # lanes per grid point of the 16-byte update kernel; each also owns one tail quad of x_next
+    v4_next = ((not mask_on_nan) and F % 4 == 0 and F <= 64
+               and (not feed or (Fs % 4 == 0 and cpad % 4 == 0 and cpad // 4 - F // 4 <= lanes)))
+    # any other feature count (the shipped Titan configuration has 21 features): the flat kernels of csrc/losses.hip -- (N, F)
+    # arrays streamed flat, the network's row tensors through LDS tiles -- take the same fused step
+    esz = 2 if model.act_dtype == torch.bfloat16 else 4
+    flat_next = ((not mask_on_nan) and F <= 64 and (N * F) % 4 == 0 and (cpad * esz) % 16 == 0 and cpad <= 256
+                 and L.diag_switch("P4C_NO_FLAT_STEP") != "1")
+    return feed, v4_next, flat_next
+
+
+def _fused_tail(model, v4_next, flat_next, F, mask_on_nan):
+    """bf16 flavour: the network's 1x1 output convolution runs INSIDE the AR step's kernel (p4c_out_conv_update_loss_fwd /
+    p4c_out_conv_update_fwd: y is never written and read back, one launch less per AR step; same new state bit for bit;
+    P4C_FUSED_TAIL=0: the two-kernel route).  (Feature counts off the 16-byte grid: the flat kernel takes the convolution as its
+    front end.)"""
+    return (model.act_dtype == torch.bfloat16 and (v4_next or (flat_next and F % 4 != 0)) and not mask_on_nan
+            and model.out_channels >= F and L.diag_switch("P4C_FUSED_TAIL") != "0")
+
+
+def _free_step(model, desc, flat, saved, y, fused_tail, prev, sbs_prev, target, sbs_tgt, std, mean, border, interior, new, sbs_new,
+               nan_to_num, B, N, F, x_next, cpad, st, sbs, Fs, forcing_next, sbs_forc, Ff, stream):
+    """One AR step without a loss term (an intermediary call of num_inter_steps >= 2, an inference call): the update, the border
+    forcing where ``target`` / ``border`` / ``interior`` are given, optionally the next network input -- behind the fused 1x1 output
+    convolution where the fused tail applies."""
+    if fused_tail:
+        ta, tsc, tsh, tw = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        L.call("p4c_halfunet_tail", ctypes.byref(desc), L.ptr(flat), L.ptr(saved), ctypes.byref(ta), ctypes.byref(tsc),
+               ctypes.byref(tsh), ctypes.byref(tw))
+        L.call("p4c_out_conv_update_fwd", ta, tsc, tsh, tw, model.out_channels, L.ptr(prev), sbs_prev, L.ptr(target), sbs_tgt,
+               L.ptr(std), L.ptr(mean), L.ptr(border), L.ptr(interior), L.ptr(new), sbs_new, B, N, F, 1.0,
+               L.ptr(x_next), cpad, L.ptr(st), sbs, Fs, L.ptr(forcing_next), sbs_forc, Ff, stream)
+    else:
+        L.call("p4c_ar_update_next", L.ptr(prev), sbs_prev, L.ptr(y), L.dtype_code(model.act_dtype), NF, L.ptr(target), sbs_tgt,
+               L.ptr(std), L.ptr(mean), L.ptr(border), L.ptr(interior), L.ptr(new), sbs_new, int(nan_to_num), B, N, F, 1.0,
+               L.ptr(x_next), cpad, L.ptr(st), sbs, Fs, L.ptr(forcing_next), sbs_forc, Ff, stream)
+
+
 class _NativeRolloutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, lm, inputs, forcing, outputs, statics, std, mean, border_flat, interior_flat, force_border,
-                weights, num_interior, kind, mask_mode, training, keep_saved, *params):
+                weights, num_interior, kind, mask_mode, training, keep_saved, K, *params):
         L.require_cuda(inputs, forcing, outputs)
         dev = inputs.device
         B, T = outputs.shape[0], outputs.shape[1]
@@ -669,17 +806,7 @@ class _NativeRolloutFn(torch.autograd.Function):
         # "feed next step" fused: the update kernel of step i also writes step i+1's network input (new state | statics |
         # next forcing | padding), so only step 0 runs p4c_build_x.  (The NaN-mask input channel needs p4c_build_x.)
         # (T_in >= 2: the next input is a window of several states, built by p4c_build_x; the update kernels run without x_next)
-        feed = T_in == 1
-        lanes = 1
-        while lanes < F // 4:
-            lanes *= 2  # lanes per grid point of the 16-byte update kernel; each also owns one tail quad of x_next
-        v4_next = ((not mask_on_nan) and F % 4 == 0 and F <= 64
-                   and (not feed or (Fs % 4 == 0 and cpad % 4 == 0 and cpad // 4 - F // 4 <= lanes)))
-        # any other feature count (the shipped Titan configuration has 21 features): the flat kernels of csrc/losses.hip -- (N, F)
-        # arrays streamed flat, the network's row tensors through LDS tiles -- take the same fused step
-        esz = 2 if adt == torch.bfloat16 else 4
-        flat_next = ((not mask_on_nan) and F <= 64 and (N * F) % 4 == 0 and (cpad * esz) % 16 == 0 and cpad <= 256
-                     and L.diag_switch("P4C_NO_FLAT_STEP") != "1")
+        feed, v4_next, flat_next = _step_paths(model, T_in, N, F, Fs, mask_on_nan)
         step_capable = v4_next or flat_next
         fuse_next = feed and step_capable
         x_next = None
@@ -688,20 +815,26 @@ class _NativeRolloutFn(torch.autograd.Function):
         save_lg = (keep_saved and adt == torch.bfloat16 and step_capable and mask_mode == L.MASK_NONE
                    and L.diag_switch("P4C_SAVE_LOSS_GRAD") != "0")
         lgrads = torch.empty(T, B, N, F, dtype=torch.bfloat16, device=dev) if save_lg else None
-        # bf16 flavour: the network's 1x1 output convolution runs INSIDE the AR step's kernel (p4c_out_conv_update_loss_fwd: y is
-        # never written and read back, one launch less per AR step; same new state bit for bit; P4C_FUSED_TAIL=0: the two-kernel route)
-        # (feature counts off the 16-byte grid: the flat kernel takes the convolution as its front end)
-        fused_tail = (adt == torch.bfloat16 and (v4_next or (flat_next and F % 4 != 0)) and mask_mode == L.MASK_NONE
-                      and model.out_channels >= F and L.diag_switch("P4C_FUSED_TAIL") != "0")
+        fused_tail = _fused_tail(model, v4_next, flat_next, F, mask_on_nan)
         desc_fwd = desc
         if fused_tail:
             desc_fwd = HalfUNetDesc.from_buffer_copy(desc)
             desc_fwd.skip_out_conv = 1
-        for i in range(T):
-            if feed:
-                prev, sbs_prev = (inputs[:, 0], sbs_input) if i == 0 else (states[:, i], sbs_state)
-            else:
+        # The schedule: T * K model calls.  Call (i, k) with k < K - 1 is a FREE step -- forced to outputs[:, i] at the border, no loss,
+        # its state not part of the prediction (lightning.py:583-658): it goes to a scratch ring of two buffers, and its next input
+        # takes forcing[:, i] again (_next_x(batch, prev_states, i) for every k); call (i, K - 1) is the loss step, writes prediction
+        # slot i, and its next input takes forcing[:, i + 1].  Only activations (xs / saveds) are kept per call for the reverse sweep.
+        inter = [torch.empty(B, H, W, F, dtype=torch.float32, device=dev) for _ in range(min(2, K - 1))]
+        for c in range(T * K):
+            i, k = divmod(c, K)
+            if not feed:
                 prev, sbs_prev = states[:, i + T_in - 1], sbs_state
+            elif c == 0:
+                prev, sbs_prev = inputs[:, 0], sbs_input
+            elif k == 0:
+                prev, sbs_prev = states[:, i], sbs_state
+            else:
+                prev, sbs_prev = inter[(k - 1) % 2], N * F
             if x_next is not None:
                 x = x_next
             else:
@@ -713,6 +846,16 @@ class _NativeRolloutFn(torch.autograd.Function):
                 saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
             L.call("p4c_halfunet_forward", ctypes.byref(desc_fwd), L.ptr(x), L.ptr(flat), L.ptr(model._running),
                    None if fused_tail else L.ptr(y), L.ptr(saved), L.ptr(scratch), int(training), stream)
+            if k < K - 1:
+                x_next = torch.empty(B, H, W, cpad, dtype=adt, device=dev) if fuse_next else None
+                _free_step(model, desc_fwd, flat, saved, y, fused_tail, prev, sbs_prev, outputs[:, i] if force_border else None,
+                           T * N * F, std, mean, border_flat if force_border else None, interior_flat if force_border else None,
+                           inter[k % 2], N * F, mask_on_nan, B, N, F, x_next, cpad, st, sbs, Fs,
+                           forcing[:, i] if fuse_next else None, T * N * Ff, Ff, stream)
+                if keep_saved:
+                    xs.append(x)
+                    saveds.append(saved)
+                continue
             if fused_tail:
                 last = i + 1 == T or not feed
                 x_next = None if last else torch.empty(B, H, W, cpad, dtype=adt, device=dev)
@@ -750,7 +893,7 @@ class _NativeRolloutFn(torch.autograd.Function):
                 saveds.append(saved)
         ctx.model, ctx.desc, ctx.training = model, desc, training
         ctx.meta = (B, T, H, W, F, force_border, num_interior, kind, mask_mode)
-        ctx.T_in = T_in
+        ctx.T_in, ctx.K = T_in, K
         ctx.tensors = (states, outputs, std, interior_flat, weights, count, xs, saveds)
         ctx.lgrads = lgrads
         ctx.set_materialize_grads(False)
@@ -783,7 +926,7 @@ class _NativeRolloutFn(torch.autograd.Function):
         # full-resolution ones left over at the end of AR step i's backward then run beside the HBM-bound head of step i-1's
         # chain instead of alone (P4C_DEFER_JOIN=0: join after every step, the round-2 behaviour).  xs / saveds stay referenced
         # until the join below -- the side stream reads them.
-        defer = T > 1 and L.diag_switch("P4C_DEFER_JOIN") != "0"
+        defer = T * ctx.K > 1 and L.diag_switch("P4C_DEFER_JOIN") != "0"
         if defer:
             L.call("p4c_side_stream_defer", 1)
         ok = False
@@ -817,41 +960,49 @@ class _NativeRolloutFn(torch.autograd.Function):
         sbs_state = (T + 1) * N * F
         adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
         have_next = False
-        for i in range(T - 1, -1, -1):
+        K = ctx.K
+        # all T * K model calls in reverse; call c = i * K + k is a free step for k < K - 1 (its adjoint reads nothing of the forward:
+        # p4c_ar_update_next_bwd; it has no loss gradient, no prediction slot and nothing saved)
+        for c in range(T * K - 1, -1, -1):
+            i, k = divmod(c, K)
             g_next = dprev if have_next else None
-            if g_pred is not None:  # somebody differentiates through the prediction itself: add its slice
+            if g_pred is not None and k == K - 1:  # somebody differentiates through the prediction itself: add its slice
                 if g_next is None:
                     dprev.copy_(g_pred[:, i])
                 else:
                     dprev.add_(g_pred[:, i])
                 g_next = dprev
-            if ctx.lgrads is not None:
+            if k < K - 1:
+                L.call("p4c_ar_update_next_bwd", L.ptr(g_next), N * F, L.ptr(dx if have_next else None), acode, NF, L.ptr(std),
+                       L.ptr(interior_flat if force_border else None), int(force_border), L.ptr(dy), acode, NF,
+                       L.ptr(dprev) if c > 0 else None, N * F, B, N, F, 1.0, stream)
+            elif ctx.lgrads is not None:
                 L.call("p4c_ar_update_loss_bwd_saved", L.ptr(g_next), N * F, L.ptr(dx if have_next else None), acode, NF,
                        L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(ctx.lgrads[i]), N * F, L.ptr(std), L.ptr(interior_flat),
                        int(force_border), L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF,
-                       L.ptr(dprev) if i > 0 else None, N * F, B, N, F, 1.0, stream)
+                       L.ptr(dprev) if c > 0 else None, N * F, B, N, F, 1.0, stream)
             else:
                 L.call("p4c_ar_update_loss_bwd", L.ptr(g_next), N * F, L.ptr(dx if have_next else None), acode, NF,
                        L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(states[:, i + 1]), sbs_state, L.ptr(outputs[:, i]),
                        T * N * F, L.ptr(std), L.ptr(interior_flat), int(force_border), L.ptr(weights), num_interior,
-                       L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF, L.ptr(dprev) if i > 0 else None, N * F, B, N, F,
+                       L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF, L.ptr(dprev) if c > 0 else None, N * F, B, N, F,
                        1.0, stream)
-            d = desc if i > 0 else desc0
-            L.call("p4c_halfunet_backward", ctypes.byref(d), L.ptr(xs[i]), L.ptr(flat), L.ptr(dy),
-                   L.ptr(dx) if i > 0 else None, L.ptr(gflat), L.ptr(saveds[i]), L.ptr(scratch), int(ctx.training), stream)
+            d = desc if c > 0 else desc0
+            L.call("p4c_halfunet_backward", ctypes.byref(d), L.ptr(xs[c]), L.ptr(flat), L.ptr(dy),
+                   L.ptr(dx) if c > 0 else None, L.ptr(gflat), L.ptr(saveds[c]), L.ptr(scratch), int(ctx.training), stream)
             have_next = True
             if not defer:
-                xs[i] = None
-                saveds[i] = None  # release the step's activations as soon as its backward is enqueued
+                xs[c] = None
+                saveds[c] = None  # release the step's activations as soon as its backward is enqueued
         if defer:
             L.call("p4c_side_stream_join", stream)
-            for i in range(T):
-                xs[i] = None
-                saveds[i] = None
+            for c in range(T * K):
+                xs[c] = None
+                saveds[c] = None
         if target is not None:  # already accumulated into param.grad
-            return (None,) * (17 + len(model._param_slices))
+            return (None,) * (18 + len(model._param_slices))
         grads = tuple(gflat[o : o + n].view(s) for (o, n, s) in model._param_slices)
-        return (None,) * 17 + grads
+        return (None,) * 18 + grads
 
     @staticmethod
     def _sweep_window(ctx, g_pred, gl, dy, dprev, gflat, flat, scratch, desc, desc0, stream, target, defer):
@@ -915,6 +1066,6 @@ class _NativeRolloutFn(torch.autograd.Function):
                 xs[i] = None
                 saveds[i] = None
         if target is not None:
-            return (None,) * (17 + len(model._param_slices))
+            return (None,) * (18 + len(model._param_slices))
         grads = tuple(gflat[o : o + n].view(s) for (o, n, s) in model._param_slices)
-        return (None,) * 17 + grads
+        return (None,) * 18 + grads

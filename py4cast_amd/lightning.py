@@ -393,8 +393,16 @@ class AutoRegressiveLightning(_Base):
             )
 
         native = getattr(self.model, "native_rollout", None) if getattr(self, "use_native_rollout", True) else None
-        if native is not None and not ds and self.mask_ratio == 0 and num_inter_steps == 1 and not inference:
-            prediction = native(self, batch, std, mean, border_flat, interior_flat, force_border)
+        if native is not None and not ds and self.mask_ratio == 0:
+            # one route for the whole schedule: num_inter_steps model calls per target step, and the forward-only forecast of
+            # phase "inference" (no border forcing, no loss, no autograd node)
+            if num_inter_steps == 1 and not inference:
+                prediction = native(self, batch, std, mean, border_flat, interior_flat, force_border)
+            else:
+                prediction = native(self, batch, std, mean, border_flat, interior_flat, force_border,
+                                    num_inter_steps=num_inter_steps, phase=phase)
+            if prediction is not None and inference:
+                return NamedTensor(prediction.type(self.output_dtype), self.output_dim_names, self.output_feature_names), batch.outputs
             if prediction is not None:
                 pred_out = NamedTensor.new_like(prediction.type_as(batch.outputs.tensor), batch.outputs)
                 pred_out.fused_loss = getattr(prediction, "fused_loss", None)
