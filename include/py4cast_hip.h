@@ -425,6 +425,33 @@ int p4c_conv_stat_tiles_ks(int compute, int storage, int CI, int ks, int B, int 
 /* which kernel p4c_conv_fwd launches for a 64-filter convolution of this shape: 2 = row-streaming kernel (csrc/conv_rows.hip),
  * 1 = tile-ring kernel, 0 = generic tiled kernel.  (bench.py names the roofline kernel with it.) */
 int p4c_conv_kernel_kind(int compute, int storage, int CI, int ks, int B, int H, int W);
+/* The latency-oriented 3x3 convolution 64 -> 64 on bf16 maps of the HalfUNet plan's coarse levels (csrc/conv_small.hip): one tile per
+ * workgroup, ONE statistics slot [2][64] per workgroup (p4c_conv_small_stat_slots per sample), the stored map bit-identical to
+ * p4c_conv_fwd's.  p4c_conv_small_ok: 1 when the plan routes this shape to it (a measured threshold; 0 with P4C_SMALL_CONV=0 in the
+ * diagnostic library).  p4c_conv_small_fwd runs the kernel on ANY shape it can address, routed or not: the arguments of p4c_conv_fwd
+ * (compute = storage = P4C_BF16, CI = 64, ks = 3, out_cs = 64, m_blocks = 1, no bias; input plain, or relu(in * scale + shift) with
+ * in_relu = 1), then the eight NormBwdCoef pointers of the data-gradient load mode (not implemented: all NULL), then the in-kernel
+ * BatchNorm finalize -- fin_ticket (a zeroed word; NULL = leave the slots only), gamma, beta, eps, momentum, the running statistics
+ * (or NULL) and the (B,64) outputs scale / shift / mean / rstd.  Last, the consumer-side finish of the plan's coarse levels: pre_slots
+ * (or NULL) = the statistics slots a launch of this kernel at the SAME shape left unfinished (at most 256, not stat_partial), with
+ * in_relu = 1 and no in_scale / in_shift -- every workgroup combines them in the in-kernel finalize's order, normalises its input with
+ * the result, and workgroup 0 writes pre_scale / pre_shift / pre_mean / pre_rstd (B,64) and updates pre_running_* (same eps /
+ * momentum). */
+int p4c_conv_small_ok(int storage, int B, int H, int W);
+int p4c_conv_small_stat_slots(int B, int H, int W);
+int p4c_conv_small_fwd(const void* in, int compute, int storage, int CI, const void* wprep, int ks, const float* in_scale,
+                       const float* in_shift, int in_relu, const float* bias, void* out, int out_cs, float* stat_partial, int B, int H,
+                       int W, int m_blocks, p4c_stream_t stream, const void* nb_y, const float* nb_gamma, const float* nb_scale,
+                       const float* nb_shift, const float* nb_rstd, const float* nb_mean, const float* nb_k1, const float* nb_k2,
+                       unsigned int* fin_ticket, const float* fin_gamma, const float* fin_beta, float eps, float momentum,
+                       float* running_mean, float* running_var, float* scale, float* shift, float* mean, float* rstd,
+                       const float* pre_slots, const float* pre_gamma, const float* pre_beta, float* pre_running_mean,
+                       float* pre_running_var, float* pre_scale, float* pre_shift, float* pre_mean, float* pre_rstd);
+/* The plan's statistics finalize on a caller's slots [B][slots_per_sample][2][64]: mode 0 BatchNorm (training; running statistics
+ * updated when given), mode 1 GroupNorm.  hw = H * W; outputs (B,64) each. */
+int p4c_norm_finalize(const float* partial, int slots_per_sample, int B, int64_t hw, int mode, int groups, const float* gamma,
+                      const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* scale, float* shift,
+                      float* mean, float* rstd, p4c_stream_t stream);
 int p4c_conv_wgrad(const void* in, int compute, int storage, int CI_pad, int ks, const float* in_scale, const float* in_shift,
                    int in_relu, const void* dout, int CO, int CI, float* grad, void* workspace, int B, int H, int W,
                    p4c_stream_t stream);

@@ -25,6 +25,8 @@ constexpr int NCONV = 12;    // 3x3 convs: enc k conv j -> 2(k-1)+j-1 ; decoder 
 // 2*NCONV / 2*NCONV + 1 = 1x1 output conv forward / data gradient
 constexpr int NWSLOT = 2 * NCONV + 3;   // forward + data-gradient images of the 3x3 blocks, the two of the 1x1 output conv, the first conv's 64-channel row image
 
+constexpr int64_t HANDOFF_SLOT_FLOATS = 256 * 128;   // statp: a hand-off producer's statistics slots lie behind its consumer's own (at most 256 each; conv_block_fwd)
+
 struct Layout {
     int esz;                  // bytes per activation element
     int64_t n[NLEV];          // B*Hk*Wk per level
@@ -152,6 +154,7 @@ void make_layout(const p4c_halfunet_desc& d, Layout& L) {
             const int64_t st = first_conv_tail_slots(d.B, d.H, d.W);
             if (st > slots) slots = st;
         }
+        if ((int64_t)d.B * slots * 128 < 2 * HANDOFF_SLOT_FLOATS) slots = (2 * HANDOFF_SLOT_FLOATS / 128 + d.B - 1) / d.B;   // (conv_block_fwd: hand-off)
         L.statp = off; off += (int64_t)d.B * slots * 128;
     }
     // per-workgroup weight-gradient partials, one region per convolution (NCONV: the 1x1 output convolution): the reductions of a
@@ -238,8 +241,17 @@ int prepare_weights(const p4c_halfunet_desc& d, const WS& ws, const float* param
 }
 
 // conv3x3 forward + statistics + normalisation parameters of its output
+// handoff (the two convolutions of a coarse level on the latency-oriented kernel, conv_small.hip): 1 = this block leaves its statistics
+// slots and ends, its consumer finishes them; 2 = this block finishes the statistics of block i - 1 in its prologue (and publishes
+// that block's normalisation arrays and running statistics for the backward)
+bool small_handoff(const p4c_halfunet_desc& d, const Layout& L, int lev, int training) {
+    const char* ie = diag_env("P4C_NO_INKERNEL_FINALIZE");
+    return lev > 0 && training && d.norm == 0 && d.compute == P4C_BF16 && !(ie && ie[0] == '1') &&
+           conv_small_handoff_ok(d.dtype, d.B, L.Hk[lev], L.Wk[lev]);
+}
+
 int conv_block_fwd(const p4c_halfunet_desc& d, const WS& ws, int i, const void* in, const Norm* in_norm, const float* params,
-                   float* running, int training, hipStream_t st) {
+                   float* running, int training, hipStream_t st, int handoff = 0) {
     const Layout& L = ws.L;
     const int lev = conv_level(i), H = L.Hk[lev], W = L.Wk[lev];
     void* wp = wslot(ws, i);
@@ -264,7 +276,27 @@ int conv_block_fwd(const p4c_halfunet_desc& d, const WS& ws, int i, const void* 
                        nm.scale, nm.shift, nm.mean, nm.rstd, (double)d.B * H * W, d.eps, d.momentum, d.B};
     }
     int ntiles = stat_tiles(d.compute, d.dtype, conv_cin_pad(d, i), d.B, H, W);
-    if (i == 0 && !in_norm && first_conv_split_ok(d.compute, d.dtype, d.cin, d.cin_pad, d.B, H, W)) {
+    // the coarse levels: the latency-oriented kernel (conv_small.hip: one tile and ONE statistics slot per workgroup; the stored map
+    // is bit-identical to the row / ring kernel's).  It finishes BatchNorm itself like they do; GroupNorm and eval mode go through
+    // the norm_finalize / norm_eval launches below, on its slot count.
+    const bool small = d.compute == P4C_BF16 && conv_cin_pad(d, i) == NF && conv_small_ok(d.dtype, d.B, H, W);
+    if (handoff && !small) return fail(P4C_ERR_INVALID, "halfunet: statistics hand-off on a block the small kernel does not run");
+    if (small) {
+        float* other = statp ? statp + HANDOFF_SLOT_FLOATS : nullptr;
+        BatchFin pre{};
+        if (handoff == 2) {
+            Norm pn = norm_at(ws, i - 1, d.B);
+            float* prm = running ? running + (int64_t)(i - 1) * 128 : nullptr;
+            pre = BatchFin{other, nullptr, params + L.gamma[i - 1], params + L.beta[i - 1], prm, prm ? prm + 64 : nullptr,
+                           pn.scale, pn.shift, pn.mean, pn.rstd, (double)d.B * H * W, d.eps, d.momentum, d.B};
+        }
+        const bool given = in_norm && handoff != 2;   // (hand-off: scale / shift come from the producer's slots, not from memory)
+        P4C_TRY(launch_conv3x3_bf16_small(in, wp, given ? in_norm->scale : nullptr, given ? in_norm->shift : nullptr, in_norm ? 1 : 0,
+                                          ws.act(L.Y[i]), handoff == 1 ? other : statp, d.B, H, W, st,
+                                          infin && handoff != 1 ? &fin : nullptr, handoff == 2 ? &pre : nullptr));
+        if (handoff == 1) return P4C_OK;
+        ntiles = conv_small_stat_slots(d.B, H, W);
+    } else if (i == 0 && !in_norm && first_conv_split_ok(d.compute, d.dtype, d.cin, d.cin_pad, d.B, H, W)) {
         // 69 -> 64 at the benchmark's channel count: a 64-channel row launch on channels 0..63 of the 96-channel pixels, then the tail
         // adds the product of the channels beyond 64 and takes the statistics of the result (conv_thin.hip)
         P4C_TRY(launch_conv_bf16_rows_wide_pixels(in, d.cin_pad, wslot(ws, 2 * NCONV + 2), ws.act(L.Y[i]), d.B, H, W, st));
@@ -564,9 +596,10 @@ extern "C" int p4c_halfunet_forward(const p4c_halfunet_desc* dp, const void* x, 
     // against 673 us per forward -- and removed in round 5: profiles/r04_step_ab_runs.txt block 25, profiles/HISTORY.md)
     for (int k = 0; k < NLEV; ++k) {
         const void* in = k == 0 ? x : ws.act(L.P[k]);
-        P4C_TRY(conv_block_fwd(d, ws, 2 * k, in, nullptr, params, running, training, st));
+        const bool hand = small_handoff(d, L, k, training);
+        P4C_TRY(conv_block_fwd(d, ws, 2 * k, in, nullptr, params, running, training, st, hand ? 1 : 0));
         Norm n1 = norm_at(ws, 2 * k, d.B);
-        P4C_TRY(conv_block_fwd(d, ws, 2 * k + 1, ws.act(L.Y[2 * k]), &n1, params, running, training, st));
+        P4C_TRY(conv_block_fwd(d, ws, 2 * k + 1, ws.act(L.Y[2 * k]), &n1, params, running, training, st, hand ? 2 : 0));
         if (k + 1 < NLEV) {
             Norm n2 = norm_at(ws, 2 * k + 1, d.B);
             P4C_TRY(pool_fwd(d.dtype, ws.act(L.Y[2 * k + 1]), n2.scale, n2.shift, d.B, L.Hk[k], L.Wk[k], ws.act(L.P[k + 1]), st));
@@ -819,6 +852,55 @@ extern "C" int p4c_conv_fwd(const void* in, int compute, int storage, int CI, co
                              m_blocks, as_stream(stream));
     return conv_fwd_f32((const float*)in, CI, (const float*)wprep, ks, in_scale, in_shift, in_relu, bias, (float*)out, out_cs,
                         stat_partial, B, H, W, m_blocks, as_stream(stream));
+}
+
+// ---- the latency-oriented 3x3 64->64 bf16 kernel of the coarse levels (conv_small.hip), for the op-level tests
+extern "C" int p4c_conv_small_ok(int storage, int B, int H, int W) { return conv_small_ok(storage, B, H, W) ? 1 : 0; }
+
+extern "C" int p4c_conv_small_stat_slots(int B, int H, int W) { return conv_small_stat_slots(B, H, W); }
+
+extern "C" int p4c_conv_small_fwd(const void* in, int compute, int storage, int CI, const void* wprep, int ks, const float* in_scale,
+                                  const float* in_shift, int in_relu, const float* bias, void* out, int out_cs, float* stat_partial,
+                                  int B, int H, int W, int m_blocks, p4c_stream_t stream, const void* nb_y, const float* nb_gamma,
+                                  const float* nb_scale, const float* nb_shift, const float* nb_rstd, const float* nb_mean,
+                                  const float* nb_k1, const float* nb_k2, unsigned int* fin_ticket, const float* fin_gamma,
+                                  const float* fin_beta, float eps, float momentum, float* running_mean, float* running_var,
+                                  float* scale, float* shift, float* mean, float* rstd, const float* pre_slots, const float* pre_gamma,
+                                  const float* pre_beta, float* pre_running_mean, float* pre_running_var, float* pre_scale,
+                                  float* pre_shift, float* pre_mean, float* pre_rstd) {
+    P4C_CHECK_ARG(in && wprep && out, "p4c_conv_small_fwd: null pointer");
+    P4C_CHECK_ARG(compute == P4C_BF16 && storage == P4C_BF16 && CI == 64 && ks == 3 && m_blocks == 1 && out_cs == 64 && !bias,
+                  "p4c_conv_small_fwd: 3x3 convolution 64 -> 64 on bf16 maps only");
+    if (nb_y || nb_gamma || nb_scale || nb_shift || nb_rstd || nb_mean || nb_k1 || nb_k2)
+        return fail(P4C_ERR_UNSUPPORTED, "p4c_conv_small_fwd: the NormBwdCoef load mode is not implemented");
+    BatchFin fin{};
+    if (fin_ticket) {
+        P4C_CHECK_ARG(stat_partial && fin_gamma && fin_beta && scale && shift && mean && rstd && (running_mean == nullptr) == (running_var == nullptr),
+                      "p4c_conv_small_fwd: the in-kernel finalize needs the slot buffer, gamma / beta and the four output arrays");
+        fin = BatchFin{stat_partial, fin_ticket, fin_gamma, fin_beta, running_mean, running_var, scale, shift, mean, rstd,
+                       (double)B * H * W, eps, momentum, B};
+    }
+    BatchFin pre{};
+    if (pre_slots) {
+        P4C_CHECK_ARG(pre_gamma && pre_beta && pre_scale && pre_shift && pre_mean && pre_rstd && (pre_running_mean == nullptr) == (pre_running_var == nullptr),
+                      "p4c_conv_small_fwd: the consumer-side finish needs gamma / beta and the four output arrays of the producer");
+        pre = BatchFin{const_cast<float*>(pre_slots), nullptr, pre_gamma, pre_beta, pre_running_mean, pre_running_var, pre_scale, pre_shift,
+                       pre_mean, pre_rstd, (double)B * H * W, eps, momentum, B};
+    }
+    return launch_conv3x3_bf16_small(in, wprep, in_scale, in_shift, in_relu, out, stat_partial, B, H, W, as_stream(stream),
+                                     fin_ticket ? &fin : nullptr, pre_slots ? &pre : nullptr);
+}
+
+// norm_finalize on a caller's statistics slots [B][slots_per_sample][2][64] (what the plan launches after a convolution that does not
+// finish its statistics itself): the reference of the in-kernel finalizes in the op-level tests
+extern "C" int p4c_norm_finalize(const float* partial, int slots_per_sample, int B, int64_t hw, int mode, int groups, const float* gamma,
+                                 const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* scale,
+                                 float* shift, float* mean, float* rstd, p4c_stream_t stream) {
+    P4C_CHECK_ARG(partial && gamma && beta && scale && shift && mean && rstd && slots_per_sample > 0 && B > 0 && hw > 0,
+                  "p4c_norm_finalize: bad arguments");
+    P4C_CHECK_ARG(mode == 0 || (mode == 1 && groups > 0 && 64 % groups == 0), "p4c_norm_finalize: bad mode / groups");
+    return norm_finalize(partial, slots_per_sample, B, hw, mode, groups, gamma, beta, eps, momentum, running_mean, running_var, scale,
+                         shift, mean, rstd, as_stream(stream));
 }
 
 extern "C" size_t p4c_conv_wgrad_workspace_bytes(int CI_pad, int ks) {

@@ -143,6 +143,18 @@ int launch_conv3x3_bf16_rows(const void* in, const void* wp, int ks, const float
 int conv_wgrad_bf16(const void* in, int storage, int CI, int ks, const float* in_scale, const float* in_shift, int in_relu,
                     const void* dout, float* partial, int G, int B, int H, int W, int CO, int CIreal, float* grad,
                     hipStream_t stream, const NormBwdCoef* nb = nullptr);
+// conv_small.hip: the latency-oriented 3x3 64->64 bf16 kernel of the HalfUNet plan's coarse levels (one tile per workgroup, one
+// statistics slot [2][64] per workgroup; stored map bit-identical to the row / ring kernel's).  conv_small_ok: the plan routes this
+// shape to it (a measured threshold); the launcher itself takes any shape whose per-sample byte offsets fit 32 bits.
+bool conv_small_ok(int storage, int B, int H, int W);
+int conv_small_stat_slots(int B, int H, int W);   // statistics slots per sample
+// pre (with in_relu = 1 and no in_scale / in_shift): the input is relu(norm(y)) of a producer that ran this kernel at the same shape
+// and left its slots in pre->slots without finishing them -- every workgroup combines them as BatchFin would and workgroup 0 writes
+// pre's outputs (conv_small_handoff_ok: the shape allows it; the slots must not be the buffer this launch writes its own to).
+bool conv_small_handoff_ok(int storage, int B, int H, int W);
+int launch_conv3x3_bf16_small(const void* in, const void* wp, const float* in_scale, const float* in_shift, int in_relu, void* out,
+                              float* stat_partial, int B, int H, int W, hipStream_t stream, const BatchFin* fin,
+                              const BatchFin* pre = nullptr);
 // conv_wgrad_rows.hip: the row-streaming weight gradient of the 3x3 convolution to 64 output channels, one chunk of <= 64 input channels
 // per launch (maps at least 64 pixels wide, W % 64 == 0); partial: [*nslots_out <= G][9][part_cip][64] floats for wgrad_reduce
 bool conv_wgrad_rows_ok(int storage, int in_cs, int ci_off, int dout_cs, int ks, int G, int B, int H, int W);

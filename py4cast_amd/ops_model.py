@@ -44,6 +44,59 @@ def conv_fwd(x: torch.Tensor, wprep: torch.Tensor, ks: int, m_blocks: int = 1, i
     return (out, stats) if want_stats else out
 
 
+def conv_small_ok(B: int, H: int, W: int) -> bool:
+    """True when the HalfUNet plan routes a 3x3 64 -> 64 convolution on a bf16 (B,H,W,64) map to the latency-oriented kernel."""
+    return bool(L.lib().p4c_conv_small_ok(L.BF16, B, H, W))
+
+
+def conv_small_fwd(x: torch.Tensor, wprep: torch.Tensor, in_scale: Optional[torch.Tensor] = None, in_shift: Optional[torch.Tensor] = None,
+                   want_stats: bool = False, finalize: Optional[dict] = None, pre: Optional[dict] = None):
+    """The latency-oriented 3x3 convolution 64 -> 64 (p4c_conv_small_fwd; csrc/conv_small.hip) on a bf16 (B,H,W,64) map, routed or not:
+    plain input, or relu(x * in_scale + in_shift).  want_stats: also the statistics slots (B * slots, 2, 64), one per workgroup.
+    finalize = {"gamma", "beta", "eps", "momentum", "running_mean", "running_var"} (the last two may be None): BatchNorm is finished in
+    the launch; returns (out, stats, (scale, shift, mean, rstd)).
+    pre = {"slots", "gamma", "beta", "running_mean", "running_var"}: x is the raw output of a launch at the same shape that left `slots`
+    unfinished; this launch finishes them in its prologue (eps / momentum: finalize's), convolves relu(norm(x)) and also returns the
+    producer's (scale, shift, mean, rstd) as a last element."""
+    L.require_cuda(x)
+    B, H, W, CI = x.shape
+    assert CI == 64 and x.dtype == torch.bfloat16
+    out = torch.empty(B, H, W, 64, dtype=x.dtype, device=x.device)
+    stats = None
+    if want_stats or finalize is not None:
+        stats = torch.empty(B * L.lib().p4c_conv_small_stat_slots(B, H, W), 2, 64, dtype=torch.float32, device=x.device)
+    fin = [None] * 2 + [0.0, 0.0] + [None] * 6
+    ticket, res = None, None
+    if finalize is not None:
+        ticket = torch.zeros(1, dtype=torch.int32, device=x.device)
+        res = tuple(torch.empty(B, 64, dtype=torch.float32, device=x.device) for _ in range(4))
+        fin = [L.ptr(finalize["gamma"]), L.ptr(finalize["beta"]), float(finalize["eps"]), float(finalize["momentum"]),
+               L.ptr(finalize.get("running_mean")), L.ptr(finalize.get("running_var"))] + [L.ptr(t) for t in res]
+    pre_args, pre_res = [None] * 9, None
+    if pre is not None:
+        assert finalize is not None and in_scale is None
+        pre_res = tuple(torch.empty(B, 64, dtype=torch.float32, device=x.device) for _ in range(4))
+        pre_args = [L.ptr(pre["slots"]), L.ptr(pre["gamma"]), L.ptr(pre["beta"]), L.ptr(pre.get("running_mean")),
+                    L.ptr(pre.get("running_var"))] + [L.ptr(t) for t in pre_res]
+    L.call("p4c_conv_small_fwd", L.ptr(x.contiguous()), L.BF16, L.BF16, 64, L.ptr(wprep), 3, L.ptr(in_scale), L.ptr(in_shift),
+           int(in_scale is not None or pre is not None), None, L.ptr(out), 64, L.ptr(stats), B, H, W, 1, L.stream(x.device),
+           None, None, None, None, None, None, None, None, L.ptr(ticket), *fin, *pre_args)
+    if pre is not None:
+        return out, stats, res, pre_res
+    if finalize is not None:
+        return out, stats, res
+    return (out, stats) if want_stats else out
+
+
+def norm_finalize(stats: torch.Tensor, B: int, hw: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float, momentum: float,
+                  running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None):
+    """BatchNorm scale / shift / mean / rstd (B,64) from statistics slots (B * slots, 2, 64) in a launch of its own (p4c_norm_finalize)."""
+    res = tuple(torch.empty(B, 64, dtype=torch.float32, device=stats.device) for _ in range(4))
+    L.call("p4c_norm_finalize", L.ptr(stats), stats.shape[0] // B, B, hw, 0, 0, L.ptr(gamma), L.ptr(beta), float(eps), float(momentum),
+           L.ptr(running_mean), L.ptr(running_var), *[L.ptr(t) for t in res], L.stream(stats.device))
+    return res
+
+
 def conv_wgrad(x: torch.Tensor, dout: torch.Tensor, ks: int, CO: int, CI: int, grad: torch.Tensor,
                in_scale: Optional[torch.Tensor] = None, in_shift: Optional[torch.Tensor] = None, in_relu: bool = False,
                compute="f32"):
