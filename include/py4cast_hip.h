@@ -569,6 +569,22 @@ int64_t p4c_halfunet_param_count(const p4c_halfunet_desc* d);
 /* saved_bytes: activations kept from forward for backward (one per forward call still awaiting its
  * backward); scratch_bytes: transient buffers shareable between calls on one stream. */
 int p4c_halfunet_workspace_bytes(const p4c_halfunet_desc* d, size_t* saved_bytes, size_t* scratch_bytes);
+/* Where the plan keeps what, as BYTE offsets (host-only query; nothing is launched).  Blocks 0..11: encoder level k convolution j is
+ * 2k + j (k = 0..4, j = 0, 1), the decoder's are 10 and 11.  Activations and activation gradients are (B,Hk,Wk,64) maps of elem_bytes
+ * wide elements (the descriptor's dtype), Hk = H >> k.
+ *   saved workspace:   Y[i] raw output of convolution i; P[k] pooled input of level k = 1..4 (P[0] = -1: level 0 reads x); S the
+ *                      up-sampled sum; norm[i] four fp32 arrays of (B,64) in a row: scale | shift | mean | rstd
+ *   scratch workspace: G0 = dS (gradient of S); TB the x passes tx_1..tx_4 of the up-sampling adjoints back to back, (B,H,W >> k,64);
+ *                      DY[set][i] the gradient buffer of block i, k1 / k2[set][i] its normalisation backward's (B,64) fp32 coefficients;
+ *                      a backward call uses one of the two sets (consecutive calls of a thread alternate)
+ *   parameters:        w / gamma / beta[i], wout inside the flat parameter (and gradient) vector, params_bytes its size */
+typedef struct p4c_halfunet_layout_t {
+    int64_t elem_bytes;
+    int64_t Y[12], P[5], S, norm[12], saved_bytes;
+    int64_t G0, TB, DY[2][12], k1[2][12], k2[2][12], scratch_bytes;
+    int64_t w[12], gamma[12], beta[12], wout, params_bytes;
+} p4c_halfunet_layout_t;
+int p4c_halfunet_layout(const p4c_halfunet_desc* d, p4c_halfunet_layout_t* out);
 /* re-lays (and for P4C_BF16 rounds) every convolution weight, forward and data-gradient orientation, into the
  * scratch workspace: one launch.  Valid until the parameters change or the scratch workspace is reused elsewhere. */
 int p4c_halfunet_prepare_weights(const p4c_halfunet_desc* d, const float* params, void* scratch, p4c_stream_t stream);

@@ -21,6 +21,18 @@ class HalfUNetDesc(ctypes.Structure):
 DP = ctypes.POINTER(HalfUNetDesc)
 
 
+class HalfUNetLayout(ctypes.Structure):
+    """struct p4c_halfunet_layout_t: byte offsets into the plan's saved / scratch workspaces and its flat parameter vector"""
+
+    _fields_ = [
+        ("elem_bytes", c_int64),
+        ("Y", c_int64 * 12), ("P", c_int64 * 5), ("S", c_int64), ("norm", c_int64 * 12), ("saved_bytes", c_int64),
+        ("G0", c_int64), ("TB", c_int64), ("DY", c_int64 * 12 * 2), ("k1", c_int64 * 12 * 2), ("k2", c_int64 * 12 * 2),
+        ("scratch_bytes", c_int64),
+        ("w", c_int64 * 12), ("gamma", c_int64 * 12), ("beta", c_int64 * 12), ("wout", c_int64), ("params_bytes", c_int64),
+    ]
+
+
 class RowMlpDesc(ctypes.Structure):
     """struct p4c_row_mlp_desc"""
 
@@ -60,6 +72,7 @@ SIGNATURES = {
     "p4c_upsample_sum_bwd_x": [I, P, I, I, I, P, P, P, P, P],
     "p4c_first_conv_tail": [P, I, I, P, P, P, I, I, I, P],
     "p4c_halfunet_workspace_bytes": [DP, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)],
+    "p4c_halfunet_layout": [DP, ctypes.POINTER(HalfUNetLayout)],
     "p4c_halfunet_prepare_weights": [DP, P, P, P],
     "p4c_halfunet_forward": [DP, P, P, P, P, P, P, I, P],
     "p4c_halfunet_tail": [DP, P, P, P, P, P, P],

@@ -571,6 +571,37 @@ extern "C" int p4c_halfunet_workspace_bytes(const p4c_halfunet_desc* d, size_t* 
     return P4C_OK;
 }
 
+extern "C" int p4c_halfunet_layout(const p4c_halfunet_desc* d, p4c_halfunet_layout_t* out) {
+    P4C_TRY(check_desc(d));
+    P4C_CHECK_ARG(out, "p4c_halfunet_layout: null pointer");
+    Layout L;
+    make_layout(*d, L);
+    const int64_t f = (int64_t)sizeof(float);
+    out->elem_bytes = L.esz;
+    for (int i = 0; i < NCONV; ++i) {
+        out->Y[i] = L.Y[i] * L.esz;
+        out->norm[i] = L.norm_base + L.norm[i] * f;
+        out->w[i] = L.w[i] * f;
+        out->gamma[i] = L.gamma[i] * f;
+        out->beta[i] = L.beta[i] * f;
+        for (int s = 0; s < 2; ++s) {
+            out->DY[s][i] = L.g_base + L.DY[s][i] * L.esz;
+            out->k1[s][i] = L.k1i[s][i] * f;
+            out->k2[s][i] = L.k2i[s][i] * f;
+        }
+    }
+    out->P[0] = -1;
+    for (int k = 1; k < NLEV; ++k) out->P[k] = L.P[k] * L.esz;
+    out->S = L.S * L.esz;
+    out->saved_bytes = L.saved_bytes;
+    out->G0 = L.g_base + L.G0 * L.esz;
+    out->TB = L.g_base + L.TB * L.esz;
+    out->scratch_bytes = L.scratch_bytes;
+    out->wout = L.wout * f;
+    out->params_bytes = L.nparams * f;
+    return P4C_OK;
+}
+
 extern "C" int p4c_halfunet_prepare_weights(const p4c_halfunet_desc* dp, const float* params, void* scratchv,
                                             p4c_stream_t stream) {
     P4C_TRY(check_desc(dp));

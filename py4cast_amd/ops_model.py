@@ -44,6 +44,27 @@ def conv_fwd(x: torch.Tensor, wprep: torch.Tensor, ks: int, m_blocks: int = 1, i
     return (out, stats) if want_stats else out
 
 
+def halfunet_layout(desc):
+    """p4c_halfunet_layout of a HalfUNetDesc: byte offsets of every buffer the HalfUNet plan keeps in its saved / scratch workspaces
+    and of every parameter in the flat vector, as plain Python ints and lists (host-only; no device needed)."""
+    import ctypes
+
+    from ._lib_model import HalfUNetLayout
+
+    lay = HalfUNetLayout()
+    L.check(L.lib().p4c_halfunet_layout(ctypes.byref(desc), ctypes.byref(lay)), "p4c_halfunet_layout")
+    out = {}
+    for name, _ in HalfUNetLayout._fields_:
+        v = getattr(lay, name)
+        out[name] = int(v) if isinstance(v, int) else [list(r) if hasattr(r, "__len__") else int(r) for r in v]
+    return out
+
+
+def conv_kernel_kind(B: int, H: int, W: int, CI: int = 64, ks: int = 3) -> int:
+    """Which bf16 kernel conv_fwd runs on a bf16 (B,H,W,CI) map: 2 = row-streaming, 1 = tile ring, 0 = the generic tile kernel."""
+    return int(L.lib().p4c_conv_kernel_kind(L.BF16, L.BF16, CI, ks, B, H, W))
+
+
 def conv_small_ok(B: int, H: int, W: int) -> bool:
     """True when the HalfUNet plan routes a 3x3 64 -> 64 convolution on a bf16 (B,H,W,64) map to the latency-oriented kernel."""
     return bool(L.lib().p4c_conv_small_ok(L.BF16, B, H, W))

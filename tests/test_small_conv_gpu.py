@@ -188,23 +188,21 @@ def test_consumer_side_finish_equals_the_in_kernel_finish(gpu_device, B, H, W):
     assert torch.equal(again[2], y2b) and all(torch.equal(a, b) for a, b in zip(again[5], n1b)) and torch.equal(again[6], rm_b)
 
 
-def _saved_views(saved, B, H, W):
-    """Raw conv outputs Y[0..11] and normalisation arrays (scale, shift, mean, rstd) of the bf16 plan's saved workspace
-    (csrc/halfunet.cpp: make_layout)."""
+def _saved_views(saved, lay, B, H, W):
+    """Raw conv outputs Y[0..11] and normalisation arrays (scale, shift, mean, rstd) of the bf16 plan's saved workspace, at the offsets
+    the library reports (ops_model.halfunet_layout)."""
     n = [B * (H >> k) * (W >> k) for k in range(5)]
     lev = [i // 2 if i < 10 else 0 for i in range(12)]
-    off, Y = 0, []
-    for i in range(12):
-        Y.append(saved[2 * off: 2 * (off + n[lev[i]] * 64)].view(torch.bfloat16))
-        off += n[lev[i]] * 64
-    off += sum(n[1:]) * 64 + n[0] * 64
-    base = (2 * off + 255) // 256 * 256
-    norms = [saved[base + 4 * i * 4 * B * 64: base + 4 * (i + 1) * 4 * B * 64].view(torch.float32) for i in range(12)]
+    assert lay["elem_bytes"] == 2 and lay["saved_bytes"] == saved.numel()
+    Y = [saved[lay["Y"][i]: lay["Y"][i] + 2 * n[lev[i]] * 64].view(torch.bfloat16) for i in range(12)]
+    norms = [saved[lay["norm"][i]: lay["norm"][i] + 4 * 4 * B * 64].view(torch.float32) for i in range(12)]
     return Y, norms
 
 
 def _plan_run(model, x, gy, buffers, B, H, W, env):
     """one forward + backward under the A/B switches `env`: (y, gradients, raw conv outputs, normalisation arrays)"""
+    from py4cast_amd import ops_model as om
+
     os.environ.update(env)
     try:
         with torch.no_grad():
@@ -217,7 +215,7 @@ def _plan_run(model, x, gy, buffers, B, H, W, env):
         while node is not None and not saved:   # (behind the channel slice and the cast to the caller's dtype: the plan's node)
             saved = [t for t in getattr(node, "saved_tensors", ()) if t.dtype == torch.uint8]
             node = node.next_functions[0][0] if node.next_functions else None
-        Y, norms = _saved_views(saved[0].clone(), B, H, W)
+        Y, norms = _saved_views(saved[0].clone(), om.halfunet_layout(model._desc(B, H, W)), B, H, W)
         (y * gy).sum().backward()
         torch.cuda.synchronize()
         return y.detach().clone(), {n: p.grad.clone() for n, p in model.named_parameters()}, Y, norms
