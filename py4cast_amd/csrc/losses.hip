@@ -1319,128 +1319,163 @@ extern "C" int p4c_nan_moments(const float* x, const float* x_next, int64_t batc
     return P4C_OK;
 }
 
-static int ar_update_loss_fwd_impl(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs,
-                                   const float* target, int64_t tgt_bs, const float* std, const float* mean,
-                                   const float* border_mask, const float* interior_mask, float* new_state,
-                                   int64_t new_bs, const float* weights, float num_interior,
-                                   const int32_t* masked_count, int kind, int mask_mode, float* loss_out,
-                                   int64_t loss_stride, void* workspace, int B, int64_t N, int F, float keep_prev,
-                                   const NextX* next, p4c_stream_t stream, bool loss = true) {
-    // loss == false: the free step (p4c_ar_update_next) -- the LOSS = false instantiations, same path conditions, no final kernel
-    if (loss)
-        P4C_CHECK_ARG(y && target && interior_mask && new_state && weights && loss_out && workspace,
+// ------------------------------------------------------------------ the AR step: host dispatch
+// Every entry point below fills one StepFwd / StepBwd and hands it to an implementation; every kernel template has ONE launch site,
+// which takes the element type and the boolean template flags from with_dtype / with_flag.
+template <typename T>
+struct type_tag {
+    using type = T;
+};
+// f(type_tag<float>) or f(type_tag<bf16>) for a P4C_F32 / P4C_BF16 code the caller has validated; f(std::true_type) or f(std::false_type)
+template <typename Fn>
+static int with_dtype(int dtype, Fn&& f) {
+    return dtype == P4C_F32 ? f(type_tag<float>{}) : f(type_tag<bf16>{});
+}
+template <typename Fn>
+static int with_flag(bool on, Fn&& f) {
+    return on ? f(std::true_type{}) : f(std::false_type{});
+}
+template <typename Fn>
+static int with_dtype_flags(int dtype, bool a, bool b, Fn&& f) {   // f(type_tag, flag a, flag b)
+    return with_dtype(dtype, [&](auto ty) -> int {
+        return with_flag(a, [&](auto fa) -> int { return with_flag(b, [&](auto fb) -> int { return f(ty, fa, fb); }); });
+    });
+}
+static inline bool rows_dtype(int dtype) { return dtype == P4C_F32 || dtype == P4C_BF16; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// One forward step.  loss == false: the free step (p4c_ar_update_next / p4c_out_conv_update_fwd) -- the LOSS = false instantiations,
+// same path conditions, no final kernel; weights, loss_out and workspace are then NULL.
+struct StepFwd {
+    const float* prev; int64_t prev_bs;
+    const void* y; int y_dtype; int y_cs;      // front.a set: y is NULL (formed by the front end), bf16 rows of 64 channels
+    const float* target; int64_t tgt_bs; const float* std; const float* mean; const float* border_mask; const float* interior_mask;
+    float* new_state; int64_t new_bs;
+    const float* weights; float num_interior; const int32_t* masked_count; int kind; int mask_mode;
+    float* loss_out; int64_t loss_stride; void* workspace;
+    int B; int64_t N; int F; float keep_prev;
+    NextX next;        // all zero: no extra output
+    FlatFront front;   // all zero: no convolution front end
+    bool loss;
+    p4c_stream_t stream;
+    // the NEXT instantiations; also: a step that asks for an extra output has no scalar kernel to fall back to
+    bool has_next() const { return next.x || next.lgrad; }
+    int esz() const { return y_dtype == P4C_BF16 ? 2 : 4; }
+};
+
+// ---- path predicates of a forward step
+// the fp32 state tensors (previous state, target, new state) in 16-byte pieces: what both fast paths ask of them
+static bool state_rows16(const StepFwd& s) {
+    return s.prev_bs % 4 == 0 && s.tgt_bs % 4 == 0 && s.new_bs % 4 == 0 && aligned16(s.prev) && aligned16(s.target) && aligned16(s.new_state);
+}
+// the 16-byte kernels: a lane owns 4 consecutive features of a grid point (NaN masks allowed)
+static bool fwd_v4_ok(const StepFwd& s) {
+    const NextX& nx = s.next;
+    return !force_flat() && rows_dtype(s.y_dtype) && s.F % 4 == 0 && s.F <= 64 && s.y_cs % 4 == 0 && state_rows16(s) && aligned16(s.y) &&
+           (!s.loss || aligned16(s.weights)) &&   // (the free step reads no weights)
+           aligned16(s.std) && aligned16(s.mean) &&
+           (!nx.x || (nx.c_pad % 4 == 0 && nx.Fs % 4 == 0 && nx.c_pad / 4 - s.F / 4 <= pow2_ge64(s.F / 4))) &&
+           (!nx.lgrad || (nx.lgrad_bs % 4 == 0 && aligned16(nx.lgrad)));   // (lgrad: 16-byte aligned here, 8-byte on the flat path)
+}
+// the flat kernels -- any other feature count (the shipped Titan configuration has F = 21): see flat_ok; weights, std and mean go
+// through LDS (no alignment asked)
+static bool fwd_flat_ok(const StepFwd& s) {
+    const NextX& nx = s.next;
+    return rows_dtype(s.y_dtype) && s.mask_mode == P4C_MASK_NONE && flat_ok(s.F, s.N, s.y_cs, s.esz()) && state_rows16(s) && aligned16(s.y) &&
+           (!nx.x || ((nx.c_pad * s.esz()) % 16 == 0 && nx.c_pad <= 256 && nx.c_pad >= s.F + nx.Fs + nx.Ff && aligned16(nx.x))) &&
+           (!nx.lgrad || (nx.lgrad_bs % 4 == 0 && aligned8(nx.lgrad)));   // (lgrad: 8-byte aligned here, 16-byte on the 16-byte path)
+}
+
+// ---- pieces shared by the forward and the backward launches
+// grid of a flat kernel: workgroups walk tiles of FLAT_P grid points
+static int flat_blocks(int64_t N, int B) {
+    const int64_t ntiles = (N + FLAT_P - 1) / FLAT_P;
+    const int nblk = loss_blocks(N, FLAT_P / 4, B);
+    return nblk > ntiles ? (int)ntiles : nblk;
+}
+// dynamic LDS of the flat kernels (the layouts are stated at the head of each kernel)
+static size_t flat_fwd_smem(const StepFwd& s) {
+    return (size_t)FLAT_P * s.y_cs * s.esz() + (s.next.x ? (size_t)FLAT_P * s.next.c_pad * s.esz() : 0) + 5 * 64 * sizeof(float) +
+           (s.front.a ? 2 * 4 * 64 * 16 + 2 * 64 * sizeof(float) : 0);
+}
+// the loss epilogue: the per-block partials of a (b, t = i) column become its loss
+static int loss_final(const StepFwd& s, int nblk, const char* label) {
+    hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(s.B), dim3(64), 0, as_stream(s.stream), (const float*)s.workspace, nblk,
+                       s.num_interior, s.masked_count, s.loss_out, s.loss_stride, s.B);
+    P4C_CHECK_LAUNCH(label);
+    return P4C_OK;
+}
+
+// ---- the forward launch sites: launch, check under `label`, then the loss epilogue under `final_label` where the step has a loss
+static int launch_fwd_v4(const StepFwd& s, const char* label, const char* final_label) {
+    const int FP4 = pow2_ge64(s.F / 4);
+    const int nblk = loss_blocks(s.N, 64 / FP4, s.B);
+    with_dtype_flags(s.y_dtype, s.has_next(), s.loss, [&](auto ty, auto next, auto loss) -> int {
+        using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((ar_update_loss_fwd_v4_kernel<TY, decltype(next)::value, decltype(loss)::value>), dim3(nblk, s.B), dim3(256), 0,
+                           as_stream(s.stream), s.prev, s.prev_bs, (const TY*)s.y, s.y_cs, s.target, s.tgt_bs, s.std, s.mean, s.border_mask,
+                           s.interior_mask, s.new_state, s.new_bs, s.weights, s.kind, s.mask_mode, (float*)s.workspace, s.N, s.F,
+                           s.keep_prev, FP4, s.next);
+        return P4C_OK;
+    });
+    P4C_CHECK_LAUNCH(label);
+    return s.loss ? loss_final(s, nblk, final_label) : P4C_OK;
+}
+
+static int launch_fwd_flat(const StepFwd& s, const char* label, const char* final_label) {
+    const int nblk = flat_blocks(s.N, s.B);
+    const size_t smem = flat_fwd_smem(s);
+    P4C_TRY(with_dtype_flags(s.y_dtype, s.front.a != nullptr, s.loss, [&](auto ty, auto front, auto loss) -> int {
+        using TY = typename decltype(ty)::type;
+        if constexpr (decltype(front)::value && !std::is_same<TY, bf16>::value) {
+            return fail(P4C_ERR_INVALID, "%s: the fused front end forms bf16 rows", label);   // (no such kernel; callers pass bf16)
+        } else {
+            auto kernel = ar_update_loss_fwd_flat_kernel<TY, decltype(front)::value, decltype(loss)::value>;
+            P4C_TRY(ensure_dyn_smem((const void*)kernel, (int)smem));
+            hipLaunchKernelGGL(kernel, dim3(nblk, s.B), dim3(256), smem, as_stream(s.stream), s.prev, s.prev_bs, (const TY*)s.y, s.y_cs,
+                               s.target, s.tgt_bs, s.std, s.mean, s.border_mask, s.interior_mask, s.new_state, s.new_bs, s.weights, s.kind,
+                               (float*)s.workspace, s.N, s.F, s.keep_prev, s.next, s.front);
+            return P4C_OK;
+        }
+    }));
+    P4C_CHECK_LAUNCH(label);
+    return s.loss ? loss_final(s, nblk, final_label) : P4C_OK;
+}
+
+static int launch_fwd_scalar(const StepFwd& s, const char* label, const char* final_label) {
+    const int FP = pow2_ge64(s.F), iters = (s.F + FP - 1) / FP;
+    const int nblk = loss_blocks(s.N, 64 / FP, s.B);
+    if (!rows_dtype(s.y_dtype)) return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_fwd: bad dtype %d", s.y_dtype);
+    with_dtype(s.y_dtype, [&](auto ty) -> int { return with_flag(s.loss, [&](auto loss) -> int {
+        using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((ar_update_loss_fwd_kernel<TY, decltype(loss)::value>), dim3(nblk, s.B), dim3(256), 0, as_stream(s.stream), s.prev,
+                           s.prev_bs, (const TY*)s.y, s.y_cs, s.target, s.tgt_bs, s.std, s.mean, s.border_mask, s.interior_mask, s.new_state,
+                           s.new_bs, s.weights, s.kind, s.mask_mode, (float*)s.workspace, s.N, s.F, s.keep_prev, FP, iters);
+        return P4C_OK;
+    }); });
+    P4C_CHECK_LAUNCH(label);
+    return s.loss ? loss_final(s, nblk, final_label) : P4C_OK;
+}
+
+static int ar_update_loss_fwd_impl(const StepFwd& s) {
+    if (s.loss)
+        P4C_CHECK_ARG(s.y && s.target && s.interior_mask && s.new_state && s.weights && s.loss_out && s.workspace,
                       "p4c_ar_update_loss_fwd: null pointer");
     else
-        P4C_CHECK_ARG(y && new_state && (!border_mask || (target && interior_mask)),
+        P4C_CHECK_ARG(s.y && s.new_state && (!s.border_mask || (s.target && s.interior_mask)),
                       "p4c_ar_update_next: null pointer (border forcing needs border_mask, interior_mask and target)");
-    P4C_CHECK_ARG(prev || keep_prev == 0.0f, "p4c_ar_update_loss_fwd: prev is null but keep_prev != 0");
-    P4C_CHECK_ARG((std == nullptr) == (mean == nullptr), "p4c_ar_update_loss_fwd: std and mean go together");
-    P4C_CHECK_ARG(mask_mode == P4C_MASK_NONE || mask_mode == P4C_MASK_FROM_NAN,
+    P4C_CHECK_ARG(s.prev || s.keep_prev == 0.0f, "p4c_ar_update_loss_fwd: prev is null but keep_prev != 0");
+    P4C_CHECK_ARG((s.std == nullptr) == (s.mean == nullptr), "p4c_ar_update_loss_fwd: std and mean go together");
+    P4C_CHECK_ARG(s.mask_mode == P4C_MASK_NONE || s.mask_mode == P4C_MASK_FROM_NAN,
                   "p4c_ar_update_loss_fwd: only MASK_NONE / MASK_FROM_NAN are fused");
-    P4C_CHECK_ARG(F > 0 && F <= 64 * LOSS_MAX_ITERS && y_cs >= F, "p4c_ar_update_loss_fwd: bad F / y_cs");
-    if (!force_flat() && (y_dtype == P4C_F32 || y_dtype == P4C_BF16) && F % 4 == 0 && F <= 64 && y_cs % 4 == 0 && prev_bs % 4 == 0 && tgt_bs % 4 == 0 && new_bs % 4 == 0 &&
-        aligned16(prev) && aligned16(y) && aligned16(target) && aligned16(new_state) && (!loss || aligned16(weights)) && aligned16(std) &&
-        aligned16(mean) &&
-        (!next || !next->x || (next->c_pad % 4 == 0 && next->Fs % 4 == 0 && next->c_pad / 4 - F / 4 <= pow2_ge64(F / 4))) &&
-        (!next || !next->lgrad || (next->lgrad_bs % 4 == 0 && aligned16(next->lgrad)))) {
-        const int FP4 = pow2_ge64(F / 4);
-        const int nblk4 = loss_blocks(N, 64 / FP4, B);
-        NextX nx{};
-        if (next) nx = *next;
-#define P4C_LAUNCH_V4(TY, NEXTF, LOSSF)                                                                                       \
-    hipLaunchKernelGGL((ar_update_loss_fwd_v4_kernel<TY, NEXTF, LOSSF>), dim3(nblk4, B), dim3(256), 0, as_stream(stream), prev, prev_bs, \
-                       (const TY*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs, weights,  \
-                       kind, mask_mode, (float*)workspace, N, F, keep_prev, FP4, nx)
-        if (!loss) {
-            if (y_dtype == P4C_F32) {
-                if (next) P4C_LAUNCH_V4(float, true, false); else P4C_LAUNCH_V4(float, false, false);
-            } else {
-                if (next) P4C_LAUNCH_V4(bf16, true, false); else P4C_LAUNCH_V4(bf16, false, false);
-            }
-            P4C_CHECK_LAUNCH("p4c_ar_update_next(v4)");
-            return P4C_OK;
-        }
-        if (y_dtype == P4C_F32) {
-            if (next) P4C_LAUNCH_V4(float, true, true); else P4C_LAUNCH_V4(float, false, true);
-        } else {
-            if (next) P4C_LAUNCH_V4(bf16, true, true); else P4C_LAUNCH_V4(bf16, false, true);
-        }
-#undef P4C_LAUNCH_V4
-        P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd(v4)");
-        hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream), (const float*)workspace,
-                           nblk4, num_interior, masked_count, loss_out, loss_stride, B);
-        P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd(final)");
-        return P4C_OK;
-    }
-    // ---- any other feature count (the shipped Titan configuration has F = 21): the flat kernels
-    {
-        const int esz = y_dtype == P4C_BF16 ? 2 : 4;
-        bool ok = (y_dtype == P4C_F32 || y_dtype == P4C_BF16) && mask_mode == P4C_MASK_NONE && flat_ok(F, N, y_cs, esz) && prev_bs % 4 == 0 &&
-                  tgt_bs % 4 == 0 && new_bs % 4 == 0 && aligned16(prev) && aligned16(y) && aligned16(target) && aligned16(new_state);
-        if (ok && next && next->x)
-            ok = (next->c_pad * esz) % 16 == 0 && next->c_pad <= 256 && next->c_pad >= F + next->Fs + next->Ff && aligned16(next->x);
-        if (ok && next && next->lgrad) ok = next->lgrad_bs % 4 == 0 && (reinterpret_cast<uintptr_t>(next->lgrad) & 7) == 0;
-        if (ok) {
-            NextX nx{};
-            if (next) nx = *next;
-            const int64_t ntiles = (N + FLAT_P - 1) / FLAT_P;
-            int nblk = loss_blocks(N, FLAT_P / 4, B);
-            if (nblk > ntiles) nblk = (int)ntiles;
-            const size_t smem = (size_t)FLAT_P * y_cs * esz + (nx.x ? (size_t)FLAT_P * nx.c_pad * esz : 0) + 5 * 64 * sizeof(float);
-            if (!loss) {
-                if (y_dtype == P4C_F32) {
-                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<float, false, false>, (int)smem));
-                    hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<float, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
-                                       prev, prev_bs, (const float*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
-                                       new_bs, weights, kind, (float*)workspace, N, F, keep_prev, nx, FlatFront{});
-                } else {
-                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16, false, false>, (int)smem));
-                    hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<bf16, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
-                                       prev, prev_bs, (const bf16*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
-                                       new_bs, weights, kind, (float*)workspace, N, F, keep_prev, nx, FlatFront{});
-                }
-                P4C_CHECK_LAUNCH("p4c_ar_update_next(flat)");
-                return P4C_OK;
-            }
-            if (y_dtype == P4C_F32) {
-                P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<float>, (int)smem));
-                hipLaunchKernelGGL(ar_update_loss_fwd_flat_kernel<float>, dim3(nblk, B), dim3(256), smem, as_stream(stream), prev, prev_bs,
-                                   (const float*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs, weights,
-                                   kind, (float*)workspace, N, F, keep_prev, nx, FlatFront{});
-            } else {
-                P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16>, (int)smem));
-                hipLaunchKernelGGL(ar_update_loss_fwd_flat_kernel<bf16>, dim3(nblk, B), dim3(256), smem, as_stream(stream), prev, prev_bs,
-                                   (const bf16*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs, weights,
-                                   kind, (float*)workspace, N, F, keep_prev, nx, FlatFront{});
-            }
-            P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd(flat)");
-            hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream), (const float*)workspace, nblk,
-                               num_interior, masked_count, loss_out, loss_stride, B);
-            P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd(final)");
-            return P4C_OK;
-        }
-    }
-    if (next) return fail(P4C_ERR_UNSUPPORTED, "p4c_ar_update_loss_fwd_next: needs the 16-byte path (F %% 4 == 0, F <= 64, aligned rows) or the "
-                                               "flat path (F <= 64, N * F %% 4 == 0, whole 16-byte slots per row, aligned rows, no NaN masks)");
-    const int FP = pow2_ge64(F), iters = (F + FP - 1) / FP;
-    const int nblk = loss_blocks(N, 64 / FP, B);
-#define P4C_LAUNCH_FWD(TY, LOSSF)                                                                                       \
-    hipLaunchKernelGGL((ar_update_loss_fwd_kernel<TY, LOSSF>), dim3(nblk, B), dim3(256), 0, as_stream(stream), prev, prev_bs, \
-                       (const TY*)y, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs,    \
-                       weights, kind, mask_mode, (float*)workspace, N, F, keep_prev, FP, iters)
-    if (y_dtype != P4C_F32 && y_dtype != P4C_BF16) return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_fwd: bad dtype %d", y_dtype);
-    if (!loss) {
-        if (y_dtype == P4C_F32) P4C_LAUNCH_FWD(float, false); else P4C_LAUNCH_FWD(bf16, false);
-        P4C_CHECK_LAUNCH("p4c_ar_update_next");
-        return P4C_OK;
-    }
-    if (y_dtype == P4C_F32) P4C_LAUNCH_FWD(float, true); else P4C_LAUNCH_FWD(bf16, true);
-#undef P4C_LAUNCH_FWD
-    P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd");
-    hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream),
-                       (const float*)workspace, nblk, num_interior, masked_count, loss_out, loss_stride, B);
-    P4C_CHECK_LAUNCH("p4c_ar_update_loss_fwd(final)");
-    return P4C_OK;
+    P4C_CHECK_ARG(s.F > 0 && s.F <= 64 * LOSS_MAX_ITERS && s.y_cs >= s.F, "p4c_ar_update_loss_fwd: bad F / y_cs");
+    const char* final_label = "p4c_ar_update_loss_fwd(final)";
+    if (fwd_v4_ok(s)) return launch_fwd_v4(s, s.loss ? "p4c_ar_update_loss_fwd(v4)" : "p4c_ar_update_next(v4)", final_label);
+    if (fwd_flat_ok(s)) return launch_fwd_flat(s, s.loss ? "p4c_ar_update_loss_fwd(flat)" : "p4c_ar_update_next(flat)", final_label);
+    if (s.has_next())
+        return fail(P4C_ERR_UNSUPPORTED, "p4c_ar_update_loss_fwd_next: needs the 16-byte path (F %% 4 == 0, F <= 64, aligned rows) or the "
+                                         "flat path (F <= 64, N * F %% 4 == 0, whole 16-byte slots per row, aligned rows, no NaN masks)");
+    return launch_fwd_scalar(s, s.loss ? "p4c_ar_update_loss_fwd" : "p4c_ar_update_next", final_label);
 }
 
 extern "C" int p4c_ar_update_loss_fwd(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs,
@@ -1450,9 +1485,9 @@ extern "C" int p4c_ar_update_loss_fwd(const float* prev, int64_t prev_bs, const 
                                       const int32_t* masked_count, int kind, int mask_mode, float* loss_out,
                                       int64_t loss_stride, void* workspace, int B, int64_t N, int F, float keep_prev,
                                       p4c_stream_t stream) {
-    return ar_update_loss_fwd_impl(prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask,
-                                   new_state, new_bs, weights, num_interior, masked_count, kind, mask_mode, loss_out,
-                                   loss_stride, workspace, B, N, F, keep_prev, nullptr, stream);
+    return ar_update_loss_fwd_impl(StepFwd{prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                           new_bs, weights, num_interior, masked_count, kind, mask_mode, loss_out, loss_stride, workspace,
+                                           B, N, F, keep_prev, NextX{}, FlatFront{}, true, stream});
 }
 
 extern "C" int p4c_ar_update_loss_fwd_next(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs,
@@ -1466,10 +1501,10 @@ extern "C" int p4c_ar_update_loss_fwd_next(const float* prev, int64_t prev_bs, c
     P4C_CHECK_ARG(x_next && statics && forcing_next, "p4c_ar_update_loss_fwd_next: null pointer");
     P4C_CHECK_ARG(c_pad >= F + Fs + Ff && Fs >= 0 && Ff >= 0, "p4c_ar_update_loss_fwd_next: c_pad must be >= F + Fs + Ff");
     P4C_CHECK_ARG(mask_mode == P4C_MASK_NONE, "p4c_ar_update_loss_fwd_next: the NaN-mask input channel is built by p4c_build_x");
-    NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0};
-    return ar_update_loss_fwd_impl(prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask,
-                                   new_state, new_bs, weights, num_interior, masked_count, kind, mask_mode, loss_out,
-                                   loss_stride, workspace, B, N, F, keep_prev, &nx, stream);
+    const NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0};
+    return ar_update_loss_fwd_impl(StepFwd{prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                           new_bs, weights, num_interior, masked_count, kind, mask_mode, loss_out, loss_stride, workspace,
+                                           B, N, F, keep_prev, nx, FlatFront{}, true, stream});
 }
 
 // The same fused step that ALSO saves d loss_elem / d pred of every element as bf16 rows (lgrad: (N, F) per sample, batch stride
@@ -1489,10 +1524,10 @@ extern "C" int p4c_ar_update_loss_fwd_next_saved(const float* prev, int64_t prev
         P4C_CHECK_ARG(c_pad >= F + Fs + Ff && Fs >= 0 && Ff >= 0, "p4c_ar_update_loss_fwd_next_saved: c_pad must be >= F + Fs + Ff");
         P4C_CHECK_ARG(mask_mode == P4C_MASK_NONE, "p4c_ar_update_loss_fwd_next_saved: the NaN-mask input channel is built by p4c_build_x");
     }
-    NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs};
-    return ar_update_loss_fwd_impl(prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask,
-                                   new_state, new_bs, weights, num_interior, masked_count, kind, mask_mode, loss_out,
-                                   loss_stride, workspace, B, N, F, keep_prev, &nx, stream);
+    const NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs};
+    return ar_update_loss_fwd_impl(StepFwd{prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                           new_bs, weights, num_interior, masked_count, kind, mask_mode, loss_out, loss_stride, workspace,
+                                           B, N, F, keep_prev, nx, FlatFront{}, true, stream});
 }
 
 // The FREE step: an AR step without a loss term -- an intermediary step of num_inter_steps >= 2 (border forced to the target, no
@@ -1507,15 +1542,15 @@ extern "C" int p4c_ar_update_next(const float* prev, int64_t prev_bs, const void
     P4C_CHECK_ARG(B > 0 && N > 0, "p4c_ar_update_next: bad dims");
     P4C_CHECK_ARG((target == nullptr) == (border_mask == nullptr), "p4c_ar_update_next: target and border_mask go together");
     const int mask_mode = nan_to_num ? P4C_MASK_FROM_NAN : P4C_MASK_NONE;
-    NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0};
     if (x_next) {
         P4C_CHECK_ARG(statics && forcing_next, "p4c_ar_update_next: null pointer");
         P4C_CHECK_ARG(c_pad >= F + Fs + Ff && Fs >= 0 && Ff >= 0, "p4c_ar_update_next: c_pad must be >= F + Fs + Ff");
         P4C_CHECK_ARG(!nan_to_num, "p4c_ar_update_next: the NaN-mask input channel is built by p4c_build_x");
     }
-    return ar_update_loss_fwd_impl(prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
-                                   new_bs, nullptr, 0.0f, nullptr, P4C_LOSS_MSE, mask_mode, nullptr, 0, nullptr, B, N, F, keep_prev,
-                                   x_next ? &nx : nullptr, stream, false);
+    const NextX nx = x_next ? NextX{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0} : NextX{};
+    return ar_update_loss_fwd_impl(StepFwd{prev, prev_bs, y, y_dtype, y_cs, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                           new_bs, nullptr, 0.0f, nullptr, P4C_LOSS_MSE, mask_mode, nullptr, 0, nullptr, B, N, F, keep_prev,
+                                           nx, FlatFront{}, false, stream});
 }
 
 // ------------------------------------------------------------------ output convolution + state update + loss in ONE pass
@@ -1719,93 +1754,62 @@ __global__ void __launch_bounds__(256) out_conv_update_loss_fwd_kernel(OutConvAr
     if (threadIdx.x == 0) g.partial[(int64_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+static int launch_out_conv(const StepFwd& s, const char* label, const char* final_label) {
+    const int FP4 = pow2_ge64(s.F / 4);
+    const int nblk = loss_blocks(s.N, 32, s.B);
+    const OutConvArgs g{s.front.a, s.front.a_scale, s.front.a_shift, s.front.wout, s.front.cout, s.prev, s.prev_bs, s.target, s.tgt_bs,
+                        s.std, s.mean, s.border_mask, s.interior_mask, s.new_state, s.new_bs, s.weights, s.kind, (float*)s.workspace,
+                        s.N, s.F, s.keep_prev, s.next};
+    with_flag(s.loss, [&](auto loss) -> int {
+        hipLaunchKernelGGL(out_conv_update_loss_fwd_kernel<decltype(loss)::value>, dim3(nblk, s.B), dim3(256), 0, as_stream(s.stream), g, FP4);
+        return P4C_OK;
+    });
+    P4C_CHECK_LAUNCH(label);
+    return s.loss ? loss_final(s, nblk, final_label) : P4C_OK;
+}
+
 // loss == false: the free step (p4c_out_conv_update_fwd) -- the LOSS = false instantiations, same form selection, no final kernel
-static int out_conv_update_impl(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
-                                const float* prev, int64_t prev_bs, const float* target, int64_t tgt_bs, const float* std,
-                                const float* mean, const float* border_mask, const float* interior_mask, float* new_state,
-                                int64_t new_bs, const float* weights, float num_interior, const int32_t* masked_count,
-                                int kind, float* loss_out, int64_t loss_stride, void* workspace, int B, int64_t N, int F,
-                                float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
-                                const float* forcing_next, int64_t forcing_bs, int Ff, void* lgrad, int64_t lgrad_bs,
-                                p4c_stream_t stream, bool loss) {
-    if (loss)
-        P4C_CHECK_ARG(a && a_scale && a_shift && wout && target && interior_mask && new_state && weights && loss_out && workspace,
+// (s.y is NULL, s.y_dtype bf16, s.y_cs 64, s.mask_mode NONE: the rows the front end forms)
+static int out_conv_update_impl(const StepFwd& s) {
+    const NextX& nx = s.next;
+    if (s.loss)
+        P4C_CHECK_ARG(s.front.a && s.front.a_scale && s.front.a_shift && s.front.wout && s.target && s.interior_mask && s.new_state &&
+                          s.weights && s.loss_out && s.workspace,
                       "p4c_out_conv_update_loss_fwd: null pointer");
     else
-        P4C_CHECK_ARG(a && a_scale && a_shift && wout && new_state && (target == nullptr) == (border_mask == nullptr) &&
-                          (!border_mask || interior_mask) && B > 0 && N > 0,
+        P4C_CHECK_ARG(s.front.a && s.front.a_scale && s.front.a_shift && s.front.wout && s.new_state &&
+                          (s.target == nullptr) == (s.border_mask == nullptr) && (!s.border_mask || s.interior_mask) && s.B > 0 && s.N > 0,
                       "p4c_out_conv_update_fwd: null pointer (target, border_mask and interior_mask go together)");
-    P4C_CHECK_ARG(prev || keep_prev == 0.0f, "p4c_out_conv_update_loss_fwd: prev is null but keep_prev != 0");
-    P4C_CHECK_ARG((std == nullptr) == (mean == nullptr), "p4c_out_conv_update_loss_fwd: std and mean go together");
-    P4C_CHECK_ARG(cout >= F && cout <= 64 && F > 0, "p4c_out_conv_update_loss_fwd: needs 0 < F <= cout <= 64");
-    P4C_CHECK_ARG(aligned16(a) && aligned16(wout), "p4c_out_conv_update_loss_fwd: a and wout must be 16-byte aligned");
+    P4C_CHECK_ARG(s.prev || s.keep_prev == 0.0f, "p4c_out_conv_update_loss_fwd: prev is null but keep_prev != 0");
+    P4C_CHECK_ARG((s.std == nullptr) == (s.mean == nullptr), "p4c_out_conv_update_loss_fwd: std and mean go together");
+    P4C_CHECK_ARG(s.front.cout >= s.F && s.front.cout <= 64 && s.F > 0, "p4c_out_conv_update_loss_fwd: needs 0 < F <= cout <= 64");
+    P4C_CHECK_ARG(aligned16(s.front.a) && aligned16(s.front.wout), "p4c_out_conv_update_loss_fwd: a and wout must be 16-byte aligned");
+    const char* final_label = "p4c_out_conv_update_loss_fwd(final)";
     // The flat AR-step kernel with the convolution as its front end serves ANY feature count -- and where both forms apply it is the
     // faster one (2 x 512 x 512 x 60: 127 against 138 us per launch, profiles/r04_step_ab_runs.txt block 21; same bits) -- so the
     // 16-byte form below is what is left when the flat path's conditions fail.  P4C_TAIL_V4=1: prefer the 16-byte form (A/B).
-    bool flat_possible = flat_ok(F, N, 64, 2) && prev_bs % 4 == 0 && tgt_bs % 4 == 0 && new_bs % 4 == 0 && aligned16(prev) && aligned16(target) &&
-                         aligned16(new_state);
-    if (flat_possible && x_next) flat_possible = statics && forcing_next && (c_pad * 2) % 16 == 0 && c_pad <= 256 && c_pad >= F + Fs + Ff && aligned16(x_next);
-    if (flat_possible && lgrad) flat_possible = lgrad_bs % 4 == 0 && (reinterpret_cast<uintptr_t>(lgrad) & 7) == 0;
+    // (Unlike the entry points above, this one learns of a missing statics / forcing_next only here: on the flat path a condition.)
+    const bool flat_possible = fwd_flat_ok(s) && (!nx.x || (nx.statics && nx.forcing));
     const char* tv4 = diag_env("P4C_TAIL_V4");
     const bool prefer_v4 = tv4 && tv4[0] == '1' && !force_flat();
-    if (F % 4 != 0 || force_flat() || (flat_possible && !prefer_v4)) {
-        const bool ok = flat_possible;
-        if (!ok && F % 4 != 0)
+    if (s.F % 4 != 0 || force_flat() || (flat_possible && !prefer_v4)) {
+        if (flat_possible)
+            return launch_fwd_flat(s, s.loss ? "p4c_out_conv_update_loss_fwd(flat)" : "p4c_out_conv_update_fwd(flat)", final_label);
+        if (s.F % 4 != 0)
             return fail(P4C_ERR_UNSUPPORTED, "p4c_out_conv_update_loss_fwd: F %% 4 != 0 needs the flat path (F <= 64, N * F %% 4 == 0, whole 16-byte "
                                              "slots per row of x_next, aligned rows)");
-        if (ok) {
-        const NextX nx{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs};
-        const FlatFront fa{(const bf16*)a, a_scale, a_shift, wout, cout};
-        const int64_t ntiles = (N + FLAT_P - 1) / FLAT_P;
-        int nblk = loss_blocks(N, FLAT_P / 4, B);
-        if (nblk > ntiles) nblk = (int)ntiles;
-        const size_t smem = (size_t)FLAT_P * 64 * 2 + (x_next ? (size_t)FLAT_P * c_pad * 2 : 0) + 5 * 64 * sizeof(float) + 2 * 4 * 64 * 16 +
-                            2 * 64 * sizeof(float);
-        if (!loss) {
-            P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16, true, false>, (int)smem));
-            hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<bf16, true, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream), prev,
-                               prev_bs, (const bf16*)nullptr, 64, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs,
-                               weights, kind, (float*)workspace, N, F, keep_prev, nx, fa);
-            P4C_CHECK_LAUNCH("p4c_out_conv_update_fwd(flat)");
-            return P4C_OK;
-        }
-        P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_fwd_flat_kernel<bf16, true>, (int)smem));
-        hipLaunchKernelGGL((ar_update_loss_fwd_flat_kernel<bf16, true>), dim3(nblk, B), dim3(256), smem, as_stream(stream), prev, prev_bs,
-                           (const bf16*)nullptr, 64, target, tgt_bs, std, mean, border_mask, interior_mask, new_state, new_bs, weights, kind,
-                           (float*)workspace, N, F, keep_prev, nx, fa);
-        P4C_CHECK_LAUNCH("p4c_out_conv_update_loss_fwd(flat)");
-        hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream), (const float*)workspace, nblk, num_interior,
-                           masked_count, loss_out, loss_stride, B);
-        P4C_CHECK_LAUNCH("p4c_out_conv_update_loss_fwd(final)");
-        return P4C_OK;
-        }
     }
-    P4C_CHECK_ARG(prev_bs % 4 == 0 && tgt_bs % 4 == 0 && new_bs % 4 == 0 && aligned16(prev) && aligned16(target) && aligned16(new_state) &&
-                      (!loss || aligned16(weights)) && aligned16(std) && aligned16(mean),
+    // the 16-byte form: the conditions of fwd_v4_ok (force_flat() aside), each refused under its own message
+    P4C_CHECK_ARG(state_rows16(s) && (!s.loss || aligned16(s.weights)) && aligned16(s.std) && aligned16(s.mean),
                   "p4c_out_conv_update_loss_fwd: rows must be 16-byte aligned (as p4c_ar_update_loss_fwd_next)");
-    if (x_next) {
-        P4C_CHECK_ARG(statics && forcing_next, "p4c_out_conv_update_loss_fwd: null pointer");
-        P4C_CHECK_ARG(c_pad % 4 == 0 && c_pad >= F + Fs + Ff && Fs % 4 == 0 && Fs >= 0 && Ff >= 0,
+    if (nx.x) {
+        P4C_CHECK_ARG(nx.statics && nx.forcing, "p4c_out_conv_update_loss_fwd: null pointer");
+        P4C_CHECK_ARG(nx.c_pad % 4 == 0 && nx.c_pad >= s.F + nx.Fs + nx.Ff && nx.Fs % 4 == 0 && nx.Fs >= 0 && nx.Ff >= 0,
                       "p4c_out_conv_update_loss_fwd: c_pad / Fs must be multiples of 4 and c_pad >= F + Fs + Ff");
-        P4C_CHECK_ARG(c_pad / 4 - F / 4 <= pow2_ge64(F / 4), "p4c_out_conv_update_loss_fwd: too many tail channels for one pass");
+        P4C_CHECK_ARG(nx.c_pad / 4 - s.F / 4 <= pow2_ge64(s.F / 4), "p4c_out_conv_update_loss_fwd: too many tail channels for one pass");
     }
-    P4C_CHECK_ARG(!lgrad || (lgrad_bs % 4 == 0 && aligned16(lgrad)), "p4c_out_conv_update_loss_fwd: lgrad must be 16-byte aligned rows");
-    const int FP4 = pow2_ge64(F / 4);
-    const int nblk = loss_blocks(N, 32, B);
-    OutConvArgs g{(const bf16*)a, a_scale, a_shift, wout, cout, prev, prev_bs, target, tgt_bs, std, mean, border_mask, interior_mask,
-                  new_state, new_bs, weights, kind, (float*)workspace, N, F, keep_prev,
-                  NextX{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs}};
-    if (!loss) {
-        hipLaunchKernelGGL(out_conv_update_loss_fwd_kernel<false>, dim3(nblk, B), dim3(256), 0, as_stream(stream), g, FP4);
-        P4C_CHECK_LAUNCH("p4c_out_conv_update_fwd");
-        return P4C_OK;
-    }
-    hipLaunchKernelGGL(out_conv_update_loss_fwd_kernel<true>, dim3(nblk, B), dim3(256), 0, as_stream(stream), g, FP4);
-    P4C_CHECK_LAUNCH("p4c_out_conv_update_loss_fwd");
-    hipLaunchKernelGGL(weighted_loss_final_kernel, dim3(B), dim3(64), 0, as_stream(stream), (const float*)workspace, nblk, num_interior,
-                       masked_count, loss_out, loss_stride, B);
-    P4C_CHECK_LAUNCH("p4c_out_conv_update_loss_fwd(final)");
-    return P4C_OK;
+    P4C_CHECK_ARG(!nx.lgrad || (nx.lgrad_bs % 4 == 0 && aligned16(nx.lgrad)), "p4c_out_conv_update_loss_fwd: lgrad must be 16-byte aligned rows");
+    return launch_out_conv(s, s.loss ? "p4c_out_conv_update_loss_fwd" : "p4c_out_conv_update_fwd", final_label);
 }
 
 extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale, const float* a_shift, const float* wout, int cout,
@@ -1816,10 +1820,11 @@ extern "C" int p4c_out_conv_update_loss_fwd(const void* a, const float* a_scale,
                                             float keep_prev, void* x_next, int c_pad, const float* statics, int64_t statics_bs, int Fs,
                                             const float* forcing_next, int64_t forcing_bs, int Ff, void* lgrad, int64_t lgrad_bs,
                                             p4c_stream_t stream) {
-    return out_conv_update_impl(a, a_scale, a_shift, wout, cout, prev, prev_bs, target, tgt_bs, std, mean, border_mask, interior_mask,
-                                new_state, new_bs, weights, num_interior, masked_count, kind, loss_out, loss_stride, workspace, B, N, F,
-                                keep_prev, x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs, stream,
-                                true);
+    return out_conv_update_impl(StepFwd{prev, prev_bs, nullptr, P4C_BF16, 64, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                        new_bs, weights, num_interior, masked_count, kind, P4C_MASK_NONE, loss_out, loss_stride, workspace,
+                                        B, N, F, keep_prev,
+                                        NextX{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, lgrad, lgrad_bs},
+                                        FlatFront{(const bf16*)a, a_scale, a_shift, wout, cout}, true, stream});
 }
 
 // The free step behind the fused 1x1 output convolution (see p4c_ar_update_next): same form selection and conditions as
@@ -1830,13 +1835,128 @@ extern "C" int p4c_out_conv_update_fwd(const void* a, const float* a_scale, cons
                                        int64_t new_bs, int B, int64_t N, int F, float keep_prev, void* x_next, int c_pad,
                                        const float* statics, int64_t statics_bs, int Fs, const float* forcing_next, int64_t forcing_bs,
                                        int Ff, p4c_stream_t stream) {
-    return out_conv_update_impl(a, a_scale, a_shift, wout, cout, prev, prev_bs, target, tgt_bs, std, mean, border_mask, interior_mask,
-                                new_state, new_bs, nullptr, 0.0f, nullptr, P4C_LOSS_MSE, nullptr, 0, nullptr, B, N, F, keep_prev, x_next,
-                                c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0, stream, false);
+    return out_conv_update_impl(StepFwd{prev, prev_bs, nullptr, P4C_BF16, 64, target, tgt_bs, std, mean, border_mask, interior_mask, new_state,
+                                        new_bs, nullptr, 0.0f, nullptr, P4C_LOSS_MSE, P4C_MASK_NONE, nullptr, 0, nullptr, B, N, F, keep_prev,
+                                        NextX{x_next, c_pad, statics, statics_bs, Fs, forcing_next, forcing_bs, Ff, nullptr, 0},
+                                        FlatFront{(const bf16*)a, a_scale, a_shift, wout, cout}, false, stream});
+}
+
+// ------------------------------------------------------------------ the AR step's backward
+// One backward step.  saved: p4c_ar_update_loss_bwd_saved -- `new_state` / `new_bs` are the bf16 rows of saved loss gradients (lgrad,
+// lgrad_bs), target is NULL (the SAVED instantiations).  loss == false: the adjoint of a free step (p4c_ar_update_next_bwd) -- the
+// LOSS = false instantiations, same path conditions.  There is no saved free step.
+struct StepBwd {
+    const float* g_next; int64_t g_next_bs; const void* g_next2; int g2_dtype; int g2_cs;
+    const float* gloss; int64_t gloss_stride;
+    const float* new_state; int64_t new_bs; const float* target; int64_t tgt_bs;
+    const float* std; const float* interior_mask; int force_border;
+    const float* weights; float num_interior; const int32_t* masked_count; int kind; int mask_mode;
+    void* dy; int dy_dtype; int y_cs; float* dprev; int64_t dprev_bs;
+    int B; int64_t N; int F; float keep_prev;
+    bool saved, loss;
+    p4c_stream_t stream;
+    int esz() const { return dy_dtype == P4C_BF16 ? 2 : 4; }
+};
+// the launch checks' names of one entry point, per path
+struct BwdLabels {
+    const char *v4, *flat, *scalar;
+};
+
+// ---- path predicates of a backward step
+// what both fast paths ask: batch strides in 16-byte pieces, aligned bases (a NULL g_next / g_next2 / dprev / target passes)
+static bool grad_rows16(const StepBwd& s) {
+    return s.g_next_bs % 4 == 0 && s.new_bs % 4 == 0 && s.tgt_bs % 4 == 0 && s.dprev_bs % 4 == 0 && aligned16(s.g_next) &&
+           aligned16(s.g_next2) && aligned16(s.target) && aligned16(s.dy) && aligned16(s.dprev);
+}
+// the 16-byte kernel.  (y_cs % 4 == 0 && y_cs / 4 <= 64 is the y_cs <= 256 the loss and the free step used to spell beside it.)
+static bool bwd_v4_ok(const StepBwd& s) {
+    return !force_flat() && rows_dtype(s.dy_dtype) && s.F % 4 == 0 && s.y_cs % 4 == 0 && s.y_cs / 4 <= 64 && s.g2_cs % 4 == 0 &&
+           grad_rows16(s) && aligned16(s.new_state) &&   // (saved: the bf16 rows too -- the flat path asks 8 bytes of them)
+           (!s.loss || aligned16(s.weights)) &&           // (the free step's adjoint reads no weights)
+           aligned16(s.std);
+}
+// the flat kernel: any other feature count (see ar_update_loss_bwd_flat_kernel)
+static bool bwd_flat_ok(const StepBwd& s) {
+    return rows_dtype(s.dy_dtype) && s.mask_mode == P4C_MASK_NONE && flat_ok(s.F, s.N, s.y_cs, s.esz()) &&
+           (!s.g_next2 || flat_ok(s.F, s.N, s.g2_cs, s.esz())) && grad_rows16(s) &&
+           (s.saved ? aligned8(s.new_state) : aligned16(s.new_state));   // the saved bf16 rows are read in 8-byte pieces, fp32 states in 16
+}
+
+// ---- the backward launch sites
+// SAVED without LOSS is no kernel: a free step saves no loss gradient
+template <typename Saved, typename Loss>
+static constexpr bool bwd_kernel_exists = Loss::value || !Saved::value;
+
+static int launch_bwd_v4(const StepBwd& s, const char* label) {
+    const int FP4 = pow2_ge64(s.y_cs / 4);
+    const int nblk = loss_blocks(s.N, 64 / FP4, s.B);
+    P4C_TRY(with_dtype_flags(s.dy_dtype, s.saved, s.loss, [&](auto ty, auto saved, auto loss) -> int {
+        using TY = typename decltype(ty)::type;
+        if constexpr (!bwd_kernel_exists<decltype(saved), decltype(loss)>) {
+            return fail(P4C_ERR_INVALID, "%s: a free step has no saved loss gradient", label);
+        } else {
+            hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<TY, decltype(saved)::value, decltype(loss)::value>), dim3(nblk, s.B), dim3(256), 0,
+                               as_stream(s.stream), s.g_next, s.g_next_bs, (const TY*)s.g_next2, s.g2_cs, s.gloss, s.gloss_stride,
+                               s.new_state, s.new_bs, s.target, s.tgt_bs, s.std, s.interior_mask, s.force_border, s.weights,
+                               s.num_interior, s.masked_count, s.kind, s.mask_mode, (TY*)s.dy, s.y_cs, s.dprev, s.dprev_bs, s.N, s.F,
+                               s.keep_prev, FP4);
+            return P4C_OK;
+        }
+    }));
+    P4C_CHECK_LAUNCH(label);
+    return P4C_OK;
+}
+
+static int launch_bwd_flat(const StepBwd& s, const char* label) {
+    const int nblk = flat_blocks(s.N, s.B);
+    const size_t smem = (size_t)FLAT_P * s.y_cs * s.esz() + (s.g_next2 ? (size_t)FLAT_P * s.g2_cs * s.esz() : 0) + 3 * 64 * sizeof(float);
+    P4C_TRY(with_dtype_flags(s.dy_dtype, s.saved, s.loss, [&](auto ty, auto saved, auto loss) -> int {
+        using TY = typename decltype(ty)::type;
+        if constexpr (!bwd_kernel_exists<decltype(saved), decltype(loss)>) {
+            return fail(P4C_ERR_INVALID, "%s: a free step has no saved loss gradient", label);
+        } else {
+            auto kernel = ar_update_loss_bwd_flat_kernel<TY, decltype(saved)::value, decltype(loss)::value>;
+            P4C_TRY(ensure_dyn_smem((const void*)kernel, (int)smem));
+            hipLaunchKernelGGL(kernel, dim3(nblk, s.B), dim3(256), smem, as_stream(s.stream), s.g_next, s.g_next_bs, (const TY*)s.g_next2,
+                               s.g2_cs, s.gloss, s.gloss_stride, s.new_state, s.new_bs, s.target, s.tgt_bs, s.std, s.interior_mask,
+                               s.force_border, s.weights, s.num_interior, s.masked_count, s.kind, (TY*)s.dy, s.y_cs, s.dprev, s.dprev_bs,
+                               s.N, s.F, s.keep_prev);
+            return P4C_OK;
+        }
+    }));
+    P4C_CHECK_LAUNCH(label);
+    return P4C_OK;
+}
+
+static int launch_bwd_scalar(const StepBwd& s, const char* label) {
+    const int FP = pow2_ge64(s.y_cs), iters = (s.y_cs + FP - 1) / FP;
+    P4C_CHECK_ARG(iters <= LOSS_MAX_ITERS, "p4c_ar_update_loss_bwd: y_cs too large");
+    const int nblk = loss_blocks(s.N, 64 / FP, s.B);
+    if (!rows_dtype(s.dy_dtype)) return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_bwd: bad dtype %d", s.dy_dtype);
+    with_dtype(s.dy_dtype, [&](auto ty) -> int { return with_flag(s.loss, [&](auto loss) -> int {
+        using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((ar_update_loss_bwd_kernel<TY, TY, decltype(loss)::value>), dim3(nblk, s.B), dim3(256), 0, as_stream(s.stream),
+                           s.g_next, s.g_next_bs, (const TY*)s.g_next2, s.g2_cs, s.gloss, s.gloss_stride, s.new_state, s.new_bs, s.target,
+                           s.tgt_bs, s.std, s.interior_mask, s.force_border, s.weights, s.num_interior, s.masked_count, s.kind,
+                           s.mask_mode, (TY*)s.dy, s.y_cs, s.dprev, s.dprev_bs, s.N, s.F, s.keep_prev, FP, iters);
+        return P4C_OK;
+    }); });
+    P4C_CHECK_LAUNCH(label);
+    return P4C_OK;
+}
+
+// the path selection of every backward step, after its entry point's argument checks
+static int step_bwd_launch(const StepBwd& s, const BwdLabels& labels) {
+    if (bwd_v4_ok(s)) return launch_bwd_v4(s, labels.v4);
+    if (bwd_flat_ok(s)) return launch_bwd_flat(s, labels.flat);
+    if (s.saved)   // (the scalar kernel has no SAVED instantiation)
+        return fail(P4C_ERR_UNSUPPORTED, "p4c_ar_update_loss_bwd_saved: needs the 16-byte path (F %% 4 == 0, aligned rows) or the flat path "
+                                         "(F <= 64, N * F %% 4 == 0, whole 16-byte slots per row, aligned rows, no NaN masks)");
+    return launch_bwd_scalar(s, labels.scalar);
 }
 
 // Backward of the fused step from the saved loss gradients (bf16 rows written by p4c_ar_update_loss_fwd_next_saved) instead of the
-// new state and the target: 120 instead of 480 bytes read per grid point at F = 60.  16-byte path only (F % 4 == 0, aligned rows).
+// new state and the target: 120 instead of 480 bytes read per grid point at F = 60.  16-byte or flat path only.
 extern "C" int p4c_ar_update_loss_bwd_saved(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype, int g2_cs,
                                             const float* gloss, int64_t gloss_stride, const void* lgrad, int64_t lgrad_bs,
                                             const float* std, const float* interior_mask, int force_border, const float* weights,
@@ -1846,164 +1966,24 @@ extern "C" int p4c_ar_update_loss_bwd_saved(const float* g_next, int64_t g_next_
     P4C_CHECK_ARG(lgrad && interior_mask && weights && dy, "p4c_ar_update_loss_bwd_saved: null pointer");
     P4C_CHECK_ARG(F > 0 && y_cs >= F && (dy_dtype == P4C_F32 || dy_dtype == P4C_BF16), "p4c_ar_update_loss_bwd_saved: bad F / y_cs / dtype");
     P4C_CHECK_ARG(dy_dtype == g2_dtype || !g_next2, "p4c_ar_update_loss_bwd_saved: g_next2 dtype must equal dy dtype");
-    const bool ok = !force_flat() && F % 4 == 0 && y_cs % 4 == 0 && y_cs / 4 <= 64 && g_next_bs % 4 == 0 && lgrad_bs % 4 == 0 && dprev_bs % 4 == 0 &&
-                    g2_cs % 4 == 0 && aligned16(g_next) && aligned16(g_next2) && aligned16(lgrad) && aligned16(dy) && aligned16(dprev) &&
-                    aligned16(weights) && aligned16(std);
-    if (!ok) {   // any other feature count: the flat kernel
-        const int esz = dy_dtype == P4C_BF16 ? 2 : 4;
-        const bool fok = mask_mode == P4C_MASK_NONE && flat_ok(F, N, y_cs, esz) && (!g_next2 || flat_ok(F, N, g2_cs, esz)) && g_next_bs % 4 == 0 &&
-                         lgrad_bs % 4 == 0 && dprev_bs % 4 == 0 && aligned16(g_next) && aligned16(g_next2) &&
-                         (reinterpret_cast<uintptr_t>(lgrad) & 7) == 0 && aligned16(dy) && aligned16(dprev);
-        if (!fok)
-            return fail(P4C_ERR_UNSUPPORTED, "p4c_ar_update_loss_bwd_saved: needs the 16-byte path (F %% 4 == 0, aligned rows) or the flat path "
-                                             "(F <= 64, N * F %% 4 == 0, whole 16-byte slots per row, aligned rows, no NaN masks)");
-        const int64_t ntiles = (N + FLAT_P - 1) / FLAT_P;
-        int nblk = loss_blocks(N, FLAT_P / 4, B);
-        if (nblk > ntiles) nblk = (int)ntiles;
-        const size_t smem = (size_t)FLAT_P * y_cs * esz + (g_next2 ? (size_t)FLAT_P * g2_cs * esz : 0) + 3 * 64 * sizeof(float);
-        if (dy_dtype == P4C_F32) {
-            P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<float, true>, (int)smem));
-            hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<float, true>), dim3(nblk, B), dim3(256), smem, as_stream(stream), g_next, g_next_bs,
-                               (const float*)g_next2, g2_cs, gloss, gloss_stride, (const float*)lgrad, lgrad_bs, nullptr, 0, std, interior_mask,
-                               force_border, weights, num_interior, masked_count, kind, (float*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev);
-        } else {
-            P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<bf16, true>, (int)smem));
-            hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<bf16, true>), dim3(nblk, B), dim3(256), smem, as_stream(stream), g_next, g_next_bs,
-                               (const bf16*)g_next2, g2_cs, gloss, gloss_stride, (const float*)lgrad, lgrad_bs, nullptr, 0, std, interior_mask,
-                               force_border, weights, num_interior, masked_count, kind, (bf16*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev);
-        }
-        P4C_CHECK_LAUNCH("p4c_ar_update_loss_bwd_saved(flat)");
-        return P4C_OK;
-    }
-    const int FP4 = pow2_ge64(y_cs / 4);
-    const int nblk4 = loss_blocks(N, 64 / FP4, B);
-    if (dy_dtype == P4C_F32)
-        hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<float, true>), dim3(nblk4, B), dim3(256), 0, as_stream(stream), g_next, g_next_bs,
-                           (const float*)g_next2, g2_cs, gloss, gloss_stride, (const float*)lgrad, lgrad_bs, nullptr, 0, std, interior_mask,
-                           force_border, weights, num_interior, masked_count, kind, mask_mode, (float*)dy, y_cs, dprev, dprev_bs, N, F,
-                           keep_prev, FP4);
-    else
-        hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<bf16, true>), dim3(nblk4, B), dim3(256), 0, as_stream(stream), g_next, g_next_bs,
-                           (const bf16*)g_next2, g2_cs, gloss, gloss_stride, (const float*)lgrad, lgrad_bs, nullptr, 0, std, interior_mask,
-                           force_border, weights, num_interior, masked_count, kind, mask_mode, (bf16*)dy, y_cs, dprev, dprev_bs, N, F,
-                           keep_prev, FP4);
-    P4C_CHECK_LAUNCH("p4c_ar_update_loss_bwd_saved");
-    return P4C_OK;
+    return step_bwd_launch(StepBwd{g_next, g_next_bs, g_next2, g2_dtype, g2_cs, gloss, gloss_stride, (const float*)lgrad, lgrad_bs, nullptr, 0,
+                                   std, interior_mask, force_border, weights, num_interior, masked_count, kind, mask_mode, dy, dy_dtype,
+                                   y_cs, dprev, dprev_bs, B, N, F, keep_prev, true, true, stream},
+                           BwdLabels{"p4c_ar_update_loss_bwd_saved", "p4c_ar_update_loss_bwd_saved(flat)", nullptr});
 }
 
-// loss == false: the adjoint of a free step (p4c_ar_update_next_bwd) -- the LOSS = false instantiations, same path conditions
-static int ar_update_loss_bwd_impl(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype,
-                                   int g2_cs, const float* gloss, int64_t gloss_stride, const float* new_state,
-                                   int64_t new_bs, const float* target, int64_t tgt_bs, const float* std,
-                                   const float* interior_mask, int force_border, const float* weights,
-                                   float num_interior, const int32_t* masked_count, int kind, int mask_mode,
-                                   void* dy, int dy_dtype, int y_cs, float* dprev, int64_t dprev_bs, int B,
-                                   int64_t N, int F, float keep_prev, p4c_stream_t stream, bool loss) {
-    if (loss)
-        P4C_CHECK_ARG(new_state && target && interior_mask && weights && dy, "p4c_ar_update_loss_bwd: null pointer");
+static int ar_update_loss_bwd_impl(const StepBwd& s) {
+    if (s.loss)
+        P4C_CHECK_ARG(s.new_state && s.target && s.interior_mask && s.weights && s.dy, "p4c_ar_update_loss_bwd: null pointer");
     else
-        P4C_CHECK_ARG(dy && (!force_border || interior_mask) && B > 0 && N > 0,
+        P4C_CHECK_ARG(s.dy && (!s.force_border || s.interior_mask) && s.B > 0 && s.N > 0,
                       "p4c_ar_update_next_bwd: null pointer (a forced border needs interior_mask)");
-    P4C_CHECK_ARG(mask_mode == P4C_MASK_NONE || mask_mode == P4C_MASK_FROM_NAN,
+    P4C_CHECK_ARG(s.mask_mode == P4C_MASK_NONE || s.mask_mode == P4C_MASK_FROM_NAN,
                   "p4c_ar_update_loss_bwd: only MASK_NONE / MASK_FROM_NAN are fused");
-    P4C_CHECK_ARG(F > 0 && F <= 64 * LOSS_MAX_ITERS && y_cs >= F, "p4c_ar_update_loss_bwd: bad F / y_cs");
-    P4C_CHECK_ARG(dy_dtype == g2_dtype || !g_next2, "p4c_ar_update_loss_bwd: g_next2 dtype must equal dy dtype");
-    if (!force_flat() && (dy_dtype == P4C_F32 || dy_dtype == P4C_BF16) && F % 4 == 0 && y_cs % 4 == 0 && y_cs <= 256 && g_next_bs % 4 == 0 && new_bs % 4 == 0 &&
-        tgt_bs % 4 == 0 && dprev_bs % 4 == 0 && g2_cs % 4 == 0 && aligned16(g_next) && aligned16(g_next2) &&
-        aligned16(new_state) && aligned16(target) && aligned16(dy) && aligned16(dprev) && (!loss || aligned16(weights)) &&
-        aligned16(std)) {
-        const int FP4 = pow2_ge64(y_cs / 4);
-        if (y_cs / 4 <= 64) {
-            const int nblk4 = loss_blocks(N, 64 / FP4, B);
-            if (!loss) {
-                if (dy_dtype == P4C_F32)
-                    hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<float, false, false>), dim3(nblk4, B), dim3(256), 0, as_stream(stream),
-                                       g_next, g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
-                                       tgt_bs, std, interior_mask, force_border, weights, num_interior, masked_count, kind,
-                                       mask_mode, (float*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev, FP4);
-                else
-                    hipLaunchKernelGGL((ar_update_loss_bwd_v4_kernel<bf16, false, false>), dim3(nblk4, B), dim3(256), 0, as_stream(stream),
-                                       g_next, g_next_bs, (const bf16*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
-                                       tgt_bs, std, interior_mask, force_border, weights, num_interior, masked_count, kind,
-                                       mask_mode, (bf16*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev, FP4);
-                P4C_CHECK_LAUNCH("p4c_ar_update_next_bwd(v4)");
-                return P4C_OK;
-            }
-            if (dy_dtype == P4C_F32)
-                hipLaunchKernelGGL(ar_update_loss_bwd_v4_kernel<float>, dim3(nblk4, B), dim3(256), 0, as_stream(stream), g_next,
-                                   g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
-                                   tgt_bs, std, interior_mask, force_border, weights, num_interior, masked_count, kind,
-                                   mask_mode, (float*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev, FP4);
-            else
-                hipLaunchKernelGGL(ar_update_loss_bwd_v4_kernel<bf16>, dim3(nblk4, B), dim3(256), 0, as_stream(stream), g_next,
-                                   g_next_bs, (const bf16*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target,
-                                   tgt_bs, std, interior_mask, force_border, weights, num_interior, masked_count, kind,
-                                   mask_mode, (bf16*)dy, y_cs, dprev, dprev_bs, N, F, keep_prev, FP4);
-            P4C_CHECK_LAUNCH("p4c_ar_update_loss_bwd(v4)");
-            return P4C_OK;
-        }
-    }
-    {   // any other feature count: the flat kernel (see ar_update_loss_bwd_flat_kernel)
-        const int esz = dy_dtype == P4C_BF16 ? 2 : 4;
-        if ((dy_dtype == P4C_F32 || dy_dtype == P4C_BF16) && mask_mode == P4C_MASK_NONE && flat_ok(F, N, y_cs, esz) &&
-            (!g_next2 || flat_ok(F, N, g2_cs, esz)) && g_next_bs % 4 == 0 && new_bs % 4 == 0 && tgt_bs % 4 == 0 && dprev_bs % 4 == 0 &&
-            aligned16(g_next) && aligned16(g_next2) && aligned16(new_state) && aligned16(target) && aligned16(dy) && aligned16(dprev)) {
-            const int64_t ntiles = (N + FLAT_P - 1) / FLAT_P;
-            int nblk = loss_blocks(N, FLAT_P / 4, B);
-            if (nblk > ntiles) nblk = (int)ntiles;
-            const size_t smem = (size_t)FLAT_P * y_cs * esz + (g_next2 ? (size_t)FLAT_P * g2_cs * esz : 0) + 3 * 64 * sizeof(float);
-            if (!loss) {
-                if (dy_dtype == P4C_F32) {
-                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<float, false, false>, (int)smem));
-                    hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<float, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
-                                       g_next, g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,
-                                       std, interior_mask, force_border, weights, num_interior, masked_count, kind, (float*)dy, y_cs, dprev,
-                                       dprev_bs, N, F, keep_prev);
-                } else {
-                    P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<bf16, false, false>, (int)smem));
-                    hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<bf16, false, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream),
-                                       g_next, g_next_bs, (const bf16*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,
-                                       std, interior_mask, force_border, weights, num_interior, masked_count, kind, (bf16*)dy, y_cs, dprev,
-                                       dprev_bs, N, F, keep_prev);
-                }
-                P4C_CHECK_LAUNCH("p4c_ar_update_next_bwd(flat)");
-                return P4C_OK;
-            }
-            if (dy_dtype == P4C_F32) {
-                P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<float, false>, (int)smem));
-                hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<float, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream), g_next,
-                                   g_next_bs, (const float*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs, std,
-                                   interior_mask, force_border, weights, num_interior, masked_count, kind, (float*)dy, y_cs, dprev, dprev_bs, N,
-                                   F, keep_prev);
-            } else {
-                P4C_TRY(ensure_dyn_smem((const void*)ar_update_loss_bwd_flat_kernel<bf16, false>, (int)smem));
-                hipLaunchKernelGGL((ar_update_loss_bwd_flat_kernel<bf16, false>), dim3(nblk, B), dim3(256), smem, as_stream(stream), g_next,
-                                   g_next_bs, (const bf16*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs, std,
-                                   interior_mask, force_border, weights, num_interior, masked_count, kind, (bf16*)dy, y_cs, dprev, dprev_bs, N,
-                                   F, keep_prev);
-            }
-            P4C_CHECK_LAUNCH("p4c_ar_update_loss_bwd(flat)");
-            return P4C_OK;
-        }
-    }
-    const int FP = pow2_ge64(y_cs), iters = (y_cs + FP - 1) / FP;
-    P4C_CHECK_ARG(iters <= LOSS_MAX_ITERS, "p4c_ar_update_loss_bwd: y_cs too large");
-    const int nblk = loss_blocks(N, 64 / FP, B);
-#define P4C_LAUNCH_BWD(TY, LOSSF)                                                                                       \
-    hipLaunchKernelGGL((ar_update_loss_bwd_kernel<TY, TY, LOSSF>), dim3(nblk, B), dim3(256), 0, as_stream(stream), g_next, \
-                       g_next_bs, (const TY*)g_next2, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,    \
-                       std, interior_mask, force_border, weights, num_interior, masked_count, kind, mask_mode, (TY*)dy, \
-                       y_cs, dprev, dprev_bs, N, F, keep_prev, FP, iters)
-    if (dy_dtype != P4C_F32 && dy_dtype != P4C_BF16) return fail(P4C_ERR_INVALID, "p4c_ar_update_loss_bwd: bad dtype %d", dy_dtype);
-    if (!loss) {
-        if (dy_dtype == P4C_F32) P4C_LAUNCH_BWD(float, false); else P4C_LAUNCH_BWD(bf16, false);
-        P4C_CHECK_LAUNCH("p4c_ar_update_next_bwd");
-        return P4C_OK;
-    }
-    if (dy_dtype == P4C_F32) P4C_LAUNCH_BWD(float, true); else P4C_LAUNCH_BWD(bf16, true);
-#undef P4C_LAUNCH_BWD
-    P4C_CHECK_LAUNCH("p4c_ar_update_loss_bwd");
-    return P4C_OK;
+    P4C_CHECK_ARG(s.F > 0 && s.F <= 64 * LOSS_MAX_ITERS && s.y_cs >= s.F, "p4c_ar_update_loss_bwd: bad F / y_cs");
+    P4C_CHECK_ARG(s.dy_dtype == s.g2_dtype || !s.g_next2, "p4c_ar_update_loss_bwd: g_next2 dtype must equal dy dtype");
+    return step_bwd_launch(s, s.loss ? BwdLabels{"p4c_ar_update_loss_bwd(v4)", "p4c_ar_update_loss_bwd(flat)", "p4c_ar_update_loss_bwd"}
+                                     : BwdLabels{"p4c_ar_update_next_bwd(v4)", "p4c_ar_update_next_bwd(flat)", "p4c_ar_update_next_bwd"});
 }
 
 extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype,
@@ -2013,9 +1993,9 @@ extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, co
                                       float num_interior, const int32_t* masked_count, int kind, int mask_mode,
                                       void* dy, int dy_dtype, int y_cs, float* dprev, int64_t dprev_bs, int B,
                                       int64_t N, int F, float keep_prev, p4c_stream_t stream) {
-    return ar_update_loss_bwd_impl(g_next, g_next_bs, g_next2, g2_dtype, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs, std,
-                                   interior_mask, force_border, weights, num_interior, masked_count, kind, mask_mode, dy, dy_dtype, y_cs,
-                                   dprev, dprev_bs, B, N, F, keep_prev, stream, true);
+    return ar_update_loss_bwd_impl(StepBwd{g_next, g_next_bs, g_next2, g2_dtype, g2_cs, gloss, gloss_stride, new_state, new_bs, target, tgt_bs,
+                                           std, interior_mask, force_border, weights, num_interior, masked_count, kind, mask_mode, dy,
+                                           dy_dtype, y_cs, dprev, dprev_bs, B, N, F, keep_prev, false, true, stream});
 }
 
 // Backward of the free step (p4c_ar_update_next / p4c_out_conv_update_fwd): with g = g_next + g_next2 the gradient arriving at the
@@ -2025,7 +2005,7 @@ extern "C" int p4c_ar_update_loss_bwd(const float* g_next, int64_t g_next_bs, co
 extern "C" int p4c_ar_update_next_bwd(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype, int g2_cs,
                                       const float* std, const float* interior_mask, int force_border, void* dy, int dy_dtype, int y_cs,
                                       float* dprev, int64_t dprev_bs, int B, int64_t N, int F, float keep_prev, p4c_stream_t stream) {
-    return ar_update_loss_bwd_impl(g_next, g_next_bs, g_next2, g2_dtype, g2_cs, nullptr, 0, nullptr, 0, nullptr, 0, std, interior_mask,
-                                   force_border, nullptr, 1.0f, nullptr, P4C_LOSS_MSE, P4C_MASK_NONE, dy, dy_dtype, y_cs, dprev, dprev_bs, B,
-                                   N, F, keep_prev, stream, false);
+    return ar_update_loss_bwd_impl(StepBwd{g_next, g_next_bs, g_next2, g2_dtype, g2_cs, nullptr, 0, nullptr, 0, nullptr, 0, std, interior_mask,
+                                           force_border, nullptr, 1.0f, nullptr, P4C_LOSS_MSE, P4C_MASK_NONE, dy, dy_dtype, y_cs, dprev,
+                                           dprev_bs, B, N, F, keep_prev, false, false, stream});
 }

@@ -488,6 +488,7 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         target, no loss, state kept in scratch: p4c_ar_update_next / p4c_out_conv_update_fwd), the K-th is the loss step above.
         ``phase == "inference"``: a forward-only forecast of free steps without border forcing (``_native_forecast``), a plain tensor.
         """
+        from .halfunet_rollout import _NativeRolloutFn
         from .losses import WeightedLoss
 
         if batch.inputs.tensor.dim() != 5:
@@ -521,87 +522,10 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         return pred
 
     def _native_forecast(self, lm, batch, std, mean, K):
-        """Forward-only native forecast (phase "inference", lightning.py:565-662 with ``inference``): T * K model calls, every one a
-        free step without border forcing (:627) -- no autograd node, one ``saved`` buffer for all calls, states written straight into
-        the (B,T,H,W,F) result (intermediary states of K >= 2 through two scratch buffers).  T comes from the forcing tensor
-        (``batch.outputs`` is None).  T_in >= 2: the window buffer of the training rollout with p4c_build_x per call.  Returns None
-        where ``native_rollout`` does (padded grids, channel mismatch)."""
-        inputs, forcing = batch.inputs.tensor, batch.forcing.tensor
-        if forcing.dim() != 5:
-            return None
-        B, T_in, H, W, F = inputs.shape
-        T = forcing.shape[1]
-        statics = lm.grid_static_features[: batch.batch_size]
-        Fs, Ff = statics.shape[-1], forcing.shape[-1]
-        mask_on_nan = int(bool(lm.mask_on_nan))
-        if T_in * F + Fs + Ff + mask_on_nan != self.in_channels or F > self.out_channels or (K > 1 and T_in > 1):
-            return None
-        if any(self.padding_for(H, W)):
-            return None
-        L.require_cuda(inputs, forcing)
-        dev = inputs.device
-        N = H * W
-        with torch.no_grad():
-            self._running = self._running_stats(dev)
-            training = self.training
-            if training and self._settings.norm == "batch":
-                torch._foreach_add_([nb.num_batches_tracked for nb in self._norms], T * K)
-            inputs, forcing = inputs.float().contiguous(), forcing.float().contiguous()
-            st = statics.float()
-            sbs = 0 if st.stride(0) == 0 else N * Fs
-            st = st[0].contiguous() if sbs == 0 else st.contiguous()
-            desc = self._desc(B, H, W)
-            flat = self._flat_params()
-            saved_bytes, scratch = self._workspaces(desc, dev)
-            cpad = self.cin_pad
-            adt, acode = self.act_dtype, L.dtype_code(self.act_dtype)
-            stream = L.stream(dev)
-            L.call("p4c_halfunet_prepare_weights", ctypes.byref(desc), L.ptr(flat), L.ptr(scratch), stream)
-            desc.weights_prepared = 1
-            feed, v4_next, flat_next = _step_paths(self, T_in, N, F, Fs, mask_on_nan)
-            fuse_next = feed and (v4_next or flat_next)
-            fused_tail = _fused_tail(self, v4_next, flat_next, F, mask_on_nan)
-            if fused_tail:
-                desc.skip_out_conv = 1
-            if feed:
-                pred, sbs_state = torch.empty(B, T, H, W, F, dtype=torch.float32, device=dev), T * N * F
-                states = None
-            else:
-                states = torch.empty(B, T_in + T, H, W, F, dtype=torch.float32, device=dev)
-                states[:, :T_in].copy_(inputs)
-                pred, sbs_state = states[:, T_in:], (T_in + T) * N * F
-            inter = [torch.empty(B, H, W, F, dtype=torch.float32, device=dev) for _ in range(min(2, K - 1))]
-            saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-            y = None if fused_tail else torch.empty(B, H, W, NF, dtype=adt, device=dev)
-            xbuf = [torch.empty(B, H, W, cpad, dtype=adt, device=dev) for _ in range(2 if fuse_next else 1)]
-            x_next = None
-            ncalls = T * K
-            for c in range(ncalls):
-                i, k = divmod(c, K)
-                if not feed:
-                    prev, sbs_prev = states[:, i + T_in - 1], sbs_state
-                elif c == 0:
-                    prev, sbs_prev = inputs[:, 0], T_in * N * F
-                elif k == 0:
-                    prev, sbs_prev = pred[:, i - 1], sbs_state
-                else:
-                    prev, sbs_prev = inter[(k - 1) % 2], N * F
-                new, sbs_new = (pred[:, i], sbs_state) if k == K - 1 else (inter[k % 2], N * F)
-                if x_next is not None:
-                    x = x_next
-                else:
-                    x = xbuf[c % len(xbuf)]
-                    win, sbs_win = (prev, sbs_prev) if feed else (states[:, i], sbs_state)
-                    L.call("p4c_build_x", L.ptr(win), sbs_win, N * F, L.ptr(st), sbs, L.ptr(forcing[:, i]), T * N * Ff,
-                           L.ptr(x), acode, cpad, B, T_in, N, F, Fs, Ff, mask_on_nan, 0, stream)
-                L.call("p4c_halfunet_forward", ctypes.byref(desc), L.ptr(x), L.ptr(flat), L.ptr(self._running), L.ptr(y),
-                       L.ptr(saved), L.ptr(scratch), int(training), stream)
-                # the next call's input: the same forcing step for an intermediary call, the next one after the K-th
-                x_next = xbuf[(c + 1) % 2] if (fuse_next and c + 1 < ncalls) else None
-                nf = forcing[:, i if k < K - 1 else i + 1] if x_next is not None else None
-                _free_step(self, desc, flat, saved, y, fused_tail, prev, sbs_prev, None, 0, std, mean, None, None, new, sbs_new,
-                           mask_on_nan, B, N, F, x_next, cpad, st, sbs, Fs, nf, T * N * Ff, Ff, stream)
-            return pred if feed else pred.contiguous()
+        """Forward-only native forecast (phase "inference"): see ``halfunet_rollout.native_forecast``."""
+        from .halfunet_rollout import native_forecast
+
+        return native_forecast(self, lm, batch, std, mean, K)
 
     def roofline(self, ktimes, B, H, W):
         """bench.py: achieved rate of the dominant kernel (conv 3x3 64->64 at full resolution) from the per-launch
@@ -708,364 +632,3 @@ class HalfUNetMI355X(ModelABC, nn.Module):
             L.lib().p4c_prof_collect(tag, B * H * W, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(units))
             out[key] = (ms.value / n.value) if n.value else None
         return out
-
-
-def _step_paths(model, T_in, N, F, Fs, mask_on_nan):
-    """(feed, v4_next, flat_next): whether the AR step's kernel also writes the next network input ("feed next step": one input
-    state, otherwise p4c_build_x builds the window), and which of the step kernels' two fast paths the shape takes -- the conditions
-    of csrc/losses.hip, stated once for the training rollout and the forecast."""
-    cpad = model.cin_pad
-    feed = T_in == 1
-    lanes = 1
-    while lanes < F // 4:
-        lanes *= 2  # lanes per grid point of the 16-byte update kernel; each also owns one tail quad of x_next
-    v4_next = ((not mask_on_nan) and F % 4 == 0 and F <= 64
-               and (not feed or (Fs % 4 == 0 and cpad % 4 == 0 and cpad // 4 - F // 4 <= lanes)))
-    # any other feature count (the shipped Titan configuration has 21 features): the flat kernels of csrc/losses.hip -- (N, F)
-    # arrays streamed flat, the network's row tensors through LDS tiles -- take the same fused step
-    esz = 2 if model.act_dtype == torch.bfloat16 else 4
-    flat_next = ((not mask_on_nan) and F <= 64 and (N * F) % 4 == 0 and (cpad * esz) % 16 == 0 and cpad <= 256
-                 and L.diag_switch("P4C_NO_FLAT_STEP") != "1")
-    return feed, v4_next, flat_next
-
-
-def _fused_tail(model, v4_next, flat_next, F, mask_on_nan):
-    """bf16 flavour: the network's 1x1 output convolution runs INSIDE the AR step's kernel (p4c_out_conv_update_loss_fwd /
-    p4c_out_conv_update_fwd: y is never written and read back, one launch less per AR step; same new state bit for bit;
-    P4C_FUSED_TAIL=0: the two-kernel route).  (Feature counts off the 16-byte grid: the flat kernel takes the convolution as its
-    front end.)"""
-    return (model.act_dtype == torch.bfloat16 and (v4_next or (flat_next and F % 4 != 0)) and not mask_on_nan
-            and model.out_channels >= F and L.diag_switch("P4C_FUSED_TAIL") != "0")
-
-
-def _free_step(model, desc, flat, saved, y, fused_tail, prev, sbs_prev, target, sbs_tgt, std, mean, border, interior, new, sbs_new,
-               nan_to_num, B, N, F, x_next, cpad, st, sbs, Fs, forcing_next, sbs_forc, Ff, stream):
-    """One AR step without a loss term (an intermediary call of num_inter_steps >= 2, an inference call): the update, the border
-    forcing where ``target`` / ``border`` / ``interior`` are given, optionally the next network input -- behind the fused 1x1 output
-    convolution where the fused tail applies."""
-    if fused_tail:
-        ta, tsc, tsh, tw = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        L.call("p4c_halfunet_tail", ctypes.byref(desc), L.ptr(flat), L.ptr(saved), ctypes.byref(ta), ctypes.byref(tsc),
-               ctypes.byref(tsh), ctypes.byref(tw))
-        L.call("p4c_out_conv_update_fwd", ta, tsc, tsh, tw, model.out_channels, L.ptr(prev), sbs_prev, L.ptr(target), sbs_tgt,
-               L.ptr(std), L.ptr(mean), L.ptr(border), L.ptr(interior), L.ptr(new), sbs_new, B, N, F, 1.0,
-               L.ptr(x_next), cpad, L.ptr(st), sbs, Fs, L.ptr(forcing_next), sbs_forc, Ff, stream)
-    else:
-        L.call("p4c_ar_update_next", L.ptr(prev), sbs_prev, L.ptr(y), L.dtype_code(model.act_dtype), NF, L.ptr(target), sbs_tgt,
-               L.ptr(std), L.ptr(mean), L.ptr(border), L.ptr(interior), L.ptr(new), sbs_new, int(nan_to_num), B, N, F, 1.0,
-               L.ptr(x_next), cpad, L.ptr(st), sbs, Fs, L.ptr(forcing_next), sbs_forc, Ff, stream)
-
-
-class _NativeRolloutFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, lm, inputs, forcing, outputs, statics, std, mean, border_flat, interior_flat, force_border,
-                weights, num_interior, kind, mask_mode, training, keep_saved, K, *params):
-        L.require_cuda(inputs, forcing, outputs)
-        dev = inputs.device
-        B, T = outputs.shape[0], outputs.shape[1]
-        T_in, H, W, F = inputs.shape[1], inputs.shape[2], inputs.shape[3], inputs.shape[4]
-        N = H * W
-        Fs, Ff = statics.shape[-1], forcing.shape[-1]
-        inputs, forcing, outputs = inputs.float().contiguous(), forcing.float().contiguous(), outputs.float().contiguous()
-        st = statics.float()
-        sbs = 0 if st.stride(0) == 0 else N * Fs
-        st = st[0].contiguous() if sbs == 0 else st.contiguous()
-        desc = model._desc(B, H, W)
-        if T_in > 1:
-            desc.dx_channels = T_in * F   # the window of past states: the gradient the sweep reads
-        elif desc.dx_channels > NF:
-            desc.dx_channels = F   # one input state (F <= out_channels <= 64): its gradient is all the sweep reads
-        flat = model._flat_params()
-        saved_bytes, scratch = model._workspaces(desc, dev)
-        cpad = model.cin_pad
-        mask_on_nan = int(mask_mode == L.MASK_FROM_NAN)
-        count = None
-        if mask_on_nan:
-            count = torch.empty(1, dtype=torch.int32, device=dev)
-            L.call("p4c_mask_all_zero_count", L.ptr(outputs), mask_mode, T * N * F, N * F, B, T, N, F, L.ptr(count), L.stream(dev))
-        # state buffer: slot 0 = input state, slot i+1 = new state of AR step i (= prediction[:, i])
-        # (slot 0 is never written: AR step 0 reads the batch's input state where it lies -- every kernel takes the previous
-        # state's batch stride separately -- which saves a 126 MB copy per rollout at the benchmark size)
-        # (T_in >= 2: slots 0 .. T_in-1 hold the input states, copied once; slot T_in + i = new state of AR step i, and the input of
-        # step i is the window of slots i .. i+T_in-1)
-        states = torch.empty(B, T_in + T, H, W, F, dtype=torch.float32, device=dev)
-        if T_in > 1:
-            states[:, :T_in].copy_(inputs)
-        sbs_state = (T_in + T) * N * F
-        sbs_input = inputs.shape[1] * N * F
-        loss = torch.empty(B, T, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.lib().p4c_loss_workspace_bytes(B, 1, N, 1) // 4, dtype=torch.float32, device=dev)
-        xs, saveds = [], []
-        adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
-        y = torch.empty(B, H, W, NF, dtype=adt, device=dev)
-        stream = L.stream(dev)
-        saved = None
-        # the parameters are fixed for the whole rollout: re-lay / round the weights once, not once per AR step
-        L.call("p4c_halfunet_prepare_weights", ctypes.byref(desc), L.ptr(flat), L.ptr(scratch), stream)
-        desc.weights_prepared = 1
-        # "feed next step" fused: the update kernel of step i also writes step i+1's network input (new state | statics |
-        # next forcing | padding), so only step 0 runs p4c_build_x.  (The NaN-mask input channel needs p4c_build_x.)
-        # (T_in >= 2: the next input is a window of several states, built by p4c_build_x; the update kernels run without x_next)
-        feed, v4_next, flat_next = _step_paths(model, T_in, N, F, Fs, mask_on_nan)
-        step_capable = v4_next or flat_next
-        fuse_next = feed and step_capable
-        x_next = None
-        # bf16 flavour, training: the update kernel also saves the loss gradient of every element as bf16 rows and the backward reads
-        # those instead of the new state and the target (480 -> 120 bytes per grid point; P4C_SAVE_LOSS_GRAD=0: recompute)
-        save_lg = (keep_saved and adt == torch.bfloat16 and step_capable and mask_mode == L.MASK_NONE
-                   and L.diag_switch("P4C_SAVE_LOSS_GRAD") != "0")
-        lgrads = torch.empty(T, B, N, F, dtype=torch.bfloat16, device=dev) if save_lg else None
-        fused_tail = _fused_tail(model, v4_next, flat_next, F, mask_on_nan)
-        desc_fwd = desc
-        if fused_tail:
-            desc_fwd = HalfUNetDesc.from_buffer_copy(desc)
-            desc_fwd.skip_out_conv = 1
-        # The schedule: T * K model calls.  Call (i, k) with k < K - 1 is a FREE step -- forced to outputs[:, i] at the border, no loss,
-        # its state not part of the prediction (lightning.py:583-658): it goes to a scratch ring of two buffers, and its next input
-        # takes forcing[:, i] again (_next_x(batch, prev_states, i) for every k); call (i, K - 1) is the loss step, writes prediction
-        # slot i, and its next input takes forcing[:, i + 1].  Only activations (xs / saveds) are kept per call for the reverse sweep.
-        inter = [torch.empty(B, H, W, F, dtype=torch.float32, device=dev) for _ in range(min(2, K - 1))]
-        for c in range(T * K):
-            i, k = divmod(c, K)
-            if not feed:
-                prev, sbs_prev = states[:, i + T_in - 1], sbs_state
-            elif c == 0:
-                prev, sbs_prev = inputs[:, 0], sbs_input
-            elif k == 0:
-                prev, sbs_prev = states[:, i], sbs_state
-            else:
-                prev, sbs_prev = inter[(k - 1) % 2], N * F
-            if x_next is not None:
-                x = x_next
-            else:
-                x = torch.empty(B, H, W, cpad, dtype=adt, device=dev)
-                win, sbs_win = (prev, sbs_prev) if feed else (states[:, i], sbs_state)
-                L.call("p4c_build_x", L.ptr(win), sbs_win, N * F, L.ptr(st), sbs, L.ptr(forcing[:, i]), T * N * Ff,
-                       L.ptr(x), acode, cpad, B, T_in, N, F, Fs, Ff, mask_on_nan, 0, stream)
-            if saved is None or keep_saved:
-                saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-            L.call("p4c_halfunet_forward", ctypes.byref(desc_fwd), L.ptr(x), L.ptr(flat), L.ptr(model._running),
-                   None if fused_tail else L.ptr(y), L.ptr(saved), L.ptr(scratch), int(training), stream)
-            if k < K - 1:
-                x_next = torch.empty(B, H, W, cpad, dtype=adt, device=dev) if fuse_next else None
-                _free_step(model, desc_fwd, flat, saved, y, fused_tail, prev, sbs_prev, outputs[:, i] if force_border else None,
-                           T * N * F, std, mean, border_flat if force_border else None, interior_flat if force_border else None,
-                           inter[k % 2], N * F, mask_on_nan, B, N, F, x_next, cpad, st, sbs, Fs,
-                           forcing[:, i] if fuse_next else None, T * N * Ff, Ff, stream)
-                if keep_saved:
-                    xs.append(x)
-                    saveds.append(saved)
-                continue
-            if fused_tail:
-                last = i + 1 == T or not feed
-                x_next = None if last else torch.empty(B, H, W, cpad, dtype=adt, device=dev)
-                ta, tsc, tsh, tw = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-                L.call("p4c_halfunet_tail", ctypes.byref(desc_fwd), L.ptr(flat), L.ptr(saved), ctypes.byref(ta), ctypes.byref(tsc),
-                       ctypes.byref(tsh), ctypes.byref(tw))
-                L.call("p4c_out_conv_update_loss_fwd", ta, tsc, tsh, tw, model.out_channels,
-                       L.ptr(prev), sbs_prev, L.ptr(outputs[:, i]), T * N * F, L.ptr(std), L.ptr(mean),
-                       L.ptr(border_flat if force_border else None), L.ptr(interior_flat), L.ptr(states[:, i + T_in]), sbs_state,
-                       L.ptr(weights), num_interior, L.ptr(count), kind, L.ptr(loss[:, i]), T, L.ptr(ws), B, N, F, 1.0,
-                       L.ptr(x_next), cpad, L.ptr(st), sbs, Fs, L.ptr(None if last else forcing[:, i + 1]), T * N * Ff, Ff,
-                       L.ptr(lgrads[i]) if save_lg else None, N * F, stream)
-                if keep_saved:
-                    xs.append(x)
-                    saveds.append(saved)
-                continue
-            step_args = (L.ptr(prev), sbs_prev, L.ptr(y), acode, NF, L.ptr(outputs[:, i]),
-                         T * N * F, L.ptr(std), L.ptr(mean), L.ptr(border_flat if force_border else None), L.ptr(interior_flat),
-                         L.ptr(states[:, i + T_in]), sbs_state, L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode,
-                         L.ptr(loss[:, i]), T, L.ptr(ws), B, N, F, 1.0)
-            x_next = None
-            if save_lg:
-                last = i + 1 == T or not feed
-                x_next = None if last else torch.empty(B, H, W, cpad, dtype=adt, device=dev)
-                L.call("p4c_ar_update_loss_fwd_next_saved", *step_args, L.ptr(x_next), cpad, L.ptr(st), sbs, Fs,
-                       L.ptr(None if last else forcing[:, i + 1]), T * N * Ff, Ff, L.ptr(lgrads[i]), N * F, stream)
-            elif fuse_next and i + 1 < T:
-                x_next = torch.empty(B, H, W, cpad, dtype=adt, device=dev)
-                L.call("p4c_ar_update_loss_fwd_next", *step_args, L.ptr(x_next), cpad, L.ptr(st), sbs, Fs,
-                       L.ptr(forcing[:, i + 1]), T * N * Ff, Ff, stream)
-            else:
-                L.call("p4c_ar_update_loss_fwd", *step_args, stream)
-            if keep_saved:
-                xs.append(x)
-                saveds.append(saved)
-        ctx.model, ctx.desc, ctx.training = model, desc, training
-        ctx.meta = (B, T, H, W, F, force_border, num_interior, kind, mask_mode)
-        ctx.T_in, ctx.K = T_in, K
-        ctx.tensors = (states, outputs, std, interior_flat, weights, count, xs, saveds)
-        ctx.lgrads = lgrads
-        ctx.set_materialize_grads(False)
-        pred = states[:, T_in:]
-        return pred, loss
-
-    @staticmethod
-    def backward(ctx, g_pred, g_loss):
-        model, desc = ctx.model, ctx.desc
-        B, T, H, W, F, force_border, num_interior, kind, mask_mode = ctx.meta
-        states, outputs, std, interior_flat, weights, count, xs, saveds = ctx.tensors
-        dev = states.device
-        N = H * W
-        stream = L.stream(dev)
-        flat = model._flat_params()
-        _, scratch = model._workspaces(desc, dev)
-        target = model._flat_grad_target()
-        gflat = target if target is not None else torch.zeros_like(flat)
-        adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
-        dy = torch.empty(B, H, W, NF, dtype=adt, device=dev)
-        dx = torch.empty(B, H, W, NF, dtype=adt, device=dev) if ctx.T_in == 1 else None
-        dprev = torch.empty(B, H, W, F, dtype=torch.float32, device=dev)
-        gl = g_loss.contiguous().float() if g_loss is not None else None
-        # the scratch workspace may have served another call since forward: prepare again (one launch per sweep)
-        L.call("p4c_halfunet_prepare_weights", ctypes.byref(desc), L.ptr(flat), L.ptr(scratch), stream)
-        desc0 = HalfUNetDesc.from_buffer_copy(desc)
-        desc0.dx_channels = 0  # the input state of step 0 is data: no gradient needed, skip that conv
-        have_next = False
-        # Weight gradients run on the library's side stream.  Their join is deferred over the whole reverse sweep: the
-        # full-resolution ones left over at the end of AR step i's backward then run beside the HBM-bound head of step i-1's
-        # chain instead of alone (P4C_DEFER_JOIN=0: join after every step, the round-2 behaviour).  xs / saveds stay referenced
-        # until the join below -- the side stream reads them.
-        defer = T * ctx.K > 1 and L.diag_switch("P4C_DEFER_JOIN") != "0"
-        if defer:
-            L.call("p4c_side_stream_defer", 1)
-        ok = False
-        try:
-            if ctx.T_in > 1:
-                out = _NativeRolloutFn._sweep_window(ctx, g_pred, gl, dy, dprev, gflat, flat, scratch, desc, desc0, stream, target,
-                                                     defer)
-            else:
-                out = _NativeRolloutFn._sweep(ctx, g_pred, gl, dy, dx, dprev, gflat, flat, scratch, desc, desc0, stream, target,
-                                              defer)
-            ok = True
-            return out
-        finally:
-            if defer:
-                L.call("p4c_side_stream_defer", 0)
-                if not ok:
-                    # the sweep raised between two calls: weight gradients already on the side stream still read xs / saveds / dy,
-                    # which the unwinding is about to release to the allocator -- make the caller's stream (the one the allocator
-                    # orders re-use on) wait for them first.  (The join itself must not mask the original error.)
-                    try:
-                        L.call("p4c_side_stream_join", stream)
-                    except Exception:  # noqa: BLE001
-                        pass
-
-    @staticmethod
-    def _sweep(ctx, g_pred, gl, dy, dx, dprev, gflat, flat, scratch, desc, desc0, stream, target, defer):
-        model = ctx.model
-        B, T, H, W, F, force_border, num_interior, kind, mask_mode = ctx.meta
-        states, outputs, std, interior_flat, weights, count, xs, saveds = ctx.tensors
-        N = H * W
-        sbs_state = (T + 1) * N * F
-        adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
-        have_next = False
-        K = ctx.K
-        # all T * K model calls in reverse; call c = i * K + k is a free step for k < K - 1 (its adjoint reads nothing of the forward:
-        # p4c_ar_update_next_bwd; it has no loss gradient, no prediction slot and nothing saved)
-        for c in range(T * K - 1, -1, -1):
-            i, k = divmod(c, K)
-            g_next = dprev if have_next else None
-            if g_pred is not None and k == K - 1:  # somebody differentiates through the prediction itself: add its slice
-                if g_next is None:
-                    dprev.copy_(g_pred[:, i])
-                else:
-                    dprev.add_(g_pred[:, i])
-                g_next = dprev
-            if k < K - 1:
-                L.call("p4c_ar_update_next_bwd", L.ptr(g_next), N * F, L.ptr(dx if have_next else None), acode, NF, L.ptr(std),
-                       L.ptr(interior_flat if force_border else None), int(force_border), L.ptr(dy), acode, NF,
-                       L.ptr(dprev) if c > 0 else None, N * F, B, N, F, 1.0, stream)
-            elif ctx.lgrads is not None:
-                L.call("p4c_ar_update_loss_bwd_saved", L.ptr(g_next), N * F, L.ptr(dx if have_next else None), acode, NF,
-                       L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(ctx.lgrads[i]), N * F, L.ptr(std), L.ptr(interior_flat),
-                       int(force_border), L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF,
-                       L.ptr(dprev) if c > 0 else None, N * F, B, N, F, 1.0, stream)
-            else:
-                L.call("p4c_ar_update_loss_bwd", L.ptr(g_next), N * F, L.ptr(dx if have_next else None), acode, NF,
-                       L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(states[:, i + 1]), sbs_state, L.ptr(outputs[:, i]),
-                       T * N * F, L.ptr(std), L.ptr(interior_flat), int(force_border), L.ptr(weights), num_interior,
-                       L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF, L.ptr(dprev) if c > 0 else None, N * F, B, N, F,
-                       1.0, stream)
-            d = desc if c > 0 else desc0
-            L.call("p4c_halfunet_backward", ctypes.byref(d), L.ptr(xs[c]), L.ptr(flat), L.ptr(dy),
-                   L.ptr(dx) if c > 0 else None, L.ptr(gflat), L.ptr(saveds[c]), L.ptr(scratch), int(ctx.training), stream)
-            have_next = True
-            if not defer:
-                xs[c] = None
-                saveds[c] = None  # release the step's activations as soon as its backward is enqueued
-        if defer:
-            L.call("p4c_side_stream_join", stream)
-            for c in range(T * K):
-                xs[c] = None
-                saveds[c] = None
-        if target is not None:  # already accumulated into param.grad
-            return (None,) * (18 + len(model._param_slices))
-        grads = tuple(gflat[o : o + n].view(s) for (o, n, s) in model._param_slices)
-        return (None,) * 18 + grads
-
-    @staticmethod
-    def _sweep_window(ctx, g_pred, gl, dy, dprev, gflat, flat, scratch, desc, desc0, stream, target, defer):
-        """Reverse sweep of a rollout with T_in >= 2 input states.  State slot s = i + T_in (the new state of step i) collects, summed
-        in one launch (p4c_sum_state_grads) before step i's update backward: its prediction's gradient, the residual path of step i+1
-        (whose previous state it is: dprev), and block s - k of the input gradient dx_k of every step k in i+1 .. i+T_in whose window
-        holds it.  dx_k lives in a ring of T_in + 1 buffers (written at step k, last read at step k - T_in).  Step 0's window is all
-        input data: no data gradient there."""
-        model = ctx.model
-        B, T, H, W, F, force_border, num_interior, kind, mask_mode = ctx.meta
-        T_in = ctx.T_in
-        states, outputs, std, interior_flat, weights, count, xs, saveds = ctx.tensors
-        dev = states.device
-        N = H * W
-        sbs_state = (T_in + T) * N * F
-        adt, acode = model.act_dtype, L.dtype_code(model.act_dtype)
-        dxw = NF * ((desc.dx_channels + NF - 1) // NF)
-        nring = T_in + 1
-        dxs = [torch.empty(B, H, W, dxw, dtype=adt, device=dev) for _ in range(min(nring, T))]
-        gsum = torch.empty(B, H, W, F, dtype=torch.float32, device=dev)
-        gp = g_pred.float().contiguous() if g_pred is not None else None
-        srcs = (ctypes.c_void_p * 8)()
-        sbs, scs, soff, sdt = (ctypes.c_int64 * 8)(), (ctypes.c_int * 8)(), (ctypes.c_int * 8)(), (ctypes.c_int * 8)()
-        for i in range(T - 1, -1, -1):
-            n = 0
-            parts = []
-            if gp is not None:
-                parts.append((gp[:, i], gp.stride(0), F, 0, L.F32))
-            if i + 1 < T:
-                parts.append((dprev, N * F, F, 0, L.F32))
-            s = i + T_in
-            for k in range(i + 1, min(i + T_in, T - 1) + 1):
-                parts.append((dxs[k % nring], N * dxw, dxw, (s - k) * F, acode))
-            for (t, bs, cs, off, dt) in parts:
-                srcs[n], sbs[n], scs[n], soff[n], sdt[n] = t.data_ptr(), bs, cs, off, dt
-                n += 1
-            g_next = None
-            if n:
-                L.call("p4c_sum_state_grads", L.ptr(gsum), N * F, n, srcs, sbs, scs, soff, sdt, B, N, F, stream)
-                g_next = gsum
-            if ctx.lgrads is not None:
-                L.call("p4c_ar_update_loss_bwd_saved", L.ptr(g_next), N * F, None, acode, NF,
-                       L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(ctx.lgrads[i]), N * F, L.ptr(std), L.ptr(interior_flat),
-                       int(force_border), L.ptr(weights), num_interior, L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF,
-                       L.ptr(dprev) if i > 0 else None, N * F, B, N, F, 1.0, stream)
-            else:
-                L.call("p4c_ar_update_loss_bwd", L.ptr(g_next), N * F, None, acode, NF,
-                       L.ptr(gl[:, i]) if gl is not None else None, T, L.ptr(states[:, s]), sbs_state, L.ptr(outputs[:, i]),
-                       T * N * F, L.ptr(std), L.ptr(interior_flat), int(force_border), L.ptr(weights), num_interior,
-                       L.ptr(count), kind, mask_mode, L.ptr(dy), acode, NF, L.ptr(dprev) if i > 0 else None, N * F, B, N, F,
-                       1.0, stream)
-            d = desc if i > 0 else desc0
-            L.call("p4c_halfunet_backward", ctypes.byref(d), L.ptr(xs[i]), L.ptr(flat), L.ptr(dy),
-                   L.ptr(dxs[i % nring]) if i > 0 else None, L.ptr(gflat), L.ptr(saveds[i]), L.ptr(scratch), int(ctx.training), stream)
-            if not defer:
-                xs[i] = None
-                saveds[i] = None
-        if defer:
-            L.call("p4c_side_stream_join", stream)
-            for i in range(T):
-                xs[i] = None
-                saveds[i] = None
-        if target is not None:
-            return (None,) * (18 + len(model._param_slices))
-        grads = tuple(gflat[o : o + n].view(s) for (o, n, s) in model._param_slices)
-        return (None,) * 18 + grads
