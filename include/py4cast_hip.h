@@ -1100,6 +1100,25 @@ int p4c_deeplab_assemble_fwd(const void* a0, const void* a1, const void* a2, con
                              int D, p4c_stream_t stream);
 int p4c_deeplab_assemble_bwd(const void* dbuf, void* d0, void* d1, void* d2, void* d3, int B, int HW, int D, p4c_stream_t stream);
 
+/* CustomUNet (csrc/customunet.hip), features-last bf16 storage, fp32 arithmetic, fixed-order sums (no atomics).
+ * up2cat: x (B, h, w, Cx), skip (B, 2h, 2w, Cs) or NULL, out (B, 2h, 2w) rows of stride ld >= Cx + Cs; Cx, Cs, ld multiples of 8, every
+ * pointer 16-byte aligned.  Forward: out[b][2i+di][2j+dj][0:Cx] = x[b][i][j][:] (di, dj in {0, 1}), out[..][Cx:Cx+Cs] = skip[..][:];
+ * skip == NULL: channels >= Cx are not touched (their producer wrote them in place).  Backward, one pass over dout (rows of stride ld):
+ * dx[b][i][j][c] = bf16(((dout[2i][2j] + dout[2i][2j+1]) + dout[2i+1][2j]) + dout[2i+1][2j+1]) in fp32, dskip (B, 2h, 2w, Cs) = the
+ * slice dout[..][Cx:Cx+Cs] copied; dskip == NULL: not written (the producer reads its slice of dout in place).
+ * Stem tail with the skip: p4c_deeplab_stem_fwd with act = bf16(relu(y scale + shift)) (B, H, W, C) also written at `skip` (rows of
+ * stride ld >= C, a multiple of 4; 8-byte aligned), the pool and the routing bytes as there.  Backward: dz = relu'(act) (dskip + the dpool
+ * of the windows whose maximum is this pixel), dskip rows of stride ld; partial [p4c_customunet_stem_bwd_blocks][2][C] as
+ * p4c_deeplab_stem_bwd.  C a multiple of 4 up to 1024. */
+int p4c_up2_cat_fwd(const void* x, const void* skip, void* out, int64_t ld, int B, int h, int w, int Cx, int Cs, p4c_stream_t stream);
+int p4c_up2_cat_bwd(const void* dout, int64_t ld, void* dx, void* dskip, int B, int h, int w, int Cx, int Cs, p4c_stream_t stream);
+int p4c_customunet_stem_fwd(const void* y, const float* scale, const float* shift, void* skip, int64_t ld, void* pool, void* arg, int B, int H,
+                            int W, int C, p4c_stream_t stream);
+int p4c_customunet_stem_bwd_blocks(int B, int H, int W, int C);
+int p4c_customunet_stem_bwd(const void* y, const void* dskip, int64_t ld, const void* dpool, const void* arg, const float* scale,
+                            const float* shift, const float* mean, const float* rstd, void* dz, float* partial, int B, int H, int W, int C,
+                            p4c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,10 @@ SIGNATURES = {
     "p4c_deeplab_pool_broadcast": [P, P, I, I, I, P],
     "p4c_deeplab_assemble_fwd": [P, P, P, P, P, P, I, I, I, P],
     "p4c_deeplab_assemble_bwd": [P, P, P, P, P, I, I, I, P],
+    "p4c_up2_cat_fwd": [P, P, P, L, I, I, I, I, I, P],
+    "p4c_up2_cat_bwd": [P, L, P, P, I, I, I, I, I, P],
+    "p4c_customunet_stem_fwd": [P, P, P, P, L, P, P, I, I, I, I, P],
+    "p4c_customunet_stem_bwd": [P, P, L, P, P, P, P, P, P, P, P, I, I, I, I, P],
 }
 OTHER = {
     "p4c_conv_wgrad_workspace_bytes": ([I, I], c_size_t),
@@ -175,4 +179,5 @@ OTHER = {
     "p4c_seg_dw3x3_wgrad_rows": ([I, I, I], c_int),
     "p4c_seg_sra_bwd_workspace_bytes": ([I, I, I, I], c_size_t),
     "p4c_deeplab_stem_bwd_blocks": ([I, I, I, I], c_int),
+    "p4c_customunet_stem_bwd_blocks": ([I, I, I, I], c_int),
 }

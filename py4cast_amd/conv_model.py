@@ -1,4 +1,4 @@
-"""What the features-last convolutional models of the registry (UNet, Segformer, DeepLabV3) share on the host: the plugin attribute
+"""What the features-last convolutional models of the registry (UNet, Segformer, DeepLabV3, CustomUNet) share on the host: the plugin attribute
 contract, the ``compute_dtype`` / ``activation_dtype`` settings, the rollout's input format, bench.py's roofline hook and the padding
 steps that take channel counts to the 8-element granularity of the GEMM kernels (csrc/gemm.hip).  Each model keeps its module tree, its
 own settings checks, ``check_grid`` / ``padding_for``, ``timed_entry_points`` and its forward routes."""

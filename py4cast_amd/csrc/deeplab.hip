@@ -2,12 +2,8 @@
 // cover.  Features-last bf16 storage, fp32 arithmetic, every sum in a fixed order (no atomics): reruns and graph replays are
 // bit-identical.
 //
-//   stem tail : forward -- a = relu(y * scale + shift) of the stem convolution's raw output y (BatchNorm from the producer's statistics,
-//               p4c_bnorm_finalize), rounded to bf16, and the 3x3 / stride-2 / padding-1 max-pool of it (padding value -inf) in ONE
-//               pass: the pre-pool map is never written; the window's first maximum in row-major order (torch's choice) is kept as a
-//               byte per output element.  Backward -- one pass per input pixel: dA = sum over the (up to 4) windows that chose this
-//               pixel of dpool, in window order; dz = dA relu'(a); the batch-norm backward sums (sum dz, sum dz xhat) in the partial
-//               layout [blk][2][C] of p4c_inorm_reduce -> p4c_inorm_finalize_bwd, p4c_inorm_apply.
+//   stem tail : BatchNorm + ReLU + the 3x3 / stride-2 / padding-1 max-pool in one pass each way, the pre-pool map never written: the
+//               kernels of csrc/stem_tail.hpp without their skip output.
 //   col sums  : partial[b][s][c] = sum over rows s R .. s R + R - 1 of sample b of x[b][row][c] (x bf16 rows of stride ld), rows in
 //               order: the ASPP pooling branch's spatial mean (forward) and the pooled column's gradient (backward).
 //   pool head : the pooling branch after the mean -- z = W mean (1x1 conv, no bias, fp32), BatchNorm over the B samples (fp32: the
@@ -16,108 +12,12 @@
 //   assemble  : the projection's input (M, 5 dc) = [a0 | a1 | a2 | a3 | broadcast pooled] -- the four spatial branches and the pooled
 //               row of the pixel's sample; backward: the four column slices out into their own (M, dc) gradients.
 #include "common.hpp"
+#include "stem_tail.hpp"
 
 namespace p4c {
 namespace deeplab {
 
-__device__ __forceinline__ float rbf(float v) { return __bfloat162float(__float2bfloat16(v)); }
-
 inline int grid_for(int64_t n) { return (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536); }
-
-// ---------------------------------------------------------------- stem tail
-// thread = 4 channels of one pooled output
-__global__ void __launch_bounds__(256) stem_fwd_kernel(const bf16* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                       bf16* __restrict__ pool, unsigned char* __restrict__ arg, int B, int H, int W, int C, int Ho,
-                                                       int Wo) {
-    const int cq = C >> 2;
-    const int64_t n = (int64_t)B * Ho * Wo * cq;
-    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
-        const int c = (int)(g % cq) * 4;
-        const int64_t win = g / cq;
-        const int ox = (int)(win % Wo);
-        const int64_t t = win / Wo;
-        const int oy = (int)(t % Ho);
-        const int64_t b = t / Ho;
-        const p4c_f32x4 sc = load4f(scale + c), sh = load4f(shift + c);
-        float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        int am[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int iy = 2 * oy - 1 + k / 3, ix = 2 * ox - 1 + k % 3;
-            if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-            const p4c_f32x4 v = load4f(y + ((b * H + iy) * W + ix) * C + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a = rbf(fmaxf(__builtin_fmaf(v[j], sc[j], sh[j]), 0.f));     // the stored value the library route would pool
-                if (a > mx[j]) { mx[j] = a; am[j] = k; }
-            }
-        }
-        store4f(pool + win * C + c, p4c_f32x4{mx[0], mx[1], mx[2], mx[3]});
-        const unsigned int packed = (unsigned)am[0] | ((unsigned)am[1] << 8) | ((unsigned)am[2] << 16) | ((unsigned)am[3] << 24);
-        *reinterpret_cast<unsigned int*>(arg + win * C + c) = packed;
-    }
-}
-
-constexpr int BWD_BLOCKS_MAX = 1024;
-__host__ __device__ inline int bwd_pixels_per_block(int C) { return 256 / (C >> 2) > 0 ? 256 / (C >> 2) : 1; }
-
-__global__ void __launch_bounds__(256) stem_bwd_kernel(const bf16* __restrict__ y, const bf16* __restrict__ dpool, const unsigned char* __restrict__ arg,
-                                                       const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-                                                       const float* __restrict__ rstd, bf16* __restrict__ dz, float* __restrict__ partial, int B, int H,
-                                                       int W, int C, int Ho, int Wo) {
-    extern __shared__ float red[];       // [ppb][2][C]
-    const int cq = C >> 2, ppb = bwd_pixels_per_block(C);
-    const int lc = threadIdx.x % cq, lp = threadIdx.x / cq;
-    const bool active = lp < ppb;
-    const int c = lc * 4;
-    const int64_t npix = (int64_t)B * H * W;
-    float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
-    if (active) {
-        const p4c_f32x4 sc = load4f(scale + c), sh = load4f(shift + c), mu = load4f(mean + c), rs = load4f(rstd + c);
-        for (int64_t p = (int64_t)blockIdx.x * ppb + lp; p < npix; p += (int64_t)gridDim.x * ppb) {
-            const int ix = (int)(p % W);
-            const int64_t t = p / W;
-            const int iy = (int)(t % H);
-            const int64_t b = t / H;
-            // windows oy with 2 oy - 1 <= iy <= 2 oy + 1, in (oy, ox) order
-            const int oy0 = iy / 2, oy1 = min((iy + 1) / 2, Ho - 1);
-            const int ox0 = ix / 2, ox1 = min((ix + 1) / 2, Wo - 1);
-            float da[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int oy = oy0; oy <= oy1; ++oy)
-                for (int ox = ox0; ox <= ox1; ++ox) {
-                    const int k = (iy - (2 * oy - 1)) * 3 + (ix - (2 * ox - 1));
-                    const int64_t o = ((b * Ho + oy) * Wo + ox) * C + c;
-                    const unsigned int packed = *reinterpret_cast<const unsigned int*>(arg + o);
-                    const p4c_f32x4 gp = load4f(dpool + o);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if ((int)((packed >> (8 * j)) & 0xffu) == k) da[j] += gp[j];
-                }
-            const p4c_f32x4 v = load4f(y + p * C + c);
-            p4c_f32x4 d;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a = fmaxf(__builtin_fmaf(v[j], sc[j], sh[j]), 0.f);
-                d[j] = rbf(a) > 0.f ? da[j] : 0.f;
-                s0[j] += d[j];
-                s1[j] = __builtin_fmaf(d[j], (v[j] - mu[j]) * rs[j], s1[j]);
-            }
-            store4f(dz + p * C + c, d);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            red[(lp * 2 + 0) * C + c + j] = s0[j];
-            red[(lp * 2 + 1) * C + c + j] = s1[j];
-        }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 2 * C; e += 256) {
-        const int which = e / C, cc = e - which * C;
-        float tsum = 0.f;
-        for (int r = 0; r < ppb; ++r) tsum += red[(r * 2 + which) * C + cc];
-        partial[((int64_t)blockIdx.x * 2 + which) * C + cc] = tsum;
-    }
-}
 
 // ---------------------------------------------------------------- column sums per sample
 // block = 64 columns x 4 row lanes; grid (ceil(C / 64), S, B)
@@ -294,29 +194,23 @@ extern "C" int p4c_deeplab_stem_fwd(const void* y, const float* scale, const flo
                   "up to 1024)", B, H, W, C);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const int64_t n = (int64_t)B * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(deeplab::stem_fwd_kernel, dim3(deeplab::grid_for(n)), dim3(256), 0, as_stream(stream), (const bf16*)y, scale, shift,
-                       (bf16*)pool, (unsigned char*)arg, B, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(stem::tail_fwd_kernel<false>, dim3(deeplab::grid_for(n)), dim3(256), 0, as_stream(stream), (const bf16*)y, scale, shift,
+                       (bf16*)nullptr, (int64_t)0, (bf16*)pool, (unsigned char*)arg, B, H, W, C, Ho, Wo);
     P4C_CHECK_LAUNCH("p4c_deeplab_stem_fwd");
     return P4C_OK;
 }
 
-extern "C" int p4c_deeplab_stem_bwd_blocks(int B, int H, int W, int C) {
-    if (B <= 0 || H <= 0 || W <= 0 || C < 4) return 0;
-    const int64_t npix = (int64_t)B * H * W;
-    const int ppb = deeplab::bwd_pixels_per_block(C);
-    const int64_t need = (npix + ppb - 1) / ppb;
-    return (int)(need < deeplab::BWD_BLOCKS_MAX ? need : deeplab::BWD_BLOCKS_MAX);
-}
+extern "C" int p4c_deeplab_stem_bwd_blocks(int B, int H, int W, int C) { return stem::bwd_blocks(B, H, W, C); }
 
 extern "C" int p4c_deeplab_stem_bwd(const void* y, const void* dpool, const void* arg, const float* scale, const float* shift, const float* mean,
                                     const float* rstd, void* dz, float* partial, int B, int H, int W, int C, p4c_stream_t stream) {
     P4C_CHECK_ARG(y && dpool && arg && scale && shift && mean && rstd && dz && partial, "p4c_deeplab_stem_bwd: NULL pointer");
     P4C_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && C <= 1024, "p4c_deeplab_stem_bwd: B=%d H=%d W=%d C=%d", B, H, W, C);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int nb = p4c_deeplab_stem_bwd_blocks(B, H, W, C);
-    const size_t smem = (size_t)deeplab::bwd_pixels_per_block(C) * 2 * C * sizeof(float);
-    hipLaunchKernelGGL(deeplab::stem_bwd_kernel, dim3(nb), dim3(256), smem, as_stream(stream), (const bf16*)y, (const bf16*)dpool,
-                       (const unsigned char*)arg, scale, shift, mean, rstd, (bf16*)dz, partial, B, H, W, C, Ho, Wo);
+    const int nb = stem::bwd_blocks(B, H, W, C);
+    const size_t smem = (size_t)stem::bwd_pixels_per_block(C) * 2 * C * sizeof(float);
+    hipLaunchKernelGGL(stem::tail_bwd_kernel<false>, dim3(nb), dim3(256), smem, as_stream(stream), (const bf16*)y, (const bf16*)nullptr, (int64_t)0,
+                       (const bf16*)dpool, (const unsigned char*)arg, scale, shift, mean, rstd, (bf16*)dz, partial, B, H, W, C, Ho, Wo);
     P4C_CHECK_LAUNCH("p4c_deeplab_stem_bwd");
     return P4C_OK;
 }

@@ -96,16 +96,17 @@ class BasicBlock(nn.Module):
 
 
 class ResNetEncoder(nn.Module):
-    """torchvision's ResNet (BasicBlock) without avgpool / fc, output stride 8 (layer3 dilation 2, layer4 dilation 4)"""
+    """torchvision's ResNet (BasicBlock) without avgpool / fc; per-layer ``strides`` / ``dilations``: the defaults are output stride 8
+    (layer3 dilation 2, layer4 dilation 4: DeepLabV3), (1, 2, 2, 2) / (1, 1, 1, 1) the undilated ResNet (customunet.py)"""
 
-    def __init__(self, in_channels: int, blocks):
+    def __init__(self, in_channels: int, blocks, strides=(1, 2, 1, 1), dilations=(1, 1, 2, 4)):
         super().__init__()
         self.conv1 = nn.Conv2d(in_channels, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
         cin = 64
-        for i, (n, width, stride, dil) in enumerate(zip(blocks, (64, 128, 256, 512), (1, 2, 1, 1), (1, 1, 2, 4))):
+        for i, (n, width, stride, dil) in enumerate(zip(blocks, (64, 128, 256, 512), strides, dilations)):
             layer = []
             for j in range(n):
                 layer.append(BasicBlock(cin, width, stride if j == 0 else 1, dil))
@@ -308,17 +309,18 @@ def _find_checkpoint(name: str, path: Optional[str]) -> Optional[str]:
     return found[0] if found else None
 
 
-def load_encoder_weights(encoder: ResNetEncoder, name: str, in_channels: int, path: Optional[str] = None) -> bool:
+def load_encoder_weights(encoder: ResNetEncoder, name: str, in_channels: int, path: Optional[str] = None,
+                         owner: str = "DeepLabV3MI355X") -> bool:
     """torchvision ``name`` weights into ``encoder`` from ``path`` or the first ``<name>-*.pth`` of torch.hub's checkpoint cache, without
     any download; ``fc.*`` ignored; conv1 patched for in_channels != 3 as smp does (1 channel: the sum over the RGB kernels; otherwise
-    kernel i = RGB kernel i % 3, all scaled by 3 / in_channels).  No file: a warning (once per name) and False."""
+    kernel i = RGB kernel i % 3, all scaled by 3 / in_channels).  No file: a warning in ``owner``'s name (once per name) and False."""
     ck = _find_checkpoint(name, path)
     if ck is None or not os.path.isfile(ck):
         key = (name, path)
         if key not in _WARNED:
             _WARNED.add(key)
             where = path if path else os.path.join(torch.hub.get_dir(), "checkpoints")
-            warnings.warn(f"DeepLabV3MI355X: no {name} checkpoint found ({where}); the encoder keeps its random initialisation "
+            warnings.warn(f"{owner}: no {name} checkpoint found ({where}); the encoder keeps its random initialisation "
                           "(nothing is downloaded)")
         return False
     sd = torch.load(ck, map_location="cpu", weights_only=True)
