@@ -1119,6 +1119,30 @@ int p4c_customunet_stem_bwd(const void* y, const void* dskip, int64_t ld, const 
                             const float* shift, const float* mean, const float* rstd, void* dz, float* partial, int B, int H, int W, int C,
                             p4c_stream_t stream);
 
+/* DeepLabV3+ (csrc/deeplabplus.hip), features-last bf16 storage, fp32 arithmetic, fixed-order sums (no atomics); every map 16-byte
+ * aligned, C a multiple of 8.
+ * Depthwise 3x3 at R = 1 .. 3 rates in one launch: x (B, H, W, C), w (R, 9, C) fp32 (the R (C, 1, 3, 3) parameters tap-major: a tap's
+ * weights of a channel octet are one 32-byte load), rates d_r = 1 .. 4095 (only the first R of y0 .. y2 / dy0 .. dy2 / d0 .. d2 are read).  Forward: y_r (B, H, W, C) = depthwise3x3(x; w_r, padding =
+ * dilation = d_r), no bias; a tap outside the map is skipped (d >= H or d >= W included).  Data gradient: dx[p] = bf16(sum_r sum_t
+ * w_r[t] dy_r[p - off_t]), r outermost, taps in row-major order.  Weight gradient: partial [p4c_dlp_dw3x3_wgrad_rows(B, H, W)][R][9][C]
+ * fp32 (16-byte aligned), one row per chunk of 64 pixels (maps below 16384 pixels) or 128; their sum over the rows
+ * (p4c_seg_reduce_partials) is dw (R, 9, C).
+ * up_cat: a (B, h, w, Ca), skip (B, s h, s w, Cs), out (B, s h, s w) rows of stride ld >= Ca + Cs; Ca, Cs, ld positive multiples of 8,
+ * s = scale 1 .. 8.  Forward: out[..][0:Ca] = the align_corners = True bilinear up-sampling of a (the arithmetic of
+ * p4c_upsample_bilinear_ac_fwd, bit for bit), out[..][Ca:Ca+Cs] = skip, out[..][Ca+Cs:ld] = 0.  Backward, one pass over dout (rows of
+ * stride ld): da (B, h, w, Ca) in gather form (as p4c_upsample_bilinear_ac_bwd), dskip (B, s h, s w, Cs) = dout[..][Ca:Ca+Cs] copied. */
+int p4c_dlp_dw3x3_fwd(const void* x, const float* w, void* y0, void* y1, void* y2, int R, int d0, int d1, int d2, int B, int H, int W, int C,
+                      p4c_stream_t stream);
+int p4c_dlp_dw3x3_dgrad(const void* dy0, const void* dy1, const void* dy2, const float* w, void* dx, int R, int d0, int d1, int d2, int B, int H,
+                        int W, int C, p4c_stream_t stream);
+int p4c_dlp_dw3x3_wgrad_rows(int B, int H, int W);
+int p4c_dlp_dw3x3_wgrad(const void* x, const void* dy0, const void* dy1, const void* dy2, float* partial, int R, int d0, int d1, int d2, int B,
+                        int H, int W, int C, p4c_stream_t stream);
+int p4c_dlp_up_cat_fwd(const void* a, const void* skip, void* out, int64_t ld, int B, int h, int w, int Ca, int Cs, int scale,
+                       p4c_stream_t stream);
+int p4c_dlp_up_cat_bwd(const void* dout, int64_t ld, void* da, void* dskip, int B, int h, int w, int Ca, int Cs, int scale,
+                       p4c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

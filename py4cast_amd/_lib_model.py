@@ -146,6 +146,11 @@ SIGNATURES = {
     "p4c_up2_cat_bwd": [P, L, P, P, I, I, I, I, I, P],
     "p4c_customunet_stem_fwd": [P, P, P, P, L, P, P, I, I, I, I, P],
     "p4c_customunet_stem_bwd": [P, P, L, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    "p4c_dlp_dw3x3_fwd": [P, P, P, P, P, I, I, I, I, I, I, I, I, P],
+    "p4c_dlp_dw3x3_dgrad": [P, P, P, P, P, I, I, I, I, I, I, I, I, P],
+    "p4c_dlp_dw3x3_wgrad": [P, P, P, P, P, I, I, I, I, I, I, I, I, P],
+    "p4c_dlp_up_cat_fwd": [P, P, P, L, I, I, I, I, I, I, P],
+    "p4c_dlp_up_cat_bwd": [P, L, P, P, I, I, I, I, I, I, P],
 }
 OTHER = {
     "p4c_conv_wgrad_workspace_bytes": ([I, I], c_size_t),
@@ -180,4 +185,5 @@ OTHER = {
     "p4c_seg_sra_bwd_workspace_bytes": ([I, I, I, I], c_size_t),
     "p4c_deeplab_stem_bwd_blocks": ([I, I, I, I], c_int),
     "p4c_customunet_stem_bwd_blocks": ([I, I, I, I], c_int),
+    "p4c_dlp_dw3x3_wgrad_rows": ([I, I, I], c_int),
 }

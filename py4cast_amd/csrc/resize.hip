@@ -6,30 +6,13 @@
 //   backward: GATHER form -- dx[b, iy, ix, :] = sum over the <= (3 s)^2 output pixels that read input pixel (iy, ix) of weight * dout,
 //             in a fixed order (bit-identical reruns, no atomics); the skip's gradient is dout itself.
 #include "common.hpp"
+#include "resize_ac.hpp"
 
 namespace p4c {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void unpack8(u32x4 w, float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[2 * j] = __builtin_bit_cast(float, w[j] << 16);
-        v[2 * j + 1] = __builtin_bit_cast(float, w[j] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    u32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 p = {v[2 * j], v[2 * j + 1]};
-        o[j] = __builtin_bit_cast(unsigned int, __builtin_convertvector(p, bf16x2));
-    }
-    return o;
-}
+// (the octet packing and the align_corners = True element arithmetic live in resize_ac.hpp, shared with csrc/deeplabplus.hip)
+using namespace resize_ac;
 
 // source coordinate of output index o: i0, i1 and the weight of i1 (torch's area_pixel_compute_source_index, align_corners = False)
 __device__ __forceinline__ void src_index(int o, float inv_scale, int in_size, int& i0, int& i1, float& lam) {
@@ -117,15 +100,6 @@ __global__ void __launch_bounds__(256) upsample_bwd_kernel(const bf16* __restric
 
 // align_corners = True (smp's segmentation head, nn.UpsamplingBilinear2d): source coordinate o (in - 1) / (out - 1), as torch's
 // area_pixel_compute_scale / _source_index compute it in fp32
-__device__ __forceinline__ void src_index_ac(int o, float sc, int in_size, int& i0, int& i1, float& lam) {
-    const float s = sc * (float)o;
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    lam = s - (float)i0;
-}
-__host__ __device__ inline float ac_scale(int in_size, int out_size) { return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f; }
-
 __global__ void __launch_bounds__(256) upsample_ac_fwd_kernel(const bf16* __restrict__ x, bf16* __restrict__ out, int B, int H, int W, int C, int scale) {
     const int OH = H * scale, OW = W * scale, cq = C >> 3;
     const float sy = ac_scale(H, OH), sx = ac_scale(W, OW);
@@ -141,23 +115,10 @@ __global__ void __launch_bounds__(256) upsample_ac_fwd_kernel(const bf16* __rest
         src_index_ac(oy, sy, H, y0, y1, ly);
         src_index_ac(ox, sx, W, x0, x1, lx);
         const bf16* xb = x + (int64_t)b * H * W * C + 8 * q;
-        float a[8], bq[8], c[8], d[8], o[8];
-        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y0 * W + x0) * C), a);
-        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y0 * W + x1) * C), bq);
-        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y1 * W + x0) * C), c);
-        unpack8(*reinterpret_cast<const u32x4*>(xb + ((int64_t)y1 * W + x1) * C), d);
-        const float hy0 = 1.f - ly, wx0 = 1.f - lx;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = hy0 * (wx0 * a[j] + lx * bq[j]) + ly * (wx0 * c[j] + lx * d[j]);
+        float o[8];
+        blend8(xb, W, C, y0, y1, x0, x1, ly, lx, o);
         *reinterpret_cast<u32x4*>(out + (((int64_t)b * OH + oy) * OW + ox) * C + 8 * q) = pack8(o);
     }
-}
-
-// output rows that may read input row i: s o in [i - 1, i + 1] (a conservative range; the loop checks each one exactly)
-__device__ __forceinline__ void ac_range(int i, float sc, int out_size, int& lo, int& hi) {
-    if (sc <= 0.f) { lo = 0; hi = out_size - 1; return; }
-    lo = max(0, (int)floorf((float)(i - 1) / sc) - 1);
-    hi = min(out_size - 1, (int)ceilf((float)(i + 1) / sc) + 1);
 }
 
 __global__ void __launch_bounds__(256) upsample_ac_bwd_kernel(const bf16* __restrict__ dout, bf16* __restrict__ dx, int B, int H, int W, int C,
@@ -172,30 +133,7 @@ __global__ void __launch_bounds__(256) upsample_ac_bwd_kernel(const bf16* __rest
         p /= W;
         const int iy = (int)(p % H), b = (int)(p / H);
         float acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-        int oy_lo, oy_hi, ox_lo, ox_hi;
-        ac_range(iy, sy, OH, oy_lo, oy_hi);
-        ac_range(ix, sx, OW, ox_lo, ox_hi);
-        const bf16* db = dout + (int64_t)b * OH * OW * C + 8 * q;
-        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            int y0, y1;
-            float ly;
-            src_index_ac(oy, sy, H, y0, y1, ly);
-            const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
-            if (wy == 0.f) continue;
-            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                int x0, x1;
-                float lx;
-                src_index_ac(ox, sx, W, x0, x1, lx);
-                const float w = wy * ((x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f));
-                if (w == 0.f) continue;
-                float g[8];
-                unpack8(*reinterpret_cast<const u32x4*>(db + ((int64_t)oy * OW + ox) * C), g);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(w, g[j], acc[j]);
-            }
-        }
+        gather8(dout + (int64_t)b * OH * OW * C + 8 * q, C, iy, ix, H, W, OH, OW, sy, sx, acc);
         *reinterpret_cast<u32x4*>(dx + (((int64_t)b * H + iy) * W + ix) * C + 8 * q) = pack8(acc);
     }
 }

@@ -5,7 +5,8 @@ MI355X-native models.  Put the repository root on PYTHONPATH and ``model_name: H
 ``HalfUNetMI355X`` next to a real mfai install, which already owns the name ``HalfUNet``)
 selects the HIP implementation; likewise ``GraphLam`` / ``GraphLamMI355X`` (mesh GNN on the edge kernels) and
 ``SwinUNetR`` / ``SwinUNetRMI355X`` (fused window attention), ``UNet`` / ``UNetMI355X``, ``Segformer`` / ``SegformerMI355X``,
-``DeepLabV3`` / ``DeepLabV3MI355X``, ``CustomUNet`` / ``CustomUNetMI355X`` (smp's Unet on a ResNet encoder).
+``DeepLabV3`` / ``DeepLabV3MI355X``, ``CustomUNet`` / ``CustomUNetMI355X`` (smp's Unet on a ResNet encoder), ``DeepLabV3Plus`` /
+``DeepLabV3PlusMI355X`` (smp's DeepLabV3Plus: separable ASPP, stride-4 decoder) -- every key of the reference's registry.
 """
 
 from dataclasses import dataclass
@@ -27,6 +28,7 @@ from py4cast_amd.unet import UNetMI355X, UNetSettings  # noqa: F401,E402
 from py4cast_amd.segformer import SegformerMI355X, SegformerSettings  # noqa: F401,E402
 from py4cast_amd.deeplabv3 import DeepLabV3MI355X, DeepLabV3Settings  # noqa: F401,E402
 from py4cast_amd.customunet import CustomUNetMI355X, CustomUNetSettings  # noqa: F401,E402
+from py4cast_amd.deeplabv3plus import DeepLabV3PlusMI355X, DeepLabV3PlusSettings  # noqa: F401,E402
 
 if not HAVE_MFAI:
     # stand-alone: take the upstream names so that config/CLI/model/halfunet.yaml / graphlam.yaml work unchanged
@@ -61,6 +63,9 @@ if not HAVE_MFAI:
         register = True
 
     class CustomUNet(CustomUNetMI355X):  # config/CLI/model/customunet.yaml (mfai's CustomUnet, smp's Unet on a ResNet)
+        register = True
+
+    class DeepLabV3Plus(DeepLabV3PlusMI355X):  # config/CLI/model/deeplabv3plus.yaml (mfai's DeepLabV3Plus, smp's network)
         register = True
 
 
