@@ -275,6 +275,54 @@ int p4c_build_forcing(const float* raw, int64_t plane_stride, const float* mean,
                       const float* cos_lat, const float* lon_hours, const float* time_table, float* out, int B, int T,
                       int64_t HW, int Fe, p4c_stream_t stream);
 
+/* Native-grid planes -> the standardised features-last batch on the training sub-domain, in one pass (Titan's fit_to_grid,
+ * datasets/titan/__init__.py:184-208, + the latitude flip of load_data_for_date + the sub-domain of titan_cli.py:36 +
+ * p4c_pack_standardize).  The definition is the scipy.ndimage form of skimage.transform.resize:
+ * an optional separable Gaussian with mirror edges (p4c_regrid_blur), then an order-1 zoom with grid_mode and mirror edges
+ * (p4c_regrid_pack).  All coordinates come in host tables built from exact integer arithmetic (py4cast_amd/regrid.py).
+ *
+ * p4c_regrid_pack: out (B,T,H_sub,W_sub,F) features-last, row r = ((b*T + t)*H_sub + y)*W_sub + x:
+ *   out[r*F + channel] = (blend - mean) / std   (the two rounded steps of p4c_pack_standardize), with
+ *   blend = lerp(lerp(s[i0][j0], s[i0][j1], fx), lerp(s[i1][j0], s[i1][j1], fx), fy),  lerp(a, b, f) = fma(f, b - a, a),
+ *   s[i][j] = src[b*b_stride + t*t_stride + (row0 + i)*pitch + col0 + j],
+ *   (i0, i1, fy) = taps[table*(H_sub + W_sub) + y] and (j0, j1, fx) = taps[table*(H_sub + W_sub) + H_sub + x].
+ *   Plain IEEE arithmetic on all four taps: a NaN source pixel makes the outputs NaN that touch it with either weight.
+ *   An identity table (i1 == i0 or f == 0 on both axes, mean 0, std 1) copies finite values bit for bit, except that
+ *   -0 comes out as +0 (0 * 0 + -0).
+ * feats: F descriptors in DEVICE memory; their channels are a permutation of 0 .. F-1.  taps: device memory, (tables,
+ *   H_sub + W_sub) entries: H_sub row entries (the flip and the sub-domain origin folded in), then W_sub column entries.
+ *   The caller guarantees that every tap index lies inside the feature's window and the window inside its plane.
+ * Limits: F <= 144 (the LDS tile of p4c_pack_standardize), B*T*H_sub*W_sub < 2^31, refused before any launch. */
+typedef struct p4c_regrid_tap {
+    int32_t i0, i1; /* source indices relative to the window origin, i1 = min(i0 + 1, n - 1) */
+    float f;        /* weight of i1 */
+    int32_t pad;
+} p4c_regrid_tap;
+
+typedef struct p4c_regrid_feature {
+    const float* src;          /* the plane of (b, t) = (0, 0), device memory */
+    int64_t b_stride, t_stride; /* in floats */
+    int32_t pitch;             /* floats between two source rows */
+    int32_t row0, col0;        /* window origin inside the plane */
+    int32_t table;             /* which tap table */
+    float mean, std;
+    int32_t channel;           /* output column */
+    int32_t pad;
+} p4c_regrid_feature;
+
+int p4c_regrid_pack(const p4c_regrid_feature* feats, const p4c_regrid_tap* taps, float* out, int B, int T, int H_sub, int W_sub,
+                    int F, p4c_stream_t stream);
+
+/* The Gaussian of resize(anti_aliasing=True) over `planes` windowed planes: dst (planes, n, m) dense =
+ * gaussian_filter(window, sigma, mode="mirror"), axis 0 then axis 1, window = src[p*plane_stride + (row0 + i)*pitch + col0 + j].
+ * row_index: (n + 2*ry) ints, the mirrored source row (period 2(n-1)) of positions -ry .. n-1+ry; col_index: (m + 2*rx)
+ * likewise.  row_w: (2*ry + 1) weights exp(-k^2 / 2 sigma^2) normalised to sum 1 in float64 and rounded once; col_w likewise.
+ * A radius of 0 with the weight 1 leaves that axis untouched.  Sums run in tap order: a rerun is bit-identical.
+ * Limits: ry, rx <= 64; n, m >= 2; planes <= 65535; refused before any launch. */
+int p4c_regrid_blur(const float* src, int64_t plane_stride, int pitch, int row0, int col0, float* dst, int planes, int n, int m,
+                    const int* row_index, const int* col_index, const float* row_w, int ry, const float* col_w, int rx,
+                    p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

@@ -52,6 +52,10 @@ SIGNATURES = {
     "p4c_nan_moments": [P, P, L, P, P, I, L, I, P],
     "p4c_pack_standardize": [P, L, P, P, P, L, I, P],
     "p4c_build_forcing": [P, L, P, P, P, P, P, P, P, I, I, L, I, P],
+    # feats, taps, out, B, T, H_sub, W_sub, F, stream
+    "p4c_regrid_pack": [P, P, P, I, I, I, I, I, P],
+    # src, plane_stride, pitch, row0, col0, dst, planes, n, m, row_index, col_index, row_w, ry, col_w, rx, stream
+    "p4c_regrid_blur": [P, L, I, I, I, P, I, I, I, P, P, P, I, P, I, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],

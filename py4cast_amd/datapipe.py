@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import forcings, ops
+from . import forcings, ops, regrid
 from .base import ItemBatch
 from .namedtensor import NamedTensor
 
@@ -37,6 +37,66 @@ def load_batch(raw_io: torch.Tensor, io_names: List[str], forcing: NamedTensor, 
     t = full.tensor
     inputs = NamedTensor(t[:, :num_input_steps], DIMS.copy(), list(io_names))
     outputs = NamedTensor(t[:, num_input_steps:], DIMS.copy(), list(io_names))
+    return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
+
+
+def load_native_batch(groups, io_names: List[str], forcing: NamedTensor, stats, num_input_steps: int,
+                      standardize: bool = True) -> ItemBatch:
+    """``load_batch`` for planes still on their NATIVE grids: the reference's ``fit_to_grid`` (datasets/titan/__init__.py:184-208),
+    the latitude flip of ``load_data_for_date`` and the sub-domain of titan_cli.py:36, standardised and packed by ONE
+    ``p4c_regrid_pack`` launch for the whole batch (after one ``p4c_regrid_blur`` launch per group whose plan has a Gaussian);
+    no full-grid plane exists.  ``py4cast_amd/regrid.py`` has the definition.
+
+    groups: a list of (raw (Fg, B, T, Hs, Ws) device tensor, its Fg names, RegridPlan), all plans on one sub-domain of one
+    full grid; io_names: the output feature order, every name from exactly one group.  -> the ItemBatch of ``load_batch``."""
+    io_names = list(io_names)
+    if not groups:
+        raise ValueError("load_native_batch: no groups")
+    if not 1 <= len(io_names) <= ops.REGRID_MAX_FEATURES:
+        raise ValueError(f"load_native_batch: {len(io_names)} features: 1 .. at most {ops.REGRID_MAX_FEATURES} per call (LDS tile)")
+    first = groups[0][2]
+    where = {}
+    for gi, (raw, names, plan) in enumerate(groups):
+        names = list(names)
+        if raw.dim() != 5 or raw.shape[0] != len(names) or tuple(raw.shape[3:]) != plan.src_shape:
+            raise ValueError(f"load_native_batch: group {gi}: raw {tuple(raw.shape)} is not (Fg, B, T, Hs, Ws) with Fg = {len(names)} "
+                             f"names and (Hs, Ws) = {plan.src_shape}")
+        if tuple(raw.shape[1:3]) != tuple(groups[0][0].shape[1:3]):
+            raise ValueError(f"load_native_batch: group {gi} has batch x steps {tuple(raw.shape[1:3])}, group 0 {tuple(groups[0][0].shape[1:3])}")
+        if (plan.full_size, plan.subdomain) != (first.full_size, first.subdomain):
+            raise ValueError(f"load_native_batch: group {gi} is on sub-domain {plan.subdomain} of {plan.full_size}, group 0 on "
+                             f"{first.subdomain} of {first.full_size}: one launch writes one sub-domain")
+        for k, name in enumerate(names):
+            if name in where:
+                raise ValueError(f"load_native_batch: feature {name!r} is in groups {where[name][0]} and {gi}")
+            where[name] = (gi, k)
+    if sorted(where) != sorted(io_names):
+        raise ValueError(f"load_native_batch: io_names and the groups' names differ: {sorted(set(where) ^ set(io_names))}")
+    ops.L.require_cuda(*(g[0] for g in groups))
+    dev = groups[0][0].device
+    B, T = groups[0][0].shape[1:3]
+    if standardize:
+        mean, std = stats.to_list("mean", io_names).tolist(), stats.to_list("std", io_names).tolist()
+    else:
+        mean, std = [0.0] * len(io_names), [1.0] * len(io_names)
+    keys, plans, sources, windows, src_bytes = {}, [], [], [], 0
+    for raw, names, plan in groups:
+        if plan.key not in keys:
+            keys[plan.key] = len(plans)
+            plans.append(plan)
+        src, window = regrid.blurred(raw.contiguous().float(), plan)
+        sources.append(src)
+        windows.append(window)
+        src_bytes += regrid.source_bytes(plan, len(names) * B * T)
+    feats = []
+    for channel, name in enumerate(io_names):
+        gi, k = where[name]
+        feats.append((gi, k, windows[gi][0], windows[gi][2], keys[groups[gi][2].key], mean[channel], std[channel], channel))
+    feats.sort(key=lambda f: (f[4], f[0], f[1]))      # features of one tap table side by side: their table reads hit
+    full = ops.regrid_pack(sources, feats, regrid.device_taps(plans, dev), [p.n for p in plans], B, T, *first.out_shape,
+                           src_bytes=src_bytes)
+    inputs = NamedTensor(full[:, :num_input_steps], DIMS.copy(), io_names)
+    outputs = NamedTensor(full[:, num_input_steps:], DIMS.copy(), list(io_names))
     return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
 
 

@@ -532,3 +532,93 @@ def build_forcing(raw, mean, std, table: torch.Tensor, grid_planes: torch.Tensor
     L.call("p4c_build_forcing", L.ptr(raw), rows, L.ptr(mean), L.ptr(std), L.ptr(planes[0]), L.ptr(planes[1]), L.ptr(planes[2]),
            L.ptr(table), L.ptr(out), B, T, H * W, Fe, L.stream(dev), alg_bytes=4 * rows * (2 * Fe + 5))
     return out
+
+
+# host mirrors of p4c_regrid_tap / p4c_regrid_feature (include/py4cast_hip.h)
+REGRID_TAP = np.dtype([("i0", "<i4"), ("i1", "<i4"), ("f", "<f4"), ("pad", "<i4")])
+REGRID_FEATURE = np.dtype([("src", "<u8"), ("b_stride", "<i8"), ("t_stride", "<i8"), ("pitch", "<i4"), ("row0", "<i4"), ("col0", "<i4"),
+                           ("table", "<i4"), ("mean", "<f4"), ("std", "<f4"), ("channel", "<i4"), ("pad", "<i4")])
+REGRID_MAX_FEATURES = 144
+
+
+def regrid_features(sources, feats, table_dims, B: int, T: int) -> torch.Tensor:
+    """The device descriptors (p4c_regrid_feature) of ``regrid_pack``, checked on the host: everything the kernel will index lies
+    inside its plane, and the output channels are 0 .. F-1, each once.
+
+    sources: device tensors (Fg, B, T, Hs, Ws) fp32, dense.  feats: one tuple per output feature, (index into sources, plane of
+    that source, window row origin, window column origin, tap table, mean, std, output channel).  table_dims: per tap table the
+    (rows, columns) of the windowed source it indexes.  The result holds raw pointers into ``sources``: keep them alive."""
+    L.require_cuda(*sources)
+    F = len(feats)
+    if not 1 <= F <= REGRID_MAX_FEATURES:
+        raise L.P4CError(f"regrid_pack: {F} features: 1 .. at most {REGRID_MAX_FEATURES} per call (LDS tile)")
+    dev = sources[0].device
+    for s in sources:
+        if s.dim() != 5 or tuple(s.shape[1:3]) != (B, T) or s.dtype != torch.float32 or not s.is_contiguous() or s.device != dev:
+            raise L.P4CError(f"regrid_pack: source {tuple(s.shape)} {s.dtype} is not a dense fp32 (Fg, {B}, {T}, Hs, Ws) on {dev}")
+    if sorted(f[7] for f in feats) != list(range(F)):
+        raise L.P4CError(f"regrid_pack: the output channels {sorted(f[7] for f in feats)} are not 0 .. {F - 1}, each once")
+    desc = np.zeros(F, dtype=REGRID_FEATURE)
+    for i, (si, plane, row0, col0, table, mean, std, channel) in enumerate(feats):
+        s = sources[si]
+        Fg, _, _, Hs, Ws = s.shape
+        if not (0 <= plane < Fg and 0 <= table < len(table_dims)):
+            raise L.P4CError(f"regrid_pack: feature {i}: plane {plane} of {Fg}, tap table {table} of {len(table_dims)}")
+        n, m = table_dims[table]
+        if not (0 <= row0 and row0 + n <= Hs and 0 <= col0 and col0 + m <= Ws):
+            raise L.P4CError(f"regrid_pack: feature {i}: window {n} x {m} at ({row0}, {col0}) leaves its {Hs} x {Ws} plane")
+        desc[i] = (s.data_ptr() + 4 * plane * s.stride(0), s.stride(1), s.stride(2), Ws, row0, col0, table, mean, std, channel, 0)
+    return torch.from_numpy(desc.view(np.uint8)).to(dev)
+
+
+def regrid_pack(sources, feats, taps: torch.Tensor, table_dims, B: int, T: int, H: int, W: int, src_bytes: int = 0) -> torch.Tensor:
+    """Native-grid planes -> (B, T, H, W, F) fp32 standardised features-last on the sub-domain, one pass of ``p4c_regrid_pack``
+    (``py4cast_amd/regrid.py`` has the definition and builds the tables).
+
+    sources, feats, table_dims: as ``regrid_features`` takes them; ``feats`` may also be the tensor it returned for these very
+    sources (a caller that launches more than once on the same planes).  taps: (tables, H + W, 4) int32 on the device
+    (``regrid.device_taps``).  src_bytes: the algorithmic bytes read from the sources (``regrid.source_bytes``)."""
+    L.require_cuda(taps, *sources)
+    B, T, H, W = int(B), int(T), int(H), int(W)
+    if taps.dtype != torch.int32 or taps.dim() != 3 or tuple(taps.shape[1:]) != (H + W, 4) or taps.shape[0] != len(table_dims):
+        raise L.P4CError(f"regrid_pack: taps {tuple(taps.shape)} {taps.dtype} are not ({len(table_dims)}, H + W = {H + W}, 4) int32")
+    feats_dev = feats if isinstance(feats, torch.Tensor) else regrid_features(sources, feats, table_dims, B, T)
+    F = feats_dev.numel() // REGRID_FEATURE.itemsize
+    dev = taps.device
+    if feats_dev.device != dev or feats_dev.dtype != torch.uint8 or feats_dev.numel() != F * REGRID_FEATURE.itemsize or F < 1:
+        raise L.P4CError(f"regrid_pack: descriptors {tuple(feats_dev.shape)} {feats_dev.dtype} on {feats_dev.device}: not regrid_features' on {dev}")
+    out = torch.empty(B, T, H, W, F, dtype=torch.float32, device=dev)
+    L.call("p4c_regrid_pack", L.ptr(feats_dev), L.ptr(taps), L.ptr(out), B, T, H, W, F, L.stream(dev),
+           alg_bytes=int(src_bytes) + 4 * out.numel())
+    return out
+
+
+def regrid_blur(src: torch.Tensor, window, row_index: torch.Tensor, col_index: torch.Tensor, row_w: torch.Tensor,
+                col_w: torch.Tensor) -> torch.Tensor:
+    """The Gaussian of ``resize(anti_aliasing=True)`` over the window (r0, r1, c0, c1) of every plane of ``src`` (..., Hs, Ws) ->
+    dense (..., n, m) fp32, ``scipy.ndimage.gaussian_filter(mode="mirror")`` axis 0 then axis 1 (``p4c_regrid_blur``).  row_index:
+    (n + 2 ry) int32 mirrored source rows of the positions -ry .. n - 1 + ry, row_w: (2 ry + 1) weights; columns likewise
+    (``regrid.device_blur_tables``)."""
+    L.require_cuda(src, row_index, col_index, row_w, col_w)
+    if src.dim() < 2:
+        raise L.P4CError(f"regrid_blur: src {tuple(src.shape)} is not (..., Hs, Ws)")
+    src = src.contiguous().float()
+    Hs, Ws = src.shape[-2:]
+    r0, r1, c0, c1 = (int(v) for v in window)
+    n, m = r1 - r0, c1 - c0
+    if not (0 <= r0 and r1 <= Hs and 0 <= c0 and c1 <= Ws):
+        raise L.P4CError(f"regrid_blur: window {(r0, r1, c0, c1)} does not lie inside planes of {Hs} x {Ws}")
+    if n < 2 or m < 2:
+        raise L.P4CError(f"regrid_blur: a {n} x {m} window: each axis needs at least 2 points")
+    ry, rx = (row_w.numel() - 1) // 2, (col_w.numel() - 1) // 2
+    if row_w.numel() != 2 * ry + 1 or col_w.numel() != 2 * rx + 1 or ry > 64 or rx > 64:
+        raise L.P4CError(f"regrid_blur: {row_w.numel()} / {col_w.numel()} weights: an odd count, radius at most 64")
+    if row_index.numel() != n + 2 * ry or col_index.numel() != m + 2 * rx or row_index.dtype != torch.int32 or col_index.dtype != torch.int32:
+        raise L.P4CError(f"regrid_blur: index tables of {row_index.numel()} / {col_index.numel()} {row_index.dtype} entries, "
+                         f"expected int32 of {n + 2 * ry} / {m + 2 * rx}")
+    planes = src.numel() // (Hs * Ws)
+    out = torch.empty(*src.shape[:-2], n, m, dtype=torch.float32, device=src.device)
+    L.call("p4c_regrid_blur", L.ptr(src), Hs * Ws, Ws, r0, c0, L.ptr(out), planes, n, m, L.ptr(row_index.contiguous()),
+           L.ptr(col_index.contiguous()), L.ptr(row_w.contiguous().float()), ry, L.ptr(col_w.contiguous().float()), rx, L.stream(src.device),
+           alg_bytes=4 * planes * 2 * n * m)
+    return out
