@@ -946,6 +946,33 @@ int p4c_ghost_dw_bwd_data(const void* dout, const float* w, void* din, int dtype
 int p4c_ghost_dw_wgrad_blocks(int B, int H, int W);
 int p4c_ghost_dw_wgrad(const void* in, const void* dout, float* partial, int dtype, int B, int H, int W, p4c_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The bf16 route of HalfUNet with Ghost blocks (csrc/ghost.hip).  Features-last maps of 64 channels, storage `dtype` P4C_F32 or P4C_BF16,
+ * fp32 sums, 16-byte aligned bases, no float atomics (per-workgroup partials, summed in a fixed order: reruns are bit-identical).
+ * ------------------------------------------------------------------------------------ */
+/* The Ghost module behind its primary convolution, one pass: prim (B,H,W,32) with a pixel stride ld_prim of 32 or 64 channels, w (32, 9);
+ * out (B,H,W,64), ld_out = 64: out[..., 32 + c] = sum_tap w[c][tap] * prim[p + tap, c] (zero padding), rounded once; out[..., :32] = prim --
+ * not written when prim == out (in place, ld_prim = 64).  partial (p4c_ghost_tail_blocks(B,H,W), 2, 64) or NULL: per-workgroup sums of v
+ * and v^2 over all 64 channels of the values as stored, the producer's statistics p4c_bnorm_finalize takes (count B*H*W). */
+int p4c_ghost_tail_blocks(int B, int H, int W);
+int p4c_ghost_tail_fwd(const void* prim, int ld_prim, const float* w, void* out, int ld_out, float* partial, int dtype, int B, int H, int W,
+                       p4c_stream_t stream);
+/* Its adjoint, one pass over dz (B,H,W,64, the gradient at the concatenated map) and prim:
+ * dprim[p, c] = dz[p, c] + sum_tap w[c][tap] * dz[p - tap, 32 + c]  (B,H,W,32 with a pixel stride ld_dprim of 32 or 64);
+ * wpart (p4c_ghost_tail_bwd_blocks(B,H,W), 32, 9): partial sums of prim[p + tap, c] * dz[p, 32 + c]; the caller sums them in order. */
+int p4c_ghost_tail_bwd_blocks(int B, int H, int W);
+int p4c_ghost_tail_bwd(const void* dz, const void* prim, int ld_prim, const float* w, void* dprim, int ld_dprim, float* wpart, int dtype, int B,
+                       int H, int W, p4c_stream_t stream);
+/* HalfUNet's decoder merge, one write: out = a0 + sum_{k=1..4} up_{2^k}(a_k), a_k (B, H/2^k, W/2^k, 64), bilinear with half-pixel centres and
+ * clamped taps (F.interpolate(scale_factor=2^k, mode="bilinear", align_corners=False)); summed in fp32, rounded once.  H, W multiples of
+ * 16, C = 64 (anything else: P4C_ERR_INVALID). */
+int p4c_halfunet_merge_fwd(const void* a0, const void* a1, const void* a2, const void* a3, const void* a4, void* out, int dtype, int B, int H,
+                           int W, int C, p4c_stream_t stream);
+/* Its adjoint for k = 1..4 from dS (B,H,W,64): da_k = up_{2^k}^T dS, rounded once.  Two launches: the x pass of all four levels over dS into
+ * the caller's FP32 half-width maps tx_k (B, H, W/2^k, 64), then the y pass of all four levels.  (da_0 is dS itself.) */
+int p4c_halfunet_merge_bwd(const void* dS, void* tx1, void* tx2, void* tx3, void* tx4, void* da1, void* da2, void* da3, void* da4, int dtype,
+                           int B, int H, int W, int C, p4c_stream_t stream);
+
 /* ====================================================================================
  * InstanceNorm2d(affine) + LeakyReLU (+ residual) on features-last tensors (B, N = H*W, C) -- MONAI's UnetResBlock norm
  * (config/CLI/model/swinunetr.yaml:23, unetrpp.yaml:24 `norm_name: instance`).  C % 4 == 0, C <= 1024.

@@ -90,6 +90,12 @@ OTHER = {
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_wgrad_blocks": ([I, I, I], c_int),
     "p4c_ghost_dw_wgrad": ([P, P, P, I, I, I, I, P], c_int),
+    "p4c_ghost_tail_blocks": ([I, I, I], c_int),
+    "p4c_ghost_tail_fwd": ([P, I, P, P, I, P, I, I, I, I, P], c_int),
+    "p4c_ghost_tail_bwd_blocks": ([I, I, I], c_int),
+    "p4c_ghost_tail_bwd": ([P, P, I, P, P, I, P, I, I, I, I, P], c_int),
+    "p4c_halfunet_merge_fwd": ([P, P, P, P, P, P, I, I, I, I, I, P], c_int),
+    "p4c_halfunet_merge_bwd": ([P, P, P, P, P, P, P, P, P, I, I, I, I, I, P], c_int),
     "p4c_inorm_blocks": ([L, I], c_int),
     "p4c_inorm_reduce": ([P, P, P, P, P, F, P, I, I, L, I, P], c_int),
     "p4c_inorm_apply": ([P, P, P, P, P, P, P, P, P, P, F, P, P, I, I, L, I, P], c_int),

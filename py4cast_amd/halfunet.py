@@ -149,8 +149,17 @@ class HalfUNetMI355X(ModelABC, nn.Module):
                                    "p4c_sum_state_grads", "p4c_ar_update_next", "p4c_out_conv_update_fwd", "p4c_ar_update_next_bwd")
 
         self.use_ghost = bool(settings.use_ghost)
+        # Ghost blocks with the yaml's other values in bf16: the per-layer nodes below run on the package's own kernels
+        # (`_forward_ghost_native`); every other Ghost setting keeps the module route
+        self._ghost_native = bool(settings.use_ghost and settings.num_filters == NF and settings.dilation == 1 and not settings.bias
+                                  and settings.last_activation == "Identity" and settings.norm == "batch"
+                                  and settings.compute_dtype == "bf16" and act == "bf16")
         if self.module_path:
             self._init_modules(in_channels, out_channels, settings)
+            if self._ghost_native:
+                self.timed_entry_points = ("p4c_gemm_nt", "p4c_gemm_tn", "p4c_ghost_tail_fwd", "p4c_ghost_tail_bwd", "p4c_halfunet_merge_fwd",
+                                           "p4c_halfunet_merge_bwd", "p4c_unet_enc_tail_fwd", "p4c_unet_enc_tail_bwd", "p4c_inorm_apply",
+                                           "p4c_inorm_reduce_finalize_bwd")
             return
         # parameters in the order of p4c_halfunet_param_count (include/py4cast_hip.h)
         self._param_slices = []
@@ -199,7 +208,8 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         Convolutions without dilation to <= 64 channels from <= 96 run on the MFMA conv kernels (ops_model.conv_nhwc: forward, data
         and weight gradient; fewer than 64 output channels as zero rows of a 64-channel launch), the Ghost "cheap operation" at 64
         filters on csrc/depthwise.hip (ops_ghost.ghost_dw); wider or dilated convolutions go through the library; normalisation,
-        pooling and up-sampling are torch ops on the features-last tensors.  The fused C++ plan (p4c_halfunet_forward) serves the
+        pooling and up-sampling are torch ops on the features-last tensors (`_forward_modules`; Ghost blocks with the yaml's other
+        values in bf16 take `_forward_ghost_native` on the same module tree instead: `ghost_native`).  The fused C++ plan (p4c_halfunet_forward) serves the
         yaml's network only, so the rollout takes the generic per-step path here."""
         nf = settings.num_filters
 
@@ -220,6 +230,10 @@ class HalfUNetMI355X(ModelABC, nn.Module):
                 n.register_buffer("running_mean", torch.zeros(nf))
                 n.register_buffer("running_var", torch.ones(nf))
                 n.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+            if self._ghost_native:
+                # what ops_gemm reads from an nn.BatchNorm2d beside the parameters, the buffers and `training` (plain attributes: the
+                # state_dict keeps mfai's names)
+                n.momentum, n.eps, n.track_running_stats = 0.1, 1e-5, True
             return n
 
         for blk, attr in zip(BLOCKS, BLOCK_ATTR):
@@ -315,6 +329,47 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         if not isinstance(self.activation, nn.Identity):
             y = self.activation(y.float()).to(y.dtype)
         return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)
+
+    # ---------------------------------------------------------------- Ghost blocks, bf16, the yaml's other values: native nodes
+    def _forward_ghost_native(self, x):
+        """The Ghost network on the package's own kernels, one autograd node per piece: primary 3x3 convolution to 32 channels
+        (ops_gemm.conv2d_nhwc: csrc/gemm.hip) -> the Ghost tail (depthwise half + batch-norm sums, csrc/ghost.hip) -> batch norm + ReLU
+        (csrc/inorm.hip; with the 2x2 max-pool in the same pass behind ghost2 of levels 1-4, csrc/unet.hip) ...; the decoder merge of
+        the five levels is one kernel each way (csrc/ghost.hip).  bf16 maps, fp32 master parameters, no host synchronisation."""
+        from . import ops_gemm as G
+        from . import ops_ghost_native as GN
+        from .conv_model import crop_channels, pad_head, pad_rows, pad_weight_in
+
+        out_dtype = x.dtype
+        # (the first convolution reads rows zero-padded to the GEMM's 8-channel granularity, its weight zero columns there)
+        h = pad_rows(x.contiguous().to(self.act_dtype), (self.in_channels + 7) // 8 * 8)
+
+        def ghost(g, h, pool=False):
+            prim = G.conv2d_nhwc(h, pad_weight_in(g.conv.weight, h.shape[-1]))
+            z, stats = GN.ghost_tail(prim, g.sepconv.weight, want_stats=self.training)
+            if pool:
+                return GN.bn_relu_pool(z, stats, g.bn)
+            return G.batch_norm_act(z, stats, g.bn, slope=0.0)
+
+        levels = []
+        for k, (blk, attr) in enumerate(zip(BLOCKS[:5], BLOCK_ATTR[:5])):
+            holder = getattr(self, attr)
+            h = ghost(getattr(holder, f"{blk}ghost1"), h)
+            if k < 4:
+                a, h = ghost(getattr(holder, f"{blk}ghost2"), h, pool=True)
+            else:
+                a = ghost(getattr(holder, f"{blk}ghost2"), h)
+            levels.append(a)
+        d = GN.halfunet_merge(*levels)
+        d = ghost(self.decoder.decoderghost2, ghost(self.decoder.decoderghost1, d))
+        w, _ = pad_head(self.outconv.weight, None)
+        y = crop_channels(G.conv2d_nhwc(d, w), self.out_channels)
+        return y if y.dtype == out_dtype or not out_dtype.is_floating_point else y.to(out_dtype)
+
+    @property
+    def ghost_native(self) -> bool:
+        """Ghost blocks on the native bf16 route (decided by the settings at construction)."""
+        return self._ghost_native
 
     @property
     def settings(self):
@@ -458,6 +513,9 @@ class HalfUNetMI355X(ModelABC, nn.Module):
             y = self.forward(torch.nn.functional.pad(x, (0, 0, left, right, top, bottom)))
             return y[:, top: top + H, left: left + W, :]
         if self.module_path:
+            # P4C_GHOST_MODULES=1 (diagnostic mode only): the module route for the native configuration, the A/B side of the tests
+            if self._ghost_native and L.diag_switch("P4C_GHOST_MODULES") in (None, "", "0"):
+                return self._forward_ghost_native(x)
             return self._forward_modules(x)
         if x.shape[-1] == self.in_channels and self.cin_pad != self.in_channels:
             x = torch.nn.functional.pad(x, (0, self.cin_pad - self.in_channels))
