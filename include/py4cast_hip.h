@@ -323,6 +323,39 @@ int p4c_regrid_blur(const float* src, int64_t plane_stride, int pitch, int row0,
                     const int* row_index, const int* col_index, const float* row_w, int ry, const float* col_w, int rx,
                     p4c_stream_t stream);
 
+/* Prediction maps of a validation / test step (PredictionTimestepPlot / PredictionEpochPlot, plots.py:242-485) on the device.
+ *
+ * p4c_map_planes: of prediction / target (B,T,N,F) features-last (strides as p4c_eval_sums takes them) the K features
+ * `features` (device int32, each 0 .. F-1: the caller checks) of the n <= B leading samples, plane-major:
+ *   planes (n,T,K,2,N): [..,0,:] = target * std + mean, [..,1,:] = (pred * mask) * std + mean, every product and sum rounded on
+ *                       its own (bit-exact with plots.py:271, 299-300 in fp32);
+ *   vrange (n,K,2):     min and max of panel 0 over (T,N) (plots.py:311-312); a NaN in the panel gives NaN, as torch.min does.
+ * mask per p4c_mask_mode, explicit masks dense (B,T,N,F); P4C_MASK_FROM_NAN reads the raw target, takes its NaNs as 0 in panel
+ * 0 and as mask 0 in panel 1.  Only the memory lines that hold the K features are read.  No atomics: block partials in
+ * `workspace` (p4c_map_planes_workspace_bytes(n,T,N,K)) and a finish launch; two calls give the same bits.
+ * Limits: K <= 256, N < 2^31, n <= 65535.
+ *
+ * p4c_map_render: planes, vrange -> RGB8 frames (n,T,K,H,2W+G,3), H*W = N, G = p4c_map_gap() white columns between the target
+ * panel (left) and the prediction panel (right); frame row r shows grid row H-1-r (origin="lower").  Per pixel in fp32:
+ *   x = (v - vmin) / (vmax - vmin), 0 when vmax == vmin; index 0 for x < 0, 255 for x >= 1, else floor(256 x) (matplotlib's
+ *   Normalize + Colormap); a = clamp(interior, 0.7, 1) (plots.py:134); out = floor(a*c + (1-a)*255 + 0.5) with c = lut[index];
+ *   a NaN value, a NaN range or a NaN x gives white.
+ * lut: 256 x 3 bytes; interior: (N) floats; frames 4-byte aligned; fewer than 2^31 pixels per call.
+ *
+ * p4c_map_tile / p4c_map_max_blocks: grid points per loop trip of a p4c_map_planes workgroup / workgroups per launch;
+ * p4c_map_render_pixels / p4c_map_render_max_blocks: pixels per thread and trip (256 threads) / workgroups of p4c_map_render. */
+int p4c_map_tile(void);
+int p4c_map_max_blocks(void);
+int p4c_map_gap(void);
+int p4c_map_render_pixels(void);
+int p4c_map_render_max_blocks(void);
+size_t p4c_map_planes_workspace_bytes(int n, int T, int64_t N, int K);
+int p4c_map_planes(const float* pred, int64_t pred_bs, int64_t pred_ts, const float* target, int64_t tgt_bs, int64_t tgt_ts,
+                   const void* mask, int mask_mode, const float* std, const float* mean, const int32_t* features, float* planes,
+                   float* vrange, void* workspace, int n, int T, int64_t N, int F, int K, p4c_stream_t stream);
+int p4c_map_render(const float* planes, const float* vrange, const unsigned char* lut, const float* interior,
+                   unsigned char* frames, int n, int T, int K, int H, int W, p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

@@ -56,6 +56,10 @@ SIGNATURES = {
     "p4c_regrid_pack": [P, P, P, I, I, I, I, I, P],
     # src, plane_stride, pitch, row0, col0, dst, planes, n, m, row_index, col_index, row_w, ry, col_w, rx, stream
     "p4c_regrid_blur": [P, L, I, I, I, P, I, I, I, P, P, P, I, P, I, P],
+    # pred, bs, ts, target, bs, ts, mask, mode, std, mean, features, planes, vrange, ws, n, T, N, F, K, stream
+    "p4c_map_planes": [P, L, L, P, L, L, P, I, P, P, P, P, P, P, I, I, L, I, I, P],
+    # planes, vrange, lut, interior, frames, n, T, K, H, W, stream
+    "p4c_map_render": [P, P, P, P, P, I, I, I, I, I, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],
@@ -85,6 +89,12 @@ OTHER = {
     "p4c_loss_workspace_bytes": ([I, I, L, I], c_size_t),
     "p4c_psd_workspace_bytes": ([I, I, I, I], c_size_t),
     "p4c_eval_sums_workspace_bytes": ([I, I, L, I], c_size_t),
+    "p4c_map_planes_workspace_bytes": ([I, I, L, I], c_size_t),
+    "p4c_map_tile": ([], c_int),
+    "p4c_map_max_blocks": ([], c_int),
+    "p4c_map_gap": ([], c_int),
+    "p4c_map_render_pixels": ([], c_int),
+    "p4c_map_render_max_blocks": ([], c_int),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

@@ -638,9 +638,10 @@ class AutoRegressiveLightning(_Base):
 
     # ------------------------------------------------------------------ observers (plots / metrics of the reference)
     # The score-card and spatial-error plotters and the three metrics are native (observers.py, metrics.py) and always attached;
-    # one ops.eval_sums pass per step feeds both plotters.  PredictionTimestepPlot and PredictionEpochPlot need cartopy projections:
-    # they are py4cast's own host-side code and are attached when the `py4cast` package is importable, where the reference has them
-    # (lightning.py:868-1065).  They receive the lazy mask / target of get_mask_on_nan.
+    # one ops.eval_sums pass per step feeds both plotters.  PredictionTimestepPlot and PredictionEpochPlot: where the `py4cast` package
+    # (with cartopy) is importable its own host-side classes are attached, where the reference has them (lightning.py:868-1065); they
+    # receive the lazy mask / target of get_mask_on_nan.  Anywhere else the native ones (observers.py: ops.map_planes + ops.map_render,
+    # no map projection) are kept in valid_map_plotters / test_map_plotters and notified after the others.
     @staticmethod
     def _reference_observers():
         try:
@@ -671,9 +672,9 @@ class AutoRegressiveLightning(_Base):
 
     def on_validation_start(self):
         """lightning.py:864-886."""
-        self.valid_plotters = []
+        self.valid_plotters, self.valid_map_plotters = [], []
         if self.logging_enabled:
-            from .observers import StateErrorPlot
+            from .observers import PredictionEpochPlot, PredictionTimestepPlot, StateErrorPlot
 
             l1_loss = ScaledLoss("L1Loss", reduction="none")
             l1_loss.prepare(self, self.interior_mask, self.dataset_info)
@@ -685,12 +686,18 @@ class AutoRegressiveLightning(_Base):
                     ref_plots.PredictionTimestepPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
                     ref_plots.PredictionEpochPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
                 ]
+            else:
+                sp = getattr(self, "save_path", None)
+                self.valid_map_plotters = [
+                    PredictionTimestepPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
+                    PredictionEpochPlot(num_samples_to_plot=1, num_features_to_plot=4, prefix="Validation", save_path=sp),
+                ]
 
     def on_test_start(self):
         """lightning.py:986-1008."""
-        self.test_plotters = []
+        self.test_plotters, self.test_map_plotters = [], []
         if self.logging_enabled:
-            from .observers import SpatialErrorPlot, StateErrorPlot
+            from .observers import PredictionTimestepPlot, SpatialErrorPlot, StateErrorPlot
 
             metrics = {}
             for torch_loss, alias in ("L1Loss", "mae"), ("MSELoss", "rmse"):
@@ -706,6 +713,9 @@ class AutoRegressiveLightning(_Base):
                 self.test_plotters.append(
                     ref_plots.PredictionTimestepPlot(num_samples_to_plot=self.num_samples_to_plot, num_features_to_plot=4,
                                                      prefix="Test", save_path=sp))
+            else:
+                self.test_map_plotters = [PredictionTimestepPlot(num_samples_to_plot=self.num_samples_to_plot, num_features_to_plot=4,
+                                                                 prefix="Test", save_path=sp)]
 
     def _notify(self, plotters, batch, prediction, target, mask):
         for plotter in plotters:
@@ -720,13 +730,17 @@ class AutoRegressiveLightning(_Base):
         """lightning.py:919-941."""
         if self.logging_enabled:
             plot_period = 10   # PLOT_PERIOD, lightning.py:54
-            self._notify(getattr(self, "valid_plotters", []) if self.current_epoch_ % plot_period == 0 else [], batch, prediction,
-                         target, mask)
+            on_period = self.current_epoch_ % plot_period == 0
+            self._notify(getattr(self, "valid_plotters", []) if on_period else [], batch, prediction, target, mask)
+            for plotter in getattr(self, "valid_map_plotters", []) if on_period else []:
+                plotter.update(self, batch=batch, prediction=prediction, target=target, mask=mask)
 
     def test_step_logging(self, batch, prediction, target, mask):
         """lightning.py:1044-1065."""
         if self.logging_enabled:
             self._notify(getattr(self, "test_plotters", []), batch, prediction, target, mask)
+            for plotter in getattr(self, "test_map_plotters", []):
+                plotter.update(self, batch=batch, prediction=prediction, target=target, mask=mask)
 
     def _epoch_end(self, plotters, label: str, prefix=None):
         """lightning.py:943-982 / 1067-1103: metric results are logged (tensors) or handed to the logger (figures)."""

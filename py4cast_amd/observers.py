@@ -15,6 +15,10 @@ concatenated batches, ranks having equal batch shapes there.
 The shared pass is taken when ``metrics`` holds only ``ScaledLoss`` members on L1Loss / MSELoss (scores) and ``obj.loss`` is a
 single ``WeightedLoss`` on one of them, bare or as the only member (weight 1) of a ``CombinedLoss`` (map); anything else calls the metric objects / ``obj.loss`` as the reference does and feeds
 the same state.  Figures are plain matplotlib; without matplotlib they are skipped and everything else is still produced.
+
+``PredictionTimestepPlot`` and ``PredictionEpochPlot`` (``plots.py:242-485``) are here as well, at the end of the module: the
+reference's constructor, bookkeeping and output names around ``ops.map_planes`` + ``ops.map_render`` (``csrc/map_frames.hip``),
+which make finished RGB frames of the drawn samples and variables on the device; no map projection.
 """
 
 import json
@@ -154,8 +158,9 @@ def _pyplot():
         return None
 
 
-def _hand_on(obj, fig, name: str, step: int, dest: Optional[Path]):
-    """a figure to the logger's experiment, to a png and to mlflow, as plots.py:561-576 does"""
+def _hand_on(obj, fig, name: str, step: int, dest: Optional[Path], artifact: Optional[str] = None):
+    """a figure to the logger's experiment, to a png and to mlflow, as plots.py:561-576 does (``artifact``: the mlflow file name
+    where it is not ``name``)"""
     experiment = _experiment(obj)
     if experiment is not None and hasattr(experiment, "add_figure"):
         experiment.add_figure(name, fig, step)
@@ -164,7 +169,7 @@ def _hand_on(obj, fig, name: str, step: int, dest: Optional[Path]):
         fig.savefig(dest)
     mlflow_logger = getattr(obj, "mlflow_logger", None)
     if mlflow_logger:
-        mlflow_logger.experiment.log_figure(run_id=mlflow_logger.version, figure=fig, artifact_file=f"figures/{name}.png")
+        mlflow_logger.experiment.log_figure(run_id=mlflow_logger.version, figure=fig, artifact_file=f"figures/{artifact or name}.png")
 
 
 def plot_score_card(errors: np.ndarray, shortnames, units, title=None, step_duration=3):
@@ -319,3 +324,204 @@ class SpatialErrorPlot:
             if fig is None:
                 break
             _hand_on(obj, fig, f"spatial_error_{label}/{self.prefix}_loss", t_i, None)
+
+
+# ------------------------------------------------------------------------------------------------ prediction maps
+def plasma_table() -> Optional[np.ndarray]:
+    """matplotlib's ``plasma`` as the (256,3) uint8 colour table of ``ops.map_render``; None without matplotlib"""
+    try:
+        import matplotlib
+
+        return np.ascontiguousarray(matplotlib.colormaps["plasma"](np.arange(256), bytes=True)[:, :3], dtype=np.uint8)
+    except Exception:   # noqa: BLE001  (matplotlib absent or unusable)
+        return None
+
+
+def plot_prediction_frame(frame: np.ndarray, vmin: float, vmax: float, title=None):
+    """One rendered frame (H, 2W+MAP_GAP, 3) as the reference's two-panel figure (plots.py:113-163 without the map projection):
+    the halves under "Ground Truth" and "Prediction", one colour bar on the frame's range.  None without matplotlib."""
+    plt = _pyplot()
+    if plt is None:
+        return None
+    from matplotlib.cm import ScalarMappable
+    from matplotlib.colors import Normalize
+
+    H, W = frame.shape[0], (frame.shape[1] - ops.MAP_GAP) // 2
+    fig, axes = plt.subplots(1, 2, figsize=(13, 7))
+    extent = (-0.5, W - 0.5, -0.5, H - 0.5)   # the frame's top row is the grid's last: the axes count as origin="lower" does
+    for ax, panel, name in zip(axes, (frame[:, :W], frame[:, W + ops.MAP_GAP:]), ("Ground Truth", "Prediction")):
+        ax.imshow(panel, extent=extent, interpolation="none")
+        ax.set_title(name, size=15)
+    if np.isfinite(vmin) and np.isfinite(vmax):
+        cbar = fig.colorbar(ScalarMappable(norm=Normalize(vmin=vmin, vmax=vmax), cmap="plasma"), ax=list(axes), aspect=30)
+        cbar.ax.tick_params(labelsize=10)
+    if title:
+        fig.suptitle(title, size=20)
+    plt.close(fig)
+    return fig
+
+
+def write_gif(frames: np.ndarray, dest: Path) -> None:
+    """(T,H,W,3) uint8 frames -> a looping GIF, 250 ms per frame (plots.py:349-359), written with PIL from the frames themselves"""
+    from PIL import Image
+
+    images = [Image.fromarray(np.ascontiguousarray(f), mode="RGB") for f in frames]
+    dest.parent.mkdir(parents=True, exist_ok=True)
+    images[0].save(dest, format="GIF", append_images=images[1:], save_all=True, duration=250, loop=0)
+
+
+class MapPlot:
+    """What PredictionTimestepPlot and PredictionEpochPlot share (plots.py:242-346): the reference's constructor and bookkeeping --
+    rank zero only, ``min(B, remaining)`` samples until ``num_samples_to_plot`` are drawn, the first ``num_features_to_plot``
+    variables or all -- around ONE ``ops.map_planes`` call, ONE ``ops.map_render`` call and ONE asynchronous copy of the frames
+    and their colour ranges to pinned host memory, where the reference rescales the whole prediction and target and fetches a
+    strided plane per (lead time, variable, panel).  ``lut``: a (256,3) uint8 colour table instead of matplotlib's plasma
+    (without matplotlib and without a table nothing can be rendered; with one the GIF is still written)."""
+
+    last_step_only = False   # render only the last lead time (the colour range still spans all of them)
+
+    def __init__(self, num_samples_to_plot: int, num_features_to_plot: Optional[int] = None, prefix: str = "Test",
+                 save_path: Path = None, lut=None):
+        self.num_samples_to_plot = num_samples_to_plot
+        self.plotted_examples = 0
+        self.prefix = prefix
+        self.num_features_to_plot = num_features_to_plot
+        self.save_path = None if save_path is None else Path(save_path)
+        self._lut_host = None if lut is None else np.ascontiguousarray(np.asarray(lut), dtype=np.uint8).reshape(256, 3)
+        self._cache = {}   # device-side constants: colour table, interior mask, std / mean
+
+    # ---- bookkeeping (host only)
+    def remaining(self, obj, batch_size: int) -> int:
+        """how many leading samples of this batch are drawn (plots.py:284-291)"""
+        if not _is_global_zero(obj) or self.plotted_examples >= self.num_samples_to_plot:
+            return 0
+        return min(int(batch_size), self.num_samples_to_plot - self.plotted_examples)
+
+    def feature_names(self, prediction: NamedTensor) -> List[str]:
+        names = list(prediction.feature_names)
+        return names[: self.num_features_to_plot] if self.num_features_to_plot else names   # plots.py:315-319
+
+    @staticmethod
+    def units(obj, names: Sequence[str]) -> List[str]:
+        units = getattr(getattr(obj, "dataset_info", None), "units", None) or {}
+        return [units.get(name, "") for name in names]
+
+    @staticmethod
+    def pred_step(obj):
+        step = getattr(getattr(obj, "dataset_info", None), "pred_step", None)
+        return 1 if step is None else step   # without a step duration the lead time counts steps
+
+    @staticmethod
+    def grid(obj, prediction: NamedTensor):
+        """(H, W) of the maps; the graph layout (B,T,N,F) unfolds through ``obj.grid_shape`` (plots.py:276-282)"""
+        shape = tuple(prediction.tensor.shape[2:-1])
+        if len(shape) == 1:
+            H = int(obj.grid_shape[0])
+            return H, shape[0] // H
+        return int(shape[0]), int(shape[1])
+
+    def table(self) -> Optional[np.ndarray]:
+        if self._lut_host is None:
+            self._lut_host = plasma_table()   # taken from matplotlib once
+        return self._lut_host
+
+    # ---- device side
+    def _constants(self, obj, prediction: NamedTensor, H: int, W: int):
+        dev, names = prediction.tensor.device, tuple(prediction.feature_names)
+        key = (dev, names, H, W)
+        if self._cache.get("key") != key:
+            interior = getattr(obj, "interior_2d", None)
+            interior = (torch.ones(H * W, dtype=torch.float32, device=dev) if interior is None
+                        else interior[:, :, 0].detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous())
+            self._cache = {
+                "key": key, "interior": interior, "lut": torch.from_numpy(self.table()).to(dev),
+                "std": obj.stats.to_list("std", list(names)).to(device=dev, dtype=torch.float32),
+                "mean": obj.stats.to_list("mean", list(names)).to(device=dev, dtype=torch.float32),
+            }
+        return self._cache
+
+    def render(self, obj, prediction: NamedTensor, target: NamedTensor, mask, n: int, K: int):
+        """-> (frames (n,T',K,H,2W+G,3) uint8, vrange (n,K,2) float32) as numpy views of one pinned buffer, complete"""
+        H, W = self.grid(obj, prediction)
+        c = self._constants(obj, prediction, H, W)
+        spec, tgt = _mask_spec(mask, target)
+        planes, vrange = ops.map_planes(prediction.tensor, tgt, spec, c["std"], c["mean"], range(K), n)
+        if self.last_step_only:
+            planes = planes[:, -1:].contiguous()
+        shape = tuple(planes.shape[:3]) + (H, 2 * W + ops.MAP_GAP, 3)
+        nbytes = int(np.prod(shape))
+        tail = (nbytes + 3) // 4 * 4
+        packed = torch.empty(tail + 4 * vrange.numel(), dtype=torch.uint8, device=planes.device)   # frames, then the ranges
+        ops.map_render(planes, vrange, c["lut"], c["interior"], H, W, out=packed[:nbytes].view(shape))
+        packed[tail:].view(torch.float32).copy_(vrange.reshape(-1))
+        host = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(packed, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(planes.device))
+        done.synchronize()   # the figures are composed at once, as the reference does inside update
+        flat = host.numpy()
+        return flat[:nbytes].reshape(shape), flat[tail:].view(np.float32).reshape(tuple(vrange.shape))
+
+    def update(self, obj, batch, prediction: NamedTensor, target: NamedTensor, mask) -> None:
+        n = self.remaining(obj, prediction.tensor.shape[0])
+        if n == 0:
+            return
+        names = self.feature_names(prediction)
+        if self.table() is None:   # no matplotlib and no table: nothing to draw with
+            self.plotted_examples += n
+            return
+        frames, vrange = self.render(obj, prediction, target, mask, n, len(names))
+        for s in range(n):
+            self.plotted_examples += 1   # plots.py:309
+            self.plot_map(obj, frames[s], vrange[s], names)
+
+    def plot_map(self, obj, frames: np.ndarray, vrange: np.ndarray, names: List[str]) -> None:  # pragma: no cover - abstract
+        raise NotImplementedError
+
+    def on_step_end(self, obj, label: str = "") -> None:
+        pass
+
+
+class PredictionTimestepPlot(MapPlot):
+    """Prediction against target for each lead time, and a GIF per variable (plots.py:362-423)."""
+
+    def titles(self, obj, names: Sequence[str], t_i: int) -> List[str]:
+        step = self.pred_step(obj)
+        return [f"{name} ({unit}), t={t_i} ({step * t_i} h)" for name, unit in zip(names, self.units(obj, names))]
+
+    def plot_map(self, obj, frames, vrange, names) -> None:
+        for t_i in range(1, frames.shape[0] + 1):
+            for k, (name, title) in enumerate(zip(names, self.titles(obj, names, t_i))):
+                fig = plot_prediction_frame(frames[t_i - 1, k], float(vrange[k, 0]), float(vrange[k, 1]), title=title)
+                if fig is None:
+                    break
+                fig_name = f"timestep_evol_per_param/{name}_example_{self.plotted_examples}"
+                dest = None if self.save_path is None else self.save_path / f"{fig_name}_{t_i}.png"
+                _hand_on(obj, fig, fig_name, t_i, dest, artifact=f"{fig_name}_{t_i}")
+        if self.save_path is not None and frames.shape[0] > 1:   # plots.py:419-423
+            for k, name in enumerate(names):
+                write_gif(frames[:, k], self.save_path / f"timestep_evol_per_param/{name}.gif")
+
+
+class PredictionEpochPlot(MapPlot):
+    """Prediction against target at the last lead time, once per epoch (plots.py:426-485)."""
+
+    last_step_only = True
+
+    def titles(self, obj, names: Sequence[str], max_step: int) -> List[str]:
+        leadtime, epoch = self.pred_step(obj) * max_step, int(getattr(obj, "current_epoch", 0) or 0)
+        return [f"{name} ({unit}), t={max_step} ({leadtime} h) - epoch {epoch}" for name, unit in zip(names, self.units(obj, names))]
+
+    def render(self, obj, prediction, target, mask, n, K):
+        self._max_step = int(prediction.tensor.shape[1])
+        return super().render(obj, prediction, target, mask, n, K)
+
+    def plot_map(self, obj, frames, vrange, names) -> None:
+        epoch = int(getattr(obj, "current_epoch", 0) or 0)
+        for k, (name, title) in enumerate(zip(names, self.titles(obj, names, self._max_step))):
+            fig = plot_prediction_frame(frames[-1, k], float(vrange[k, 0]), float(vrange[k, 1]), title=title)
+            if fig is None:
+                break
+            fig_name = f"epoch_evol_per_param/{name}_example_{self.plotted_examples}"
+            dest = None if self.save_path is None else self.save_path / f"{fig_name}_{epoch}.png"
+            _hand_on(obj, fig, fig_name, epoch, dest, artifact=f"{fig_name}_{epoch}")

@@ -622,3 +622,94 @@ def regrid_blur(src: torch.Tensor, window, row_index: torch.Tensor, col_index: t
            L.ptr(col_index.contiguous()), L.ptr(row_w.contiguous().float()), ry, L.ptr(col_w.contiguous().float()), rx, L.stream(src.device),
            alg_bytes=4 * planes * 2 * n * m)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ prediction maps
+# launch constants of csrc/map_frames.hip (the library reports the same through p4c_map_tile() etc.): a test sizes a case past
+# one loop trip from them
+MAP_TILE = 256                # grid points per loop trip of a map_planes workgroup
+MAP_MAX_BLOCKS = 512          # workgroups of one map_planes launch, all samples together
+MAP_MAX_FEATURES = 256        # K of one map_planes call
+MAP_GAP = 8                   # white columns between the target and the prediction panel of a frame
+MAP_RENDER_PIXELS = 4         # pixels per thread (256 per workgroup) and loop trip of map_render
+MAP_RENDER_MAX_BLOCKS = 512   # workgroups of one map_render launch
+
+
+@functools.lru_cache(maxsize=32)
+def _map_feature_index(features: tuple, device_index: int) -> torch.Tensor:
+    return torch.tensor(features, dtype=torch.int32, device=torch.device("cuda", device_index))
+
+
+def map_planes(pred, target, spec: MaskSpec, std, mean, features, n: int):
+    """Prediction and target (B,T,*S,F) -> the planes the map observers draw, of the ``n`` leading samples and the features
+    ``features`` (indices into F) only (p4c_map_planes): ``planes`` (n,T,K,2,N) fp32 with [..., 0, :] = ``target*std+mean`` and
+    [..., 1, :] = ``(pred*mask)*std+mean`` -- the two / three separately rounded fp32 steps of plots.py:271, 299-300 -- and
+    ``vrange`` (n,K,2), min and max of panel 0 over (T,N) (plots.py:311-312; NaN propagates).  ``spec`` as for ``eval_sums``; with
+    MASK_FROM_NAN ``target`` is the raw target and its NaNs count as 0.  Not differentiable."""
+    L.require_cuda(pred, target, std, mean)
+    if pred.dim() < 4 or pred.shape != target.shape:
+        raise L.P4CError(f"map_planes: prediction {tuple(pred.shape)} / target {tuple(target.shape)}: equal (B, T, *spatial, F) expected")
+    B, T, F = pred.shape[0], pred.shape[1], pred.shape[-1]
+    N = _numel_spatial(pred, 2)
+    features = tuple(int(f) for f in features)
+    K, n = len(features), int(n)
+    if not 1 <= n <= B:
+        raise L.P4CError(f"map_planes: n = {n} samples of a batch of {B}")
+    if not 1 <= K <= MAP_MAX_FEATURES:
+        raise L.P4CError(f"map_planes: {K} features: 1 .. at most {MAP_MAX_FEATURES} per call")
+    if min(features) < 0 or max(features) >= F:
+        raise L.P4CError(f"map_planes: feature indices {features} leave 0 .. {F - 1}")
+    if std.numel() != F or mean.numel() != F:
+        raise L.P4CError(f"map_planes: {std.numel()} standard deviations / {mean.numel()} means for {F} features")
+    if spec.mode in (L.MASK_F32, L.MASK_U8):
+        if spec.tensor is None or spec.tensor.numel() != pred.numel() or not spec.tensor.is_contiguous() or spec.tensor.device != pred.device:
+            raise L.P4CError("map_planes: an explicit mask is a dense tensor of the prediction's shape on its device")
+    p, (pbs, pts) = _rows(pred.detach().float(), 2)
+    g, (gbs, gts) = _rows(target.detach().float(), 2)
+    dev = p.device
+    std, mean = std.to(p).contiguous(), mean.to(p).contiguous()
+    planes = torch.empty(n, T, K, 2, N, dtype=torch.float32, device=dev)
+    vrange = torch.empty(n, K, 2, dtype=torch.float32, device=dev)
+    ws = torch.empty(L.lib().p4c_map_planes_workspace_bytes(n, T, N, K) // 4, dtype=torch.float32, device=dev)
+    index = _map_feature_index(features, dev.index if dev.index is not None else torch.cuda.current_device())
+    L.call(
+        "p4c_map_planes", L.ptr(p), pbs, pts, L.ptr(g), gbs, gts, L.ptr(spec.tensor), spec.mode, L.ptr(std), L.ptr(mean), L.ptr(index),
+        L.ptr(planes), L.ptr(vrange), L.ptr(ws), n, T, N, F, K, L.stream(dev),
+        alg_bytes=n * T * N * K * (2 * 64 + 2 * 4),   # a 64-byte line per point and tensor where the K features share one
+    )
+    return planes, vrange
+
+
+def map_render(planes, vrange, lut, interior, H: int, W: int, out: torch.Tensor = None) -> torch.Tensor:
+    """``map_planes``' results -> RGB8 frames (n,T,K,H,2W+MAP_GAP,3) (p4c_map_render): the target panel left, the prediction
+    right, MAP_GAP white columns between, grid row 0 at the bottom.  ``lut``: (256,3) uint8 colour table; ``interior``: the
+    (H*W,) interior mask, the border fades to ``clamp(interior, 0.7, 1)`` over white (plots.py:134).  The colour index is
+    matplotlib's: 0 below the range, 255 from its top, else floor(256 (v-vmin)/(vmax-vmin)); NaN is white.  ``out``: a dense uint8 device tensor of the
+    frames' shape at a 4-byte aligned address to render into (a caller that ships frames and ranges in one buffer)."""
+    L.require_cuda(planes, vrange, lut, interior)
+    H, W = int(H), int(W)
+    if planes.dim() != 5 or planes.shape[3] != 2 or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise L.P4CError(f"map_render: planes {tuple(planes.shape)} {planes.dtype}: a dense fp32 (n, T, K, 2, N) expected")
+    n, T, K, _, N = planes.shape
+    if H < 1 or W < 1 or H * W != N:
+        raise L.P4CError(f"map_render: a {H} x {W} grid for planes of {N} points")
+    if tuple(vrange.shape) != (n, K, 2) or vrange.dtype != torch.float32 or not vrange.is_contiguous():
+        raise L.P4CError(f"map_render: vrange {tuple(vrange.shape)} {vrange.dtype}: a dense fp32 ({n}, {K}, 2) expected")
+    if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8 or not lut.is_contiguous():
+        raise L.P4CError(f"map_render: colour table {tuple(lut.shape)} {lut.dtype}: a dense uint8 (256, 3) expected")
+    if interior.numel() != N:
+        raise L.P4CError(f"map_render: an interior mask of {interior.numel()} points for planes of {N}")
+    RW = 2 * W + MAP_GAP
+    if n * T * K * H * RW >= 2 ** 31:
+        raise L.P4CError(f"map_render: {n * T * K * H * RW} pixels: fewer than 2^31 per call")
+    interior = interior.reshape(-1).to(planes).contiguous()
+    shape = (n, T, K, H, RW, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=planes.device)
+    elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != planes.device
+          or out.data_ptr() % 4):
+        raise L.P4CError(f"map_render: out {tuple(out.shape)} {out.dtype}: a dense, 4-byte aligned uint8 {shape} on {planes.device} expected")
+    frames = out
+    L.call("p4c_map_render", L.ptr(planes), L.ptr(vrange), L.ptr(lut), L.ptr(interior), L.ptr(frames), n, T, K, H, W,
+           L.stream(planes.device), alg_bytes=planes.numel() * 4 + frames.numel())
+    return frames
