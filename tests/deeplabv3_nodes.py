@@ -10,7 +10,10 @@ in order: clones of the inputs, deep copies of the node's batch norm taken befor
 each output receives in the backward (cloned on entry) together with the gradients the node returns, and which recorded output each
 input is.  The calls themselves are untouched: same arguments, same kernels.  The expected call schedule is built from the model's
 modules (``schedule``) and checked call by call; the counts are asserted on exit, so a model change that routes around a recorded entry
-point fails loudly.
+point fails loudly.  What differs between the three ResNet-encoder models -- the schedule, the module whose names are patched, the extra
+node kinds -- comes from a ``Description``: DeepLabV3's here (the default), CustomUNet's in tests/customunet_nodes.py, DeepLabV3Plus's in
+tests/deeplabv3plus_nodes.py; the references of their extra nodes (``dw_node``, ``upcat_node``, ``up2cat_node``, ``stemskip_node``) and the
+``Composer`` their CPU tests build the whole network with stand beside DeepLabV3's below.
 
 References: float64 on bf16-rounded operands (the GEMM weights rounded as the GEMM reads them; the ASPP pooling branch's 1x1 weight
 and every batch-norm parameter as given: those kernels read fp32).  For a backward they take every decision from the values the device
@@ -195,6 +198,89 @@ def upsample_node(x, scale=8, dout=None):
     return out.detach(), _grads(out, (x64,), dout.double())[0]
 
 
+# ---- the nodes DeepLabV3Plus (tests/deeplabv3plus_nodes.py) and CustomUNet (tests/customunet_nodes.py) add
+
+DW = namedtuple("DW", "ys dx dws")
+
+
+def dw_node(x, ws, rates, dys=None):
+    """float64 depthwise 3x3 at R rates: ys[r] = F.conv2d(x, w_r, padding = dilation = d_r, groups = C) of a features-last x with the
+    (C, 1, 3, 3) weights AS GIVEN (the kernel reads the fp32 masters and rounds no weight).  With dys: the adjoint written out tap by
+    tap on zero-padded maps -- dx = the sum over the rates of sum_t w_r[t] dy_r[p - off_t], dws[r][c, t] = sum_p dy_r[p] x[p + off_t]
+    (tests/test_deeplabv3plus_nodes_cpu.py holds it to the autograd of F.conv2d, rates beyond the map included)."""
+    B, H, W, C = x.shape
+    x64 = x.detach().double()
+    w64 = [w.detach().double() for w in ws]
+    xn = x64.permute(0, 3, 1, 2)
+    ys = [F.conv2d(xn, w, padding=d, dilation=d, groups=C).permute(0, 2, 3, 1) for w, d in zip(w64, rates)]
+    if dys is None:
+        return DW(ys, None, None)
+    dx, dws = 0, []
+    for w, d, dy in zip(w64, rates, dys):
+        g = dy.detach().double()
+        gp, xp = F.pad(g, (0, 0, d, d, d, d)), F.pad(x64, (0, 0, d, d, d, d))
+        dw = torch.empty(C, 9, dtype=torch.float64, device=x.device)
+        for ky in range(3):
+            for kx in range(3):
+                # y[p] takes x[p + (ky - 1, kx - 1) d]: dx[p] takes dy[p - that offset], dw the product summed over the map
+                dx = dx + w[:, 0, ky, kx] * gp[:, (2 - ky) * d: (2 - ky) * d + H, (2 - kx) * d: (2 - kx) * d + W, :]
+                dw[:, ky * 3 + kx] = (g * xp[:, ky * d: ky * d + H, kx * d: kx * d + W, :]).sum((0, 1, 2))
+        dws.append(dw.view(C, 1, 3, 3))
+    return DW(ys, dx, dws)
+
+
+def upcat_node(a, skip, scale, ld, dout=None):
+    """float64 ``[F.interpolate(a, scale, bilinear, align_corners=True) | skip | zeros up to ld]``; with dout (out, da, dskip): da the
+    up-sampling's adjoint of dout's first Ca channels, dskip the slice"""
+    Ca, Cs = a.shape[-1], skip.shape[-1]
+    up = upsample_node(a, scale)
+    out = torch.cat([up, skip.detach().double(), up.new_zeros(*up.shape[:3], ld - Ca - Cs)], -1)
+    if dout is None:
+        return out
+    d = dout.detach().double()
+    return out, upsample_node(a, scale, dout=d[..., :Ca])[1], d[..., Ca: Ca + Cs]
+
+
+def up2cat_node(x, skip, dout=None):
+    """float64 ``[nearest_x2(x) | skip]`` (skip None: the up-sampling alone; for up2_into: skip = the buffer's channels from Cx on);
+    with dout (out, dx, dskip): dx the sum of the four, dskip the slice (None without a skip)"""
+    Cx = x.shape[-1]
+    up = x.detach().double().repeat_interleave(2, 1).repeat_interleave(2, 2)
+    out = up if skip is None else torch.cat([up, skip.detach().double()], -1)
+    if dout is None:
+        return out
+    d = dout.detach().double()
+    B, H2, W2, _ = d.shape
+    dx = d[..., :Cx].reshape(B, H2 // 2, 2, W2 // 2, 2, Cx).sum((2, 4))
+    return out, dx, (None if skip is None else d[..., Cx:])
+
+
+STEMSKIP = namedtuple("STEMSKIP", "act pool pool_at_arg mean var var_unbiased dy dgamma dbeta")
+
+
+def stemskip_node(y, gamma, beta, eps, running=None, arg=None, act_stored=None, dpool=None, dskip=None):
+    """stem_node with the activated map as a second output: act = relu(bn(y)), pool = max_pool2d(act, 3, 2, 1).  With dpool and dskip:
+    the backward with the routing from `arg` (the device's table) and dskip added BEFORE the ReLU mask, taken from the stored
+    activation > 0 (act_stored): dz = (dskip + the dpool of the windows that chose the pixel) [act > 0]."""
+    b = bn_act(y, gamma, beta, eps, slope=0.0, running=running)
+    a = b.out
+    pool = F.max_pool2d(a.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+    at_arg = None if arg is None else _pool_windows(a, arg)
+    dy = dgamma = dbeta = None
+    if dpool is not None:
+        B, H, W, C = y.shape
+        Ho, Wo = arg.shape[1], arg.shape[2]
+        g = dpool.detach().double()
+        dap = torch.zeros(B, H + 2, W + 2, C, dtype=torch.float64, device=y.device)
+        for k in range(9):
+            ky, kx = divmod(k, 3)
+            dap[:, ky: ky + 2 * (Ho - 1) + 1: 2, kx: kx + 2 * (Wo - 1) + 1: 2, :] += torch.where(arg.long() == k, g, torch.zeros_like(g))
+        da = (dap[:, 1: H + 1, 1: W + 1, :] + dskip.detach().double()) * (act_stored.detach().double() > 0)
+        bb = bn_act(y, gamma, beta, eps, slope=1.0, running=running, dout=da)
+        dy, dgamma, dbeta = bb.dy, bb.dgamma, bb.dbeta
+    return STEMSKIP(a, pool, at_arg, b.mean, b.var, b.var_unbiased, dy, dgamma, dbeta)
+
+
 # ------------------------------------------------------------------------------------------------ the recorder
 
 # node kinds: "patch" (DeepLabV3MI355X._patch: ops_patch._PatchConv), "conv" (conv2d_nhwc), "bn" (batch_norm_act), "stem" (stem_tail),
@@ -210,9 +296,10 @@ GRAD_SLOTS = {"patch": {"x": 0, "w": 1}, "conv": {"x": 0, "w": 1, "b": 2}, "bn":
 DIFF_INPUTS = {"patch": ("x",), "conv": ("x",), "bn": ("y", "res"), "stem": ("y",), "aspp": ("x", "a0", "a1", "a2", "a3"), "up": ("x",)}
 
 
-def schedule(model):
-    """[(kind, module name, module)] in the order DeepLabV3MI355X._forward_native calls its nodes (the bf16 route)"""
-    s = [("patch", "encoder.conv1"), ("stem", "encoder.bn1")]
+def encoder_schedule(model):
+    """[(kind, module name)] of the stem's convolution and the four ResNet layers, in the order ``_block`` calls its nodes (the stem
+    tail, whose kind differs between the models, goes between entry 0 and the rest)"""
+    s = [("patch", "encoder.conv1")]
     enc = model.encoder
     for li in range(1, 5):
         for j, blk in enumerate(getattr(enc, f"layer{li}")):
@@ -223,6 +310,13 @@ def schedule(model):
             else:
                 s.append(("conv", f"{p}.conv1"))
             s += [("bn", f"{p}.bn1"), ("conv", f"{p}.conv2"), ("bn", f"{p}.bn2")]
+    return s
+
+
+def schedule(model):
+    """[(kind, module name, module)] in the order DeepLabV3MI355X._forward_native calls its nodes (the bf16 route)"""
+    s = encoder_schedule(model)
+    s.insert(1, ("stem", "encoder.bn1"))
     for i in range(4):
         s += [("conv", f"decoder.0.convs.{i}.0"), ("bn", f"decoder.0.convs.{i}.1")]
     s += [("aspp", "decoder.0.convs.4"), ("conv", "decoder.0.project.0"), ("bn", "decoder.0.project.1"), ("conv", "decoder.1"),
@@ -241,49 +335,91 @@ def _norm_of(kind, module):
     return module[2] if kind == "aspp" else None
 
 
+class Description:
+    """What the Recorder needs to know about one of the three ResNet-encoder models.  This one is DeepLabV3's; tests/customunet_nodes.py
+    and tests/deeplabv3plus_nodes.py derive theirs: the schedule, the names their module binds (``install``) and their extra node kinds
+    (``kinds`` / ``grad_slots`` / ``diff_inputs`` / ``norm_of`` / ``params`` / ``check_owner``)."""
+
+    label = "DeepLabV3MI355X"
+    kinds, grad_slots, diff_inputs = KINDS, GRAD_SLOTS, DIFF_INPUTS
+
+    def schedule(self, model):
+        return schedule(model)
+
+    def counts(self, model):
+        return {k: sum(e[0] == k for e in self.schedule(model)) for k in self.kinds}
+
+    def norm_of(self, kind, module):
+        return _norm_of(kind, module)
+
+    def params(self, node):
+        if node.kind in ("bn", "stem"):
+            return {"gamma": node.module.weight, "beta": node.module.bias}
+        if node.kind == "aspp":
+            return {"w": node.module[1].weight, "gamma": node.module[2].weight, "beta": node.module[2].bias}
+        if node.kind == "up":
+            return {}
+        ps = {"w": node.module.weight}
+        if node.module.bias is not None:
+            ps["b"] = node.module.bias
+        return ps
+
+    def check_owner(self, kind, name, owner, module):
+        """the call's weight / module argument is the scheduled module's"""
+        if kind in ("patch", "conv"):
+            assert param_of(owner) is module.weight, f"{name}: the call's weight is not the model's {name}.weight"
+        elif kind != "up":      # (the up-sampling has no module argument: its place in the schedule identifies it)
+            assert owner is module, f"{name}: the call's module is not the model's {name}"
+
+    def install(self, rec):
+        """patch the names this model's module reaches its nodes through (ops_gemm's two are the Recorder's own) and wrap the
+        ``backward`` of their Functions"""
+        from py4cast_amd import deeplabv3 as D
+
+        rec.patch(D.DeepLabV3MI355X, "_patch", staticmethod(rec.wrap_patch(D.DeepLabV3MI355X._patch)))
+        rec.patch(D, "stem_tail", rec.wrap_stem(D.stem_tail))
+        rec.patch(D, "aspp_assemble", rec.wrap_aspp(D.aspp_assemble))
+        rec.patch(D, "upsample_bilinear_ac", rec.wrap_up(D.upsample_bilinear_ac))
+        for fn_cls in (D._StemTail, D._AsppAssemble, D._UpsampleAC):
+            rec.wrap_backward(fn_cls)
+
+
 class Node:
     """one recorded call: kind, name, module (the live module), pre / post (deep copies of its batch norm before / right after the call),
     args (input clones), src (input name -> (node index, output index) of the recorded output it is), out (output clones), gout (the
     gradients the outputs received), gin (the Function's backward results), opts (the call's options), saved (tensors the node's ctx
     saved that a reference reads: the stem's routing table)"""
 
-    def __init__(self, kind, name, module, args, opts):
+    def __init__(self, kind, name, module, args, opts, desc=None):
         self.kind, self.name, self.module, self.args, self.opts = kind, name, module, args, opts
-        bn = _norm_of(kind, module)
+        self.desc = desc or Description()
+        bn = self.desc.norm_of(kind, module)
         self.pre = copy.deepcopy(bn) if bn is not None else None
         self.post = None
         self.src, self.out, self.gout, self.gin, self.saved = {}, None, None, None, {}
 
     @property
     def norm(self):
-        return _norm_of(self.kind, self.module)
+        return self.desc.norm_of(self.kind, self.module)
 
     def grad(self, slot):
         """the gradient this node's backward returned for input `slot`"""
-        return self.gin[GRAD_SLOTS[self.kind][slot]]
+        return self.gin[self.desc.grad_slots[self.kind][slot]]
 
     def params(self):
         """{slot: leaf parameter} of this node"""
-        if self.kind in ("bn", "stem"):
-            return {"gamma": self.module.weight, "beta": self.module.bias}
-        if self.kind == "aspp":
-            return {"w": self.module[1].weight, "gamma": self.module[2].weight, "beta": self.module[2].bias}
-        if self.kind == "up":
-            return {}
-        ps = {"w": self.module.weight}
-        if self.module.bias is not None:
-            ps["b"] = self.module.bias
-        return ps
+        return self.desc.params(self)
 
 
 class Recorder:
     """``with Recorder(model) as rec: y = model(x); y.backward(dy)`` -- rec.nodes in call order; the schedule is checked call by call
-    and the node counts are asserted on exit"""
+    and the node counts are asserted on exit.  ``desc``: the model's Description (default: DeepLabV3's)."""
 
-    def __init__(self, model):
+    def __init__(self, model, desc=None):
         assert model.native, "the recorder follows the bf16 route (the fp32 flavour runs on library operations)"
         self.model = model
-        self.expected = schedule(model)
+        self.desc = desc or Description()
+        self.expected = self.desc.schedule(model)
         self.nodes = []
         self._ctx = {}
         self._keep = []
@@ -298,14 +434,11 @@ class Recorder:
     # -------------------------------------------------------------- forward side
     def _begin(self, kind, owner, args, opts):
         i = len(self.nodes)
-        assert i < len(self.expected), f"node {i} ({kind}): more node calls than DeepLabV3MI355X makes ({len(self.expected)})"
+        assert i < len(self.expected), f"node {i} ({kind}): more node calls than {self.desc.label} makes ({len(self.expected)})"
         ekind, name, module = self.expected[i]
         assert kind == ekind, f"node {i}: expected {ekind} {name}, got a {kind} call"
-        if kind in ("patch", "conv"):
-            assert param_of(owner) is module.weight, f"{name}: the call's weight is not the model's {name}.weight"
-        elif kind != "up":      # (the up-sampling has no module argument: its place in the schedule identifies it)
-            assert owner is module, f"{name}: the call's module is not the model's {name}"
-        node = Node(kind, name, module, {k: _clone(v) for k, v in args.items()}, opts)
+        self.desc.check_owner(kind, name, owner, module)
+        node = Node(kind, name, module, {k: _clone(v) for k, v in args.items()}, opts, self.desc)
         for k, v in args.items():
             if isinstance(v, torch.Tensor) and _key(v) in self._made:
                 node.src[k] = self._made[_key(v)]
@@ -324,7 +457,10 @@ class Recorder:
             self._ctx[id(ctx)] = node
             self._keep.append(ctx)
 
-    def _wrap_backward(self, fn_cls):
+    def patch(self, owner, name, value):
+        self._mp.setattr(owner, name, value)
+
+    def wrap_backward(self, fn_cls):
         orig = fn_cls.__dict__["backward"].__func__
         rec = self
 
@@ -339,17 +475,12 @@ class Recorder:
 
         self._mp.setattr(fn_cls, "backward", staticmethod(backward))
 
-    def __enter__(self):
-        from py4cast_amd import deeplabv3 as D
-        from py4cast_amd import ops_gemm as G
-        from py4cast_amd import ops_patch as P
-
+    # -------------------------------------------------------------- the wrappers of the entry points the three models share
+    def wrap_conv(self, conv0):
         rec = self
-        conv0, bn0, patch0 = G.conv2d_nhwc, G.batch_norm_act, D.DeepLabV3MI355X._patch
-        stem0, aspp0, up0 = D.stem_tail, D.aspp_assemble, D.upsample_bilinear_ac
 
         def conv2d_nhwc(x, w, b=None, res=None, want_stats=False, passthrough=False, dilation=1):
-            assert res is None, "DeepLabV3's convolutions take no residual operand (the residual goes to the batch norm)"
+            assert res is None, f"{rec.desc.label}'s convolutions take no residual operand (the residual goes to the batch norm)"
             node = rec._begin("conv", w, {"x": x, "w": w, "b": b},
                               {"want_stats": bool(want_stats), "passthrough": bool(passthrough), "dilation": int(dilation)})
             out = conv0(x, w, b, want_stats=want_stats, passthrough=passthrough, dilation=dilation)
@@ -360,12 +491,22 @@ class Recorder:
             rec._end(node, [y, st, xp], y.grad_fn)
             return out
 
+        return conv2d_nhwc
+
+    def wrap_bn(self, bn0):
+        rec = self
+
         def batch_norm_act(y, stats, bn, slope=1.0, res=None, res_passthrough=False, mul=None, mul_factor=1.0):
-            assert not res_passthrough, "DeepLabV3's batch norms pass no residual on"
+            assert not res_passthrough, f"{rec.desc.label}'s batch norms pass no residual on"
             node = rec._begin("bn", bn, {"y": y, "stats": stats, "res": res, "mul": mul}, {"slope": float(slope), "mul_factor": float(mul_factor)})
             out = bn0(y, stats, bn, slope=slope, res=res, mul=mul, mul_factor=mul_factor)
             rec._end(node, [out], out.grad_fn)
             return out
+
+        return batch_norm_act
+
+    def wrap_patch(self, patch0):
+        rec = self
 
         def _patch(conv, x):
             k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
@@ -376,6 +517,11 @@ class Recorder:
             rec._end(node, [y, st], y.grad_fn)
             return y, st
 
+        return _patch
+
+    def wrap_stem(self, stem0):
+        rec = self
+
         def stem_tail(y, stats, bn):
             node = rec._begin("stem", bn, {"y": y, "stats": stats}, {})
             pool = stem0(y, stats, bn)
@@ -383,11 +529,21 @@ class Recorder:
             rec._end(node, [pool], pool.grad_fn)
             return pool
 
+        return stem_tail
+
+    def wrap_aspp(self, aspp0):
+        rec = self
+
         def aspp_assemble(x, branches, pool_branch):
             node = rec._begin("aspp", pool_branch, {"x": x, **{f"a{k}": t for k, t in enumerate(branches)}, "w": pool_branch[1].weight}, {})
             buf = aspp0(x, branches, pool_branch)
             rec._end(node, [buf], buf.grad_fn)
             return buf
+
+        return aspp_assemble
+
+    def wrap_up(self, up0):
+        rec = self
 
         def upsample_bilinear_ac(x, scale):
             node = rec._begin("up", None, {"x": x}, {"scale": int(scale)})
@@ -395,22 +551,104 @@ class Recorder:
             rec._end(node, [out], out.grad_fn)
             return out
 
+        return upsample_bilinear_ac
+
+    def __enter__(self):
+        from py4cast_amd import ops_gemm as G
+        from py4cast_amd import ops_patch as P
+
         self._mp = pytest.MonkeyPatch()
-        self._mp.setattr(G, "conv2d_nhwc", conv2d_nhwc)
-        self._mp.setattr(G, "batch_norm_act", batch_norm_act)
-        self._mp.setattr(D.DeepLabV3MI355X, "_patch", staticmethod(_patch))
-        self._mp.setattr(D, "stem_tail", stem_tail)
-        self._mp.setattr(D, "aspp_assemble", aspp_assemble)
-        self._mp.setattr(D, "upsample_bilinear_ac", upsample_bilinear_ac)
-        for fn_cls in (G._Conv, G._BatchNormAct, P._PatchConv, D._StemTail, D._AsppAssemble, D._UpsampleAC):
-            self._wrap_backward(fn_cls)
+        # (every model reaches these two as G.<name>: one patch covers the three)
+        self._mp.setattr(G, "conv2d_nhwc", self.wrap_conv(G.conv2d_nhwc))
+        self._mp.setattr(G, "batch_norm_act", self.wrap_bn(G.batch_norm_act))
+        for fn_cls in (G._Conv, G._BatchNormAct, P._PatchConv):
+            self.wrap_backward(fn_cls)
+        self.desc.install(self)
         return self
 
     def __exit__(self, exc_type, exc, tb):
         self._mp.undo()
         self._keep = []
         if exc_type is None:
-            want = counts(self.model)
-            got = {k: sum(n.kind == k for n in self.nodes) for k in KINDS}
-            assert got == want, f"DeepLabV3 node calls {got}, expected {want}: a model change routes around the recorded entry points"
+            want = self.desc.counts(self.model)
+            got = {k: sum(n.kind == k for n in self.nodes) for k in self.desc.kinds}
+            assert got == want, f"{self.desc.label} node calls {got}, expected {want}: a model change routes around the recorded entry points"
         return False
+
+
+# ------------------------------------------------------------------------------------------------ composing the references (CPU tests)
+class Composer:
+    """the bookkeeping of a hand composition of the node references into a float64 restatement `ref` (its train / eval mode): parameter
+    gradients by name (``put``; several contributions add), each batch norm's node result by module name (``bna``), and the four ResNet
+    layers forward and backward -- what tests/test_customunet_nodes_cpu.py and tests/test_deeplabv3plus_nodes_cpu.py share"""
+
+    def __init__(self, ref):
+        self.names = {id(p): n for n, p in ref.named_parameters()}
+        self.mods = {id(m): n for n, m in ref.named_modules()}
+        self.grads, self.norms, self.train = {}, {}, ref.training
+
+    def put(self, p, g):
+        n = self.names[id(p)]
+        self.grads[n] = g if n not in self.grads else self.grads[n] + g
+
+    def running(self, bn):
+        return None if self.train else (bn.running_mean, bn.running_var)
+
+    def bna(self, y, bn, slope=0.0, **kw):
+        r = bn_act(y, bn.weight, bn.bias, bn.eps, slope=slope, running=self.running(bn), **kw)
+        self.norms[self.mods[id(bn)]] = r
+        return r
+
+    def blocks_forward(self, enc, geom, h):
+        """the BasicBlocks of layer1 .. layer4 (geom: (stride, dilation) per layer) on h: (per-block records, each layer's output)"""
+        blocks, feats = [], []
+        for li, (s, d) in enumerate(geom):
+            layer = getattr(enc, f"layer{li + 1}")
+            for j, blk in enumerate(layer):
+                st = s if j == 0 else 1
+                rec = {"x": h, "blk": blk, "st": st, "d": d, "layer": li, "last": j == len(layer) - 1}
+                rec["c1"] = conv_node(h, blk.conv1.weight, stride=st, pad=d, dilation=d, round_weight=False)
+                if hasattr(blk, "downsample"):
+                    rec["cd"] = conv_node(h, blk.downsample[0].weight, stride=st, round_weight=False)
+                    rec["bd"] = self.bna(rec["cd"], blk.downsample[1], slope=1.0)
+                    idn = rec["bd"].out
+                else:
+                    idn = h
+                rec["idn"] = idn
+                rec["b1"] = self.bna(rec["c1"], blk.bn1)
+                rec["c2"] = conv_node(rec["b1"].out, blk.conv2.weight, pad=d, dilation=d, round_weight=False)
+                rec["b2"] = self.bna(rec["c2"], blk.bn2, res=idn)
+                h = rec["b2"].out
+                blocks.append(rec)
+            feats.append(h)
+        return blocks, feats
+
+    def blocks_backward(self, blocks, dh, extra):
+        """the blocks in reverse from dh, the gradient of layer4's output; extra {layer index: the gradient that layer's output receives
+        from its consumers outside the encoder (the decoder's skips), added to the next layer's as autograd adds them}: the gradient
+        of the stem's pooled map"""
+        put = self.put
+        for rec in reversed(blocks):
+            blk, st, d = rec["blk"], rec["st"], rec["d"]
+            if rec["last"] and rec["layer"] in extra:
+                dh = dh + extra[rec["layer"]]
+            b2 = self.bna(rec["c2"], blk.bn2, res=rec["idn"], mask=rec["b2"].mask, dout=dh)
+            put(blk.bn2.weight, b2.dgamma)
+            put(blk.bn2.bias, b2.dbeta)
+            _, db1, dw, _ = conv_node(rec["b1"].out, blk.conv2.weight, pad=d, dilation=d, dy=b2.dy, round_weight=False)
+            put(blk.conv2.weight, dw)
+            b1 = self.bna(rec["c1"], blk.bn1, mask=rec["b1"].mask, dout=db1)
+            put(blk.bn1.weight, b1.dgamma)
+            put(blk.bn1.bias, b1.dbeta)
+            _, dx1, dw, _ = conv_node(rec["x"], blk.conv1.weight, stride=st, pad=d, dilation=d, dy=b1.dy, round_weight=False)
+            put(blk.conv1.weight, dw)
+            if "cd" in rec:
+                bd = self.bna(rec["cd"], blk.downsample[1], slope=1.0, dout=b2.dres)
+                put(blk.downsample[1].weight, bd.dgamma)
+                put(blk.downsample[1].bias, bd.dbeta)
+                _, dxd, dw, _ = conv_node(rec["x"], blk.downsample[0].weight, stride=st, dy=bd.dy, round_weight=False)
+                put(blk.downsample[0].weight, dw)
+                dh = dx1 + dxd                 # the block input's two consumers
+            else:
+                dh = dx1 + b2.dres             # the identity edge (conv1's passthrough on the device)
+        return dh

@@ -71,11 +71,15 @@ def test_up2cat_against_torch(gpu_device, B, h, w, Cx, Cs):
     _check_dx(xg.grad, dout, Cx)
 
 
-def test_up2cat_without_skip(gpu_device):
+@pytest.mark.parametrize("B,h,w,Cx", [(2, 32, 48, 32), (2, 256, 256, 32)])
+def test_up2cat_without_skip(gpu_device, B, h, w, Cx):
+    """(2, 256, 256, 32): decoder block 4 of the 512 x 512 bench step -- 524288 octets, a grid exactly at the cap of 2048 workgroups
+    with a full last workgroup and no second trip"""
     from py4cast_amd.customunet import up2_cat
 
     dev = gpu_device
-    B, h, w, Cx = 2, 32, 48, 32
+    if h == 256:
+        assert B * h * w * (Cx // 8) == 524288 == 2048 * 256
     g = gen(dev, 5)
     x = torch.randn(B, h, w, Cx, device=dev, generator=g).to(torch.bfloat16)
     xg = x.clone().requires_grad_(True)

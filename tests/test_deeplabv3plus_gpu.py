@@ -52,7 +52,8 @@ DW_CASES = [(1, 1, 1, 8, (12, 24, 36)),          # every non-centre tap is outsi
             (2, 14, 13, 512, (12, 24, 36)),      # the stride-16 map of a 224 x 208 input
             (2, 32, 32, 512, (12, 24, 36)),      # the bench map (512 x 512)
             (2, 128, 128, 304, (1,)),            # block2 at 512 x 512: past one trip of the grid-stride loop
-            (2, 9, 7, 8, (1, 2))]                # R = 2, small dilations
+            (2, 9, 7, 8, (1, 2)),                # R = 2, small dilations
+            (1, 5, 6, 520, (1, 2))]              # 65 octets: dw_wgrad's second channel block (gridDim.y = 2), one active lane in it
 
 
 def _dw_operands(dev, B, H, W, C, rates):
@@ -74,6 +75,8 @@ def test_depthwise_dilated_against_float64(gpu_device, B, H, W, C, rates):
     dev = gpu_device
     if (H, C) == (128, 304):
         assert B * H * W * (C // 8) == 1245184 > GRID_CAP_OCTETS
+    if C == 520:    # the weight gradient's grid is (pixel chunks, ceil(octets / 64), R): every other case and every network has C <= 512
+        assert (C // 8 + 63) // 64 == 2 and C // 8 - 64 == 1
     x, ws, dys = _dw_operands(dev, B, H, W, C, rates)
     xg = x.clone().requires_grad_(True)
     wg = [w.clone().requires_grad_(True) for w in ws]
