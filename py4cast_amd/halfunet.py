@@ -56,6 +56,28 @@ def pad32(c: int) -> int:
     return (c + 31) // 32 * 32
 
 
+def _upsample_axis(a: torch.Tensor, s: int, dim: int) -> torch.Tensor:
+    """One axis of `upsample_bilinear`: entry s i + r reads a[i - 1], a[i], a[i + 1] (clamped at the ends) with the weights of phase r,
+    f = (r + 0.5) / s - 0.5: (-f, 1 + f, 0) below the sample's centre, (0, 1 - f, f) above it."""
+    n = a.shape[dim]
+    prev = torch.cat([a.narrow(dim, 0, 1), a.narrow(dim, 0, n - 1)], dim)
+    nxt = torch.cat([a.narrow(dim, 1, n - 1), a.narrow(dim, n - 1, 1)], dim)
+    f = (torch.arange(s, device=a.device, dtype=a.dtype) + 0.5) / s - 0.5
+    shape = [1] * (a.dim() + 1)
+    shape[dim + 1] = s
+    wl, wr = (-f).clamp_min(0).view(shape), f.clamp_min(0).view(shape)
+    out = wl * prev.unsqueeze(dim + 1) + (1 - wl - wr) * a.unsqueeze(dim + 1) + wr * nxt.unsqueeze(dim + 1)
+    return out.flatten(dim, dim + 1)
+
+
+def upsample_bilinear(a: torch.Tensor, s: int) -> torch.Tensor:
+    """F.interpolate(scale_factor=s, mode="bilinear", align_corners=False) of a features-last (B,h,w,C) tensor for an integer s, written
+    as slices, products and sums.  The library's backward of that operator adds into the coarse map with atomics, in an order that
+    changes from run to run: on bf16 maps the rounding noise now and then moved one element of the coarsest level's gradient, and two
+    training steps from one state differed in that level's norm gradients.  Every operator here has a fixed-order backward."""
+    return _upsample_axis(_upsample_axis(a, s, 1), s, 2)
+
+
 class _Holder(nn.Module):
     """Parameter/buffer container giving mfai's dotted names."""
 
@@ -208,7 +230,7 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         Convolutions without dilation to <= 64 channels from <= 96 run on the MFMA conv kernels (ops_model.conv_nhwc: forward, data
         and weight gradient; fewer than 64 output channels as zero rows of a 64-channel launch), the Ghost "cheap operation" at 64
         filters on csrc/depthwise.hip (ops_ghost.ghost_dw); wider or dilated convolutions go through the library; normalisation,
-        pooling and up-sampling are torch ops on the features-last tensors (`_forward_modules`; Ghost blocks with the yaml's other
+        pooling and up-sampling (`upsample_bilinear`: a fixed-order backward) are torch ops on the features-last tensors (`_forward_modules`; Ghost blocks with the yaml's other
         values in bf16 take `_forward_ghost_native` on the same module tree instead: `ghost_native`).  The fused C++ plan (p4c_halfunet_forward) serves the
         yaml's network only, so the rollout takes the generic per-step path here."""
         nf = settings.num_filters
@@ -322,8 +344,7 @@ class HalfUNetMI355X(ModelABC, nn.Module):
             levels.append(h)
         s = levels[0].float()
         for k in range(1, 5):
-            up = F.interpolate(levels[k].permute(0, 3, 1, 2).float(), scale_factor=2**k, mode="bilinear", align_corners=False)
-            s = s + up.permute(0, 2, 3, 1)
+            s = s + upsample_bilinear(levels[k].float(), 2**k)
         d = block("decoder", self.decoder, s.to(self.act_dtype))
         y = self._conv_module(self.outconv, d)
         if not isinstance(self.activation, nn.Identity):
