@@ -513,8 +513,8 @@ __device__ __forceinline__ void flush_stats(float (&s1)[2][16], float (&s2)[2][1
 // waves of each SIMD run a matrix-heavy and a memory-heavy stream side by side.  One LDS-only barrier per tile.
 //   iteration i:  compute waves: MFMA(buf[i&1]) ; epilogue(i)
 //                 loader waves : write regs(tile i+1) -> buf[~i&1] ; issue loads(tile i+2)
-// Channel statistics are accumulated in registers over all tiles of a sample and flushed once per
-// (sample, wave): stat_partial[b][G*4][2][64], zero-filled by the launcher.
+// Channel statistics are taken of the values as stored (rounded to T), accumulated in registers over all tiles
+// of a sample and flushed once per (sample, wave): stat_partial[b][G*4][2][64], zero-filled by the launcher.
 template <typename T, int CI, int KS>
 __global__ void __launch_bounds__(512, 2)
     conv_fwd_bf16_ws_kernel(const T* __restrict__ in, const __bf16* __restrict__ wp, const float* __restrict__ in_scale,
@@ -726,7 +726,10 @@ __global__ void __launch_bounds__(512, 2)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x16& a = ct == 0 ? acc0 : acc1;
-                const f32x4 v = {a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]};
+                f32x4 v = {a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]};
+                if (std::is_same<T, __bf16>::value) {   // statistics of what is stored, as every other epilogue takes them
+                    v.x = (float)(__bf16)v.x; v.y = (float)(__bf16)v.y; v.z = (float)(__bf16)v.z; v.w = (float)(__bf16)v.w;
+                }
                 if (valid && (!(P4C_EXP & 4) || v.x == 123.456f)) store4(orow + ct * 32 + 8 * g, v);
                 if (stat_partial && !(P4C_EXP & 8)) {
 #pragma unroll

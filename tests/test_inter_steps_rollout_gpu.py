@@ -5,6 +5,7 @@ The native rollout beyond one model call per target step and beyond training (Ha
   * phase "inference": a forward-only forecast of free steps without border forcing.
 Checked against the generic per-op path on the same kernels (``lm.use_native_rollout = False``), with the bars of
 tests/test_wide_rollout_gpu.py; the launches of each route are counted by wrapping ``_lib.call``.
+The float64 check of these schedules, call by call, is tests/test_rollout_nodes_gpu.py.
 """
 import collections
 

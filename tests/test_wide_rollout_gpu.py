@@ -2,6 +2,7 @@
 The one-node native rollout with num_input_steps = T_in >= 2 (HalfUNetMI355X.native_rollout): step i's input is the window of
 states i .. i+T_in-1 of a (T_in + T)-slot buffer, and the reverse sweep sums each state's gradient in HIP (p4c_sum_state_grads).
 Checked against the generic per-op autograd path on the same kernels, as tests/test_model_gpu.py does for T_in = 1.
+The float64 check of this rollout, call by call and past the wrap of the gradient ring, is tests/test_rollout_nodes_gpu.py.
 """
 import pytest
 import torch
