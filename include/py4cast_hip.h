@@ -464,6 +464,46 @@ int p4c_ar_update_next_bwd(const float* g_next, int64_t g_next_bs, const void* g
                            const float* std, const float* interior_mask, int force_border, void* dy, int dy_dtype, int y_cs,
                            float* dprev, int64_t dprev_bs, int B, int64_t N, int F, float keep_prev, p4c_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The AR step on an AUTO-PADDED grid (csrc/rollout_win.hip; mfai's AutoPaddingModel: pad -> network -> crop as addressing).
+ * The network side (x, y, dy, g_next2 = the plan's dx) is (B, Hp, Wp, channels); the state side (prev, statics, forcing, target,
+ * masks, new_state, g_next, dprev) stays dense at N = H * W grid points.  State pixel (h, w) is network row
+ * (top + h) * Wp + left + w.  Every entry point takes the window (H, W, Hp, Wp, top, left) ahead of the stream and returns
+ * P4C_ERR_INVALID for one that does not fit (H * W != N, top + H > Hp, left + W > Wp, negative offsets).  Nothing is copied, padded
+ * or cropped; the element arithmetic is that of the entry points they mirror, bit for bit.  F <= 64.
+ *
+ * p4c_build_x_win: p4c_build_x for ONE input state (T_in must be 1, downscaling_only 0; prev_ts is ignored).  Writes EVERY element
+ *   of x (B, Hp, Wp, c_pad): inside the window the row p4c_build_x writes (state | statics | forcing | NaN-mask channel | zeros),
+ *   +0.0 in every channel outside.  No memset is needed ahead of it.
+ * p4c_ar_update_loss_fwd_win: p4c_ar_update_loss_fwd with y (B, Hp, Wp, y_cs) read through the window; same new state as that entry
+ *   point fed the cropped rows; the loss column uses p4c_loss_workspace_bytes(B, 1, N, 1) and the same final kernel.
+ * p4c_ar_update_next_win: the free step (p4c_ar_update_next without a next input), y read through the window.
+ * p4c_ar_update_loss_bwd_win: p4c_ar_update_loss_bwd with g_next2 (B, Hp, Wp, g2_cs) read through the window and dy
+ *   (B, Hp, Wp, y_cs) written in EVERY element: +0.0 outside the window and in channels >= F.  dprev / g_next stay dense (B, N, F).
+ *   A lane owns 4 channels of a dy / g_next2 row at any F: y_cs and g2_cs must be multiples of 4 and both bases 16-byte aligned
+ *   (P4C_ERR_UNSUPPORTED otherwise; the network's rows have 64 channels).
+ */
+int p4c_build_x_win(const float* prev, int64_t prev_bs, int64_t prev_ts, const float* statics, int64_t statics_bs,
+                    const float* forcing, int64_t forcing_bs, void* x, int x_dtype, int c_pad, int B, int T_in, int64_t N, int F,
+                    int Fs, int Ff, int mask_on_nan, int downscaling_only, int H, int W, int Hp, int Wp, int top, int left,
+                    p4c_stream_t stream);
+int p4c_ar_update_loss_fwd_win(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs, const float* target,
+                               int64_t tgt_bs, const float* std, const float* mean, const float* border_mask,
+                               const float* interior_mask, float* new_state, int64_t new_bs, const float* weights,
+                               float num_interior, const int32_t* masked_count, int kind, int mask_mode, float* loss_out,
+                               int64_t loss_stride, void* workspace, int B, int64_t N, int F, float keep_prev, int H, int W, int Hp,
+                               int Wp, int top, int left, p4c_stream_t stream);
+int p4c_ar_update_next_win(const float* prev, int64_t prev_bs, const void* y, int y_dtype, int y_cs, const float* target,
+                           int64_t tgt_bs, const float* std, const float* mean, const float* border_mask,
+                           const float* interior_mask, float* new_state, int64_t new_bs, int nan_to_num, int B, int64_t N, int F,
+                           float keep_prev, int H, int W, int Hp, int Wp, int top, int left, p4c_stream_t stream);
+int p4c_ar_update_loss_bwd_win(const float* g_next, int64_t g_next_bs, const void* g_next2, int g2_dtype, int g2_cs,
+                               const float* gloss, int64_t gloss_stride, const float* new_state, int64_t new_bs,
+                               const float* target, int64_t tgt_bs, const float* std, const float* interior_mask,
+                               int force_border, const float* weights, float num_interior, const int32_t* masked_count, int kind,
+                               int mask_mode, void* dy, int dy_dtype, int y_cs, float* dprev, int64_t dprev_bs, int B, int64_t N,
+                               int F, float keep_prev, int H, int W, int Hp, int Wp, int top, int left, p4c_stream_t stream);
+
 /* ====================================================================================
  * Model kernels -- the network arithmetic the reference obtains from mfai v5.0.1
  * (py4cast/models.py:10-20; model forward at py4cast/lightning.py:591-596) and, underneath,

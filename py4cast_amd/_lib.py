@@ -21,6 +21,7 @@ PROF_CONV3X3_C64, PROF_WGRAD3X3_C64, PROF_CONV3X3_C64_BWD = 1, 2, 4
 LOSS_MSE, LOSS_L1 = 0, 1
 MASK_NONE, MASK_FROM_NAN, MASK_F32, MASK_U8 = 0, 1, 2, 3
 EVAL_MAP_NONE = -1
+OK, ERR_INVALID, ERR_LAUNCH, ERR_RUNTIME, ERR_UNSUPPORTED = 0, -1, -2, -3, -4   # the return codes of every entry point
 
 P = c_void_p
 I = c_int
@@ -80,6 +81,12 @@ SIGNATURES = {
     "p4c_out_conv_update_fwd": [P, P, P, P, I, P, L, P, L, P, P, P, P, P, L, I, L, I, F, P, I, P, L, I, P, L, I, P],
     # g_next, g_next_bs, g_next2, g2_dtype, g2_cs, std, interior, force_border, dy, dy_dtype, y_cs, dprev, dprev_bs, B, N, F, keep_prev, stream
     "p4c_ar_update_next_bwd": [P, L, P, I, I, P, P, I, P, I, I, P, L, I, L, I, F, P],
+    # the AR step on an auto-padded grid (csrc/rollout_win.hip): the arguments of p4c_build_x / p4c_ar_update_loss_fwd / p4c_ar_update_next
+    # (without a next input) / p4c_ar_update_loss_bwd, then the window H, W, Hp, Wp, top, left, then the stream
+    "p4c_build_x_win": [P, L, L, P, L, P, L, P, I, I, I, I, L, I, I, I, I, I, I, I, I, I, I, I, P],
+    "p4c_ar_update_loss_fwd_win": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, I, I, I, I, I, I, P],
+    "p4c_ar_update_next_win": [P, L, P, I, I, P, L, P, P, P, P, P, L, I, I, L, I, F, I, I, I, I, I, I, P],
+    "p4c_ar_update_loss_bwd_win": [P, L, P, I, I, P, L, P, L, P, L, P, P, I, P, F, P, I, I, P, I, I, P, L, I, L, I, F, I, I, I, I, I, I, P],
 }
 OTHER = {
     "p4c_version": ([], c_int),

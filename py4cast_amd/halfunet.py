@@ -168,7 +168,9 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         self.act_dtype = torch.float32 if act == "f32" else torch.bfloat16  # dtype of x / y / dy / dx handed to the plan
         self.timed_entry_points = ("p4c_halfunet_forward", "p4c_halfunet_backward", "p4c_build_x",
                                    "p4c_ar_update_loss_fwd", "p4c_ar_update_loss_fwd_next", "p4c_ar_update_loss_bwd",
-                                   "p4c_sum_state_grads", "p4c_ar_update_next", "p4c_out_conv_update_fwd", "p4c_ar_update_next_bwd")
+                                   "p4c_sum_state_grads", "p4c_ar_update_next", "p4c_out_conv_update_fwd", "p4c_ar_update_next_bwd",
+                                   "p4c_build_x_win", "p4c_ar_update_loss_fwd_win", "p4c_ar_update_next_win",
+                                   "p4c_ar_update_loss_bwd_win")
 
         self.use_ghost = bool(settings.use_ghost)
         # Ghost blocks with the yaml's other values in bf16: the per-layer nodes below run on the package's own kernels
@@ -565,9 +567,12 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         (the caller then takes the generic per-op path).
         ``num_inter_steps`` = K >= 2 (scaled_ar): K model calls per target step; the first K - 1 are FREE steps (border forced to the
         target, no loss, state kept in scratch: p4c_ar_update_next / p4c_out_conv_update_fwd), the K-th is the loss step above.
+        Auto-padded grids (``autopad_enabled``, a grid that is not a multiple of 16 each way) with one input state and
+        ``num_inter_steps`` = 1 run natively too: the network side on the padded grid, the state side untouched at H x W, connected by
+        the window kernels of csrc/rollout_win.hip (``halfunet_rollout.padded_grid_is_native``); other padded configurations return None.
         ``phase == "inference"``: a forward-only forecast of free steps without border forcing (``_native_forecast``), a plain tensor.
         """
-        from .halfunet_rollout import _NativeRolloutFn
+        from .halfunet_rollout import _NativeRolloutFn, padded_grid_is_native
         from .losses import WeightedLoss
 
         if batch.inputs.tensor.dim() != 5:
@@ -575,11 +580,14 @@ class HalfUNetMI355X(ModelABC, nn.Module):
         if phase == "inference":
             return self._native_forecast(lm, batch, std, mean, int(num_inter_steps))
         T_in, F = batch.inputs.tensor.shape[1], batch.inputs.tensor.shape[-1]
-        if T_in > 1 and (T_in * F + lm.grid_static_features.shape[-1] + batch.forcing.tensor.shape[-1] + int(lm.mask_on_nan)
-                         != self.in_channels):
+        channels = T_in * F + lm.grid_static_features.shape[-1] + batch.forcing.tensor.shape[-1] + int(lm.mask_on_nan)
+        if T_in > 1 and channels != self.in_channels:
             return None
-        if any(self.padding_for(batch.inputs.tensor.shape[2], batch.inputs.tensor.shape[3])):
-            return None   # auto-padded grids take the generic per-step path (forward pads and crops around the plan)
+        padding = self.padding_for(batch.inputs.tensor.shape[2], batch.inputs.tensor.shape[3])
+        if any(padding) and not padded_grid_is_native(padding, self._settings.autopad_enabled, T_in, int(num_inter_steps), channels,
+                                                      self.in_channels):
+            # the generic per-step path: forward pads and crops around the plan (or raises, without autopad_enabled)
+            return None
         if num_inter_steps > 1 and T_in > 1:
             return None   # (AutoRegressiveLightning raises for this pair before it gets here)
         members = getattr(lm.loss, "losses", [])

@@ -5,6 +5,13 @@ fused next input) -> HalfUNet plan -> AR step (state update + border forcing, wi
 node (``_NativeRolloutFn``: training / validation, with the matching reverse sweep) or as a forward-only forecast
 (``native_forecast``: phase "inference").
 
+Auto-padded grids (``autopad_enabled``, a grid that is not a multiple of 16; one input state, one model call per target step): the
+NETWORK side -- x, the plan's maps, y, dy, dx -- lives on the padded grid (B, Hp, Wp, ..), the STATE side -- the batch's tensors, the
+masks, the prediction, dprev, g_pred, the loss workspace -- stays at (B, H, W, ..) and is never copied or padded.  ``_Rollout.window``
+= (Hp, Wp, top, left) says so, and the four calls that connect the two sides take the ``_win`` entry points of csrc/rollout_win.hip,
+which address through the window: state pixel (h, w) is network row (top + h) * Wp + left + w.  No fused next input, no fused 1x1
+tail, no saved loss gradients there: p4c_build_x_win runs per model call and the plan writes y.
+
 Every decision exists once: ``_Rollout`` is what a rollout passes around, ``_schedule`` maps a call index to its states, and each
 kind of native call (``_build_x``, ``_model_forward``, ``_free_step``, ``_loss_step``, ``_step_backward``, ``_model_backward``) is the
 only place that names its entry points and lays out their arguments.
@@ -39,6 +46,14 @@ def _step_paths(model, T_in, N, F, Fs, mask_on_nan):
     return feed, v4_next, flat_next
 
 
+def padded_grid_is_native(padding, autopad_enabled, T_in, K, channels, in_channels):
+    """Whether a rollout on a grid the network has to pad (``padding`` = HalfUNetMI355X.padding_for(H, W), not all zero) takes the
+    native route: only with ``autopad_enabled`` (otherwise ``forward`` raises, through the generic route), ONE input state (T_in >= 2
+    needs a windowed p4c_sum_state_grads), ONE model call per target step, and the batch's channel count
+    (T_in * F + statics + forcing + NaN-mask channel) equal to the network's.  A grid that fits is not this function's question."""
+    return bool(any(padding) and autopad_enabled and T_in == 1 and K == 1 and channels == in_channels)
+
+
 def _fused_tail(model, v4_next, flat_next, F, mask_on_nan):
     """bf16 flavour: the network's 1x1 output convolution runs INSIDE the AR step's kernel (p4c_out_conv_update_loss_fwd /
     p4c_out_conv_update_fwd: y is never written and read back, one launch less per AR step; same new state bit for bit;
@@ -53,6 +68,8 @@ class _Rollout:
       model, desc (the plan the backward uses too), desc_fwd (the forward's: skip_out_conv with the fused tail), flat, scratch,
       saved_bytes, B, T, T_in, K, H, W, N, F, Fs, Ff, cpad, inputs, forcing, statics + sbs_statics (batch stride 0 when every
       sample shares them), std, mean, mask_on_nan, adt / acode (activation dtype and its code), stream, training,
+      window (None, or (Hp, Wp, top, left) of an auto-padded grid) with Hn, Wn (the network's grid: Hp, Wp or H, W) and win_args (what
+      the _win entry points take ahead of the stream),
       feed (one input state), fuse_next (the step's kernel writes the next network input), step_capable (one of the step kernels'
       two fast paths applies), fused_tail (the 1x1 output convolution runs inside the step's kernel);
     the callers add what is listed below.  The reverse sweep reads it again; ``release_forward`` drops what only the forward needs."""
@@ -87,7 +104,10 @@ def _rollout_context(model, inputs, forcing, statics, std, mean, T, K, mask_on_n
     st = statics.float()
     sbs = 0 if st.stride(0) == 0 else N * Fs
     st = st[0].contiguous() if sbs == 0 else st.contiguous()
-    desc = model._desc(B, H, W)
+    top, bottom, left, right = model.padding_for(H, W)
+    window = (H + top + bottom, W + left + right, top, left) if (top or bottom or left or right) else None
+    Hn, Wn = window[:2] if window else (H, W)
+    desc = model._desc(B, Hn, Wn)
     if node and T_in > 1:
         desc.dx_channels = T_in * F   # the window of past states: the gradient the sweep reads
     elif node and desc.dx_channels > NF:
@@ -99,12 +119,16 @@ def _rollout_context(model, inputs, forcing, statics, std, mean, T, K, mask_on_n
     # (T_in >= 2: the next input is a window of several states, built by p4c_build_x; the update kernels run without x_next)
     feed, v4_next, flat_next = _step_paths(model, T_in, N, F, Fs, mask_on_nan)
     fused_tail = _fused_tail(model, v4_next, flat_next, F, mask_on_nan)
+    if window:
+        # the step kernels behind the window emit no next input, save no loss gradient and take y from the plan
+        v4_next = flat_next = fused_tail = False
     desc_fwd = desc
     if fused_tail:
         desc_fwd = HalfUNetDesc.from_buffer_copy(desc)
         desc_fwd.skip_out_conv = 1
     return _Rollout(model=model, desc=desc, desc_fwd=desc_fwd, flat=flat, scratch=scratch, saved_bytes=saved_bytes, B=B, T=T, T_in=T_in,
-                    K=K, H=H, W=W, N=N, F=F, Fs=Fs, Ff=Ff, cpad=model.cin_pad, inputs=inputs, forcing=forcing, statics=st,
+                    K=K, H=H, W=W, Hn=Hn, Wn=Wn, window=window, win_args=(H, W, Hn, Wn, top, left), N=N, F=F, Fs=Fs, Ff=Ff,
+                    cpad=model.cin_pad, inputs=inputs, forcing=forcing, statics=st,
                     sbs_statics=sbs, std=std, mean=mean, mask_on_nan=mask_on_nan, adt=model.act_dtype,
                     acode=L.dtype_code(model.act_dtype), stream=L.stream(dev), training=training, feed=feed,
                     fuse_next=feed and (v4_next or flat_next), step_capable=v4_next or flat_next, fused_tail=fused_tail)
@@ -152,13 +176,17 @@ def _schedule(r, c):
 
 
 def _new_x(r):
-    return torch.empty(r.B, r.H, r.W, r.cpad, dtype=r.adt, device=r.inputs.device)
+    return torch.empty(r.B, r.Hn, r.Wn, r.cpad, dtype=r.adt, device=r.inputs.device)
 
 
 def _build_x(r, i, prev, sbs_prev, x):
     win, sbs_win = (prev, sbs_prev) if r.feed else (r.states[:, i], r.sbs_state)
-    L.call("p4c_build_x", L.ptr(win), sbs_win, r.N * r.F, L.ptr(r.statics), r.sbs_statics, L.ptr(r.forcing[:, i]), r.T * r.N * r.Ff,
-           L.ptr(x), r.acode, r.cpad, r.B, r.T_in, r.N, r.F, r.Fs, r.Ff, r.mask_on_nan, 0, r.stream)
+    args = (L.ptr(win), sbs_win, r.N * r.F, L.ptr(r.statics), r.sbs_statics, L.ptr(r.forcing[:, i]), r.T * r.N * r.Ff,
+            L.ptr(x), r.acode, r.cpad, r.B, r.T_in, r.N, r.F, r.Fs, r.Ff, r.mask_on_nan, 0)
+    if r.window:
+        L.call("p4c_build_x_win", *args, *r.win_args, r.stream)   # every element of x: zeros outside the window, no memset
+    else:
+        L.call("p4c_build_x", *args, r.stream)
 
 
 def _model_forward(r, x, saved):
@@ -185,7 +213,10 @@ def _free_step(r, i, saved, prev, sbs_prev, new, sbs_new, x_next, forcing_next):
     force = r.force_border
     update = (L.ptr(r.outputs[:, i] if force else None), r.sbs_out, L.ptr(r.std), L.ptr(r.mean), L.ptr(r.border if force else None),
               L.ptr(r.interior if force else None), L.ptr(new), sbs_new)
-    if r.fused_tail:
+    if r.window:
+        L.call("p4c_ar_update_next_win", L.ptr(prev), sbs_prev, L.ptr(r.y), r.acode, NF, *update, int(r.mask_on_nan), r.B, r.N, r.F, 1.0,
+               *r.win_args, r.stream)
+    elif r.fused_tail:
         L.call("p4c_out_conv_update_fwd", *_tail(r, saved), L.ptr(prev), sbs_prev, *update, r.B, r.N, r.F, 1.0,
                *_next_input(r, x_next, forcing_next), r.stream)
     else:
@@ -205,7 +236,9 @@ def _loss_step(r, i, saved, prev, sbs_prev, new, sbs_new, x_next, forcing_next):
         L.call("p4c_out_conv_update_loss_fwd", *_tail(r, saved), L.ptr(prev), sbs_prev, *update, *loss, *nxt, *lgrad, r.stream)
         return
     step = (L.ptr(prev), sbs_prev, L.ptr(r.y), r.acode, NF, *update, r.mask_mode, *loss)
-    if r.save_lg:
+    if r.window:
+        L.call("p4c_ar_update_loss_fwd_win", *step, *r.win_args, r.stream)
+    elif r.save_lg:
         L.call("p4c_ar_update_loss_fwd_next_saved", *step, *nxt, *lgrad, r.stream)
     elif x_next is not None:
         L.call("p4c_ar_update_loss_fwd_next", *step, *nxt, r.stream)
@@ -246,7 +279,8 @@ def native_forecast(model, lm, batch, std, mean, K):
     free step without border forcing (:627) -- no autograd node, one ``saved`` buffer for all calls, states written straight into
     the (B,T,H,W,F) result (intermediary states of K >= 2 through two scratch buffers).  T comes from the forcing tensor
     (``batch.outputs`` is None).  T_in >= 2: the window buffer of the training rollout with p4c_build_x per call.  Returns None
-    where ``native_rollout`` does (padded grids, channel mismatch)."""
+    where ``native_rollout`` does (channel mismatch; padded grids unless ``padded_grid_is_native``: those run behind the window, with
+    p4c_build_x_win per call and p4c_ar_update_next_win as the free step)."""
     inputs, forcing = batch.inputs.tensor, batch.forcing.tensor
     if forcing.dim() != 5:
         return None
@@ -254,10 +288,11 @@ def native_forecast(model, lm, batch, std, mean, K):
     T = forcing.shape[1]
     statics = lm.grid_static_features[: batch.batch_size]
     mask_on_nan = int(bool(lm.mask_on_nan))
-    if (T_in * F + statics.shape[-1] + forcing.shape[-1] + mask_on_nan != model.in_channels or F > model.out_channels
-            or (K > 1 and T_in > 1)):
+    channels = T_in * F + statics.shape[-1] + forcing.shape[-1] + mask_on_nan
+    if channels != model.in_channels or F > model.out_channels or (K > 1 and T_in > 1):
         return None
-    if any(model.padding_for(H, W)):
+    padding = model.padding_for(H, W)
+    if any(padding) and not padded_grid_is_native(padding, model._settings.autopad_enabled, T_in, K, channels, model.in_channels):
         return None
     L.require_cuda(inputs, forcing)
     dev = inputs.device
@@ -271,7 +306,7 @@ def native_forecast(model, lm, batch, std, mean, K):
         _prepare_weights(r)
         _state_slots(r, window=not r.feed)
         r.inter = [torch.empty(B, H, W, F, dtype=torch.float32, device=dev) for _ in range(min(2, K - 1))]
-        r.y = None if r.fused_tail else torch.empty(B, H, W, NF, dtype=r.adt, device=dev)
+        r.y = None if r.fused_tail else torch.empty(B, r.Hn, r.Wn, NF, dtype=r.adt, device=dev)
         _run_schedule(r, [_new_x(r) for _ in range(2 if r.fuse_next else 1)], keep_saved=False)
         return r.pred if r.feed else r.pred.contiguous()
 
@@ -296,7 +331,7 @@ class _NativeRolloutFn(torch.autograd.Function):
         _state_slots(r, window=True)
         r.loss = torch.empty(B, T, dtype=torch.float32, device=dev)
         r.ws = torch.empty(L.lib().p4c_loss_workspace_bytes(B, 1, N, 1) // 4, dtype=torch.float32, device=dev)
-        r.y = torch.empty(B, H, W, NF, dtype=r.adt, device=dev)
+        r.y = torch.empty(B, r.Hn, r.Wn, NF, dtype=r.adt, device=dev)
         _prepare_weights(r)
         # bf16 flavour, training: the update kernel also saves the loss gradient of every element as bf16 rows and the backward reads
         # those instead of the new state and the target (480 -> 120 bytes per grid point; P4C_SAVE_LOSS_GRAD=0: recompute)
@@ -321,7 +356,7 @@ class _NativeRolloutFn(torch.autograd.Function):
         flat = model._flat_params()
         _, scratch = model._workspaces(desc, dev)
         target = model._flat_grad_target()
-        new = lambda c: torch.empty(r.B, r.H, r.W, c, dtype=r.adt, device=dev)   # noqa: E731
+        new = lambda c: torch.empty(r.B, r.Hn, r.Wn, c, dtype=r.adt, device=dev)   # noqa: E731  (network side: the padded grid)
         # the scratch workspace may have served another call since forward: prepare again (one launch per sweep)
         w = SimpleNamespace(stream=stream, flat=flat, scratch=scratch, target=target,
                             gflat=target if target is not None else torch.zeros_like(flat), dy=new(NF),
@@ -373,10 +408,13 @@ def _step_backward(r, w, i, free, g_next, g_next2, dprev):
         return
     gloss = (L.ptr(w.gl[:, i]) if w.gl is not None else None, r.T)
     loss = (L.ptr(r.std), L.ptr(r.interior), int(r.force_border), L.ptr(r.weights), r.num_interior, L.ptr(r.count), r.kind, r.mask_mode)
-    if r.lgrads is not None:
+    recompute = (L.ptr(r.pred[:, i]), r.sbs_state, L.ptr(r.outputs[:, i]), r.sbs_out)
+    if r.window:   # dx read and dy written through the window: every element of dy, zeros outside
+        L.call("p4c_ar_update_loss_bwd_win", *grads, *gloss, *recompute, *loss, *out[:-1], *r.win_args, w.stream)
+    elif r.lgrads is not None:
         L.call("p4c_ar_update_loss_bwd_saved", *grads, *gloss, L.ptr(r.lgrads[i]), state_sz, *loss, *out)
     else:
-        L.call("p4c_ar_update_loss_bwd", *grads, *gloss, L.ptr(r.pred[:, i]), r.sbs_state, L.ptr(r.outputs[:, i]), r.sbs_out, *loss, *out)
+        L.call("p4c_ar_update_loss_bwd", *grads, *gloss, *recompute, *loss, *out)
 
 
 def _model_backward(r, w, c, dx):
