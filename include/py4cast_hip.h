@@ -356,6 +356,37 @@ int p4c_map_planes(const float* pred, int64_t pred_bs, int64_t pred_ts, const fl
 int p4c_map_render(const float* planes, const float* vrange, const unsigned char* lut, const float* interior,
                    unsigned char* frames, int n, int T, int K, int H, int W, p4c_stream_t stream);
 
+/* Forecast frames of the inference path (predict_step's save_gifs: lightning.py:1162-1188, io/outputs.py:223-240,
+ * utils.py:112-223) on the device, as palette indices; the colour table stays with the caller.
+ *
+ * p4c_forecast_frames: of the NORMALISED prediction (B,T,N,F) features-last, N = H*W (strides as p4c_map_planes takes them),
+ * the samples `samples` (HOST int32, n of them, each 0 .. B-1) and the K features `features` (device int32, each 0 .. F-1: the
+ * caller checks), with `display` (device fp32 (K,4): offset, floor, vmin, vmax per drawn feature):
+ *   frames (n,T,K,H,W) uint8: frame row r holds grid row H-1-r (origin="lower");
+ *   vrange (n,T,K,2) fp32:    the colour range each frame was drawn with.
+ * Per pixel, f = features[k]:  v = pred * std[f] (rounded) + mean[f] (rounded), the two steps of p4c_unnormalize_planes, then
+ * + offset in fp32 unless the offset is 0.  The pixel is bad when v is not finite or v < floor (-inf: no floor).  The range is
+ * (vmin, vmax) as given or, where either is NaN, min / max of the frame's good pixels ((NaN, NaN) without one).  Index: 255 bad;
+ * 0 when vmax == vmin; else x = (v - vmin) / (vmax - vmin): 0 for x < 0, 254 for x >= 1, floor(255 x) between.
+ * auto_range: 0 when no row of `display` holds a NaN range (one launch, `workspace` may be null; a NaN range then draws an all-bad
+ * frame), else 1: block partials in `workspace` (p4c_forecast_frames_workspace_bytes(n,T,N,K)) and a finish launch.  No atomics:
+ * two calls give the same bits.
+ * Errors (nothing is launched): a null pointer, K > p4c_forecast_max_features(), n > p4c_forecast_max_samples(), n*T > 65535,
+ * a sample index outside 0 .. B-1, `frames` not 4-byte aligned, more than 2^31 - 1 pixels.
+ *
+ * p4c_forecast_tile / p4c_forecast_max_blocks: grid points per loop trip of a workgroup / workgroups per launch over all
+ * (sample, lead time) pairs: each pair gets min(tiles, max(1, max_blocks / (n*T))) workgroups, which stride over its tiles.
+ * p4c_forecast_frames_dense(K, F): 1 when the call reads whole points and transposes through LDS, 0 when it gathers the K features. */
+int p4c_forecast_tile(void);
+int p4c_forecast_max_blocks(void);
+int p4c_forecast_max_features(void);
+int p4c_forecast_max_samples(void);
+int p4c_forecast_frames_dense(int K, int F);
+size_t p4c_forecast_frames_workspace_bytes(int n, int T, int64_t N, int K);
+int p4c_forecast_frames(const float* pred, int64_t pred_bs, int64_t pred_ts, const int32_t* samples, const float* std,
+                        const float* mean, const int32_t* features, const float* display, int auto_range, unsigned char* frames,
+                        float* vrange, void* workspace, int B, int n, int T, int H, int W, int F, int K, p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

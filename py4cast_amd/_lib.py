@@ -61,6 +61,8 @@ SIGNATURES = {
     "p4c_map_planes": [P, L, L, P, L, L, P, I, P, P, P, P, P, P, I, I, L, I, I, P],
     # planes, vrange, lut, interior, frames, n, T, K, H, W, stream
     "p4c_map_render": [P, P, P, P, P, I, I, I, I, I, P],
+    # pred, bs, ts, samples (host), std, mean, features, display, auto_range, frames, vrange, ws, B, n, T, H, W, F, K, stream
+    "p4c_forecast_frames": [P, L, L, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],
@@ -102,6 +104,12 @@ OTHER = {
     "p4c_map_gap": ([], c_int),
     "p4c_map_render_pixels": ([], c_int),
     "p4c_map_render_max_blocks": ([], c_int),
+    "p4c_forecast_frames_workspace_bytes": ([I, I, L, I], c_size_t),
+    "p4c_forecast_tile": ([], c_int),
+    "p4c_forecast_max_blocks": ([], c_int),
+    "p4c_forecast_max_features": ([], c_int),
+    "p4c_forecast_max_samples": ([], c_int),
+    "p4c_forecast_frames_dense": ([I, I], c_int),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

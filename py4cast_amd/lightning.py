@@ -345,6 +345,8 @@ class AutoRegressiveLightning(_Base):
     def _record_names(self, batch: ItemBatch, ds: bool):
         """lightning.py:541-558."""
         self.input_feature_names = batch.inputs.feature_names
+        if batch.outputs is None:   # the first batch of a forecast carries no target: what training (or the checkpoint) recorded stays
+            return
         self.output_feature_names = batch.outputs.feature_names
         self.output_dim_names = batch.outputs.names
         self.output_dtype = batch.outputs.tensor.dtype
@@ -798,8 +800,56 @@ class AutoRegressiveLightning(_Base):
         self.test_step_logging(batch, prediction, target_masked, mask)
         return mean_loss
 
+    def _datamodule(self):
+        try:
+            return getattr(self.trainer, "datamodule", None)
+        except (AttributeError, RuntimeError):   # a LightningModule that no trainer holds raises
+            return None
+
+    def forecast_samples(self, batch_idx: int, batch_size: int):
+        """(runtimes, accepted) of the samples of a predicted batch (lightning.py:1140-1149): the runtime is the sample's start date
+        as %Y%m%d%H -- ``sample{index:06d}`` where the module has no ``infer_ds.sample_list`` -- and a sample is accepted when its hour
+        is in ``trainer.datamodule.list_run_hour`` (without a datamodule: always)."""
+        samples = getattr(self.infer_ds, "sample_list", None)
+        datamodule = self._datamodule()
+        hours = getattr(datamodule, "list_run_hour", None)
+        runtimes, accepted = [], []
+        for b in range(batch_size):
+            index = batch_idx * batch_size + b
+            if samples is not None:
+                start = samples[index].timestamps.datetime
+                runtimes.append(start.strftime("%Y%m%d%H"))
+                accepted.append(hours is None or start.hour in hours)
+            else:
+                runtimes.append(f"sample{index:06d}")
+                accepted.append(True)
+        return runtimes, accepted
+
+    def _write_forecast_outputs(self, batch_idx: int, preds: NamedTensor, std: torch.Tensor, mean: torch.Tensor) -> None:
+        """``io_conf`` is set: the GIFs of the accepted samples (lightning.py:1133-1188) through ``outputs.ForecastGifWriter``, kept
+        as ``self.forecast_writer`` -- whoever runs the loop drains it at the end (``Trainer.predict`` does)."""
+        from .outputs import ForecastGifWriter, OutputSavingSettings
+
+        if getattr(self, "_output_settings", None) is None:
+            self._output_settings = OutputSavingSettings.from_json(self.io_conf)   # read once
+        datamodule = self._datamodule()
+        runtimes, accepted = self.forecast_samples(batch_idx, preds.tensor.shape[0])
+        if not any(accepted):
+            return
+        if getattr(datamodule, "save_gribs", getattr(self, "save_gribs", False)) and not getattr(self, "_warned_gribs", False):
+            import warnings
+
+            self._warned_gribs = True
+            warnings.warn("save_gribs: writing GRIB files needs epygram and a template GRIB; none is written")
+        if not getattr(datamodule, "save_gifs", getattr(self, "save_gifs", True)):
+            return
+        if getattr(self, "forecast_writer", None) is None:
+            self.forecast_writer = ForecastGifWriter(self._output_settings, preds.tensor.device)
+        self.forecast_writer.submit(preds, std, mean, runtimes, accepted)
+
     def predict_step(self, batch: ItemBatch, batch_idx: int) -> torch.Tensor:
-        """lightning.py:1118-1188: rollout without border forcing, then un-normalise per feature (:1162-1169).  With an
+        """lightning.py:1118-1188: rollout without border forcing, then un-normalise per feature (:1162-1169).  With ``io_conf`` the
+        accepted samples' forecast GIFs are rendered from the normalised prediction and written (``_write_forecast_outputs``).  With an
         ``output_stager`` attached (py4cast_amd.outputs.OutputStager) the un-normalised prediction also leaves for the host as
         feature-major planes in a pinned buffer -- what the GRIB / GIF writers of io/outputs.py consume -- without blocking;
         ``self.staged_slot`` is the ticket for ``output_stager.wait``."""
@@ -816,6 +866,8 @@ class AutoRegressiveLightning(_Base):
             stager = getattr(self, "output_stager", None)
             if stager is not None:
                 self.staged_slot = stager.submit(preds, std, mean)   # reads the normalised tensor: before the in-place pass below
+            if self.io_conf is not None:
+                self._write_forecast_outputs(batch_idx, preds, std, mean)   # likewise
             t = preds.tensor.contiguous().float()
             preds.tensor = ops.unnormalize(t, std, mean, out=t)  # one kernel, the reference's two rounded steps
         return preds

@@ -6,6 +6,7 @@ HIP stream through the C ABI and wire the matching backward entry point.  They a
 outputs with the PyTorch caching allocator (the library owns no memory).
 """
 
+import ctypes
 import functools
 from typing import Optional, Tuple
 
@@ -713,3 +714,88 @@ def map_render(planes, vrange, lut, interior, H: int, W: int, out: torch.Tensor 
     L.call("p4c_map_render", L.ptr(planes), L.ptr(vrange), L.ptr(lut), L.ptr(interior), L.ptr(frames), n, T, K, H, W,
            L.stream(planes.device), alg_bytes=planes.numel() * 4 + frames.numel())
     return frames
+
+
+# ------------------------------------------------------------------------------------------------ forecast frames
+# launch constants of csrc/forecast_frames.hip (p4c_forecast_tile() etc. report the same)
+FORECAST_TILE = 128            # grid points per loop trip of a workgroup
+FORECAST_MAX_BLOCKS = 1024     # workgroups of one launch, all (sample, lead time) pairs together
+FORECAST_MAX_FEATURES = 256    # K of one call
+FORECAST_MAX_SAMPLES = 256     # n of one call
+FORECAST_BAD = 255             # the palette index of a pixel that is not drawn
+
+
+def _display_row(d) -> tuple:
+    """(offset, floor, vmin, vmax) of one feature as floats: from an object with these attributes (outputs.FeatureDisplay) or a
+    4-tuple; None = no offset / no floor / auto-scaled"""
+    if not isinstance(d, (tuple, list)):
+        d = (d.offset, d.floor, d.vmin, d.vmax)
+    off, flo, lo, hi = d
+    row = (0.0 if off is None else float(off), float("-inf") if flo is None else float(flo),
+           float("nan") if lo is None else float(lo), float("nan") if hi is None else float(hi))
+    if row[0] != row[0] or abs(row[0]) == float("inf") or abs(row[2]) == float("inf") or abs(row[3]) == float("inf"):
+        raise L.P4CError(f"forecast_frames: display row {d}: a finite offset, and a finite or absent (auto-scaled) range expected")
+    return row
+
+
+@functools.lru_cache(maxsize=32)
+def _forecast_tables(features: tuple, rows: tuple, device_index: int):
+    dev = torch.device("cuda", device_index)
+    return (torch.tensor(features, dtype=torch.int32, device=dev), torch.tensor(rows, dtype=torch.float32, device=dev).reshape(-1, 4),
+            any(r[2] != r[2] or r[3] != r[3] for r in rows))
+
+
+def forecast_frames(pred, std, mean, display, samples=None, features=None, out=None):
+    """The normalised prediction (B,T,H,W,F) -- or (B,T,N,F), one row of N pixels -- -> palette-index frames (p4c_forecast_frames):
+    ``frames`` (n,T,K,H,W) uint8, grid row 0 at the bottom, and ``vrange`` (n,T,K,2) fp32, the colour range of every frame.
+    ``display``: one row (offset, floor, vmin, vmax) per feature of F (tuples, or objects with these attributes; None = none /
+    auto-scaled per frame); ``samples``: indices into B (default all); ``features``: indices into F to draw (default all).
+    A pixel is ``v = pred*std + mean (+ offset)``; it gets FORECAST_BAD = 255 when v is not finite or below the floor, else 0 ..
+    254 by matplotlib's Normalize rule over 255 colours.  ``out``: (frames, vrange) dense device tensors of those shapes to write
+    into, frames 4-byte aligned.  Not differentiable."""
+    L.require_cuda(pred, std, mean)
+    if pred.dim() not in (4, 5):
+        raise L.P4CError(f"forecast_frames: prediction {tuple(pred.shape)}: (B, T, H, W, F) or (B, T, N, F) expected")
+    B, T, F = pred.shape[0], pred.shape[1], pred.shape[-1]
+    H, W = (pred.shape[2], pred.shape[3]) if pred.dim() == 5 else (1, pred.shape[2])
+    display = list(display)
+    if len(display) != F or std.numel() != F or mean.numel() != F:
+        raise L.P4CError(f"forecast_frames: {len(display)} display rows / {std.numel()} standard deviations / {mean.numel()} means "
+                         f"for {F} features")
+    features = tuple(range(F)) if features is None else tuple(int(f) for f in features)
+    samples = tuple(range(B)) if samples is None else tuple(int(s) for s in samples)
+    K, n = len(features), len(samples)
+    if not 1 <= K <= FORECAST_MAX_FEATURES:
+        raise L.P4CError(f"forecast_frames: {K} features: 1 .. at most {FORECAST_MAX_FEATURES} per call")
+    if min(features) < 0 or max(features) >= F:
+        raise L.P4CError(f"forecast_frames: feature indices {features} leave 0 .. {F - 1}")
+    if not 1 <= n <= FORECAST_MAX_SAMPLES or n * T > 65535:
+        raise L.P4CError(f"forecast_frames: {n} samples: 1 .. at most {FORECAST_MAX_SAMPLES} per call, n*T <= 65535")
+    if min(samples) < 0 or max(samples) >= B:
+        raise L.P4CError(f"forecast_frames: sample indices {samples} leave 0 .. {B - 1}")
+    N = H * W
+    if n * T * K * N >= 2 ** 31:
+        raise L.P4CError(f"forecast_frames: {n * T * K * N} pixels: fewer than 2^31 per call")
+    p, (pbs, pts) = _rows(pred.detach().float(), 2)
+    dev = p.device
+    std, mean = std.to(p).contiguous(), mean.to(p).contiguous()
+    rows = tuple(_display_row(display[f]) for f in features)
+    index, table, auto = _forecast_tables(features, rows, dev.index if dev.index is not None else torch.cuda.current_device())
+    fshape, rshape = (n, T, K, H, W), (n, T, K, 2)
+    if out is None:
+        frames = torch.empty(fshape, dtype=torch.uint8, device=dev)
+        vrange = torch.empty(rshape, dtype=torch.float32, device=dev)
+    else:
+        frames, vrange = out
+        if (tuple(frames.shape) != fshape or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.device != dev
+                or frames.data_ptr() % 4 or tuple(vrange.shape) != rshape or vrange.dtype != torch.float32
+                or not vrange.is_contiguous() or vrange.device != dev):
+            raise L.P4CError(f"forecast_frames: out: a dense, 4-byte aligned uint8 {fshape} and a dense fp32 {rshape} on {dev} expected")
+    ws = torch.empty(L.lib().p4c_forecast_frames_workspace_bytes(n, T, N, K) // 4, dtype=torch.float32, device=dev) if auto else None
+    host_samples = (ctypes.c_int32 * n)(*samples)
+    dense = bool(L.lib().p4c_forecast_frames_dense(K, F))
+    per_point = 4 * F if dense else 64 * K   # whole points, or a 64-byte line per drawn feature where no two share one
+    L.call("p4c_forecast_frames", L.ptr(p), pbs, pts, host_samples, L.ptr(std), L.ptr(mean), L.ptr(index), L.ptr(table), int(auto),
+           L.ptr(frames), L.ptr(vrange), L.ptr(ws), B, n, T, H, W, F, K, L.stream(dev),
+           alg_bytes=n * T * N * ((2 if auto else 1) * per_point + K))
+    return frames, vrange

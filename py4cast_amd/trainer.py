@@ -990,3 +990,19 @@ class Trainer:
                 mean /= dist.get_world_size()
             self.callback_metrics["val_mean_loss"] = mean
         return self.callback_metrics
+
+    def predict(self, module, dataloader: Iterable):
+        """``predict_step`` over the batches, in eval mode under no_grad; the module's forecast writer (``io_conf``: the GIFs of batch i
+        are encoded while batch i+1 is on the device) is drained at the end.  Returns the list of un-normalised predictions."""
+        module.trainer = self
+        module.eval()
+        predictions = []
+        try:
+            with torch.no_grad():
+                for i, batch in enumerate(dataloader):
+                    predictions.append(module.predict_step(self._to_device(batch, self.device), i))
+        finally:
+            writer = getattr(module, "forecast_writer", None)
+            if writer is not None:
+                writer.drain()
+        return predictions
