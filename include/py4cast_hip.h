@@ -387,6 +387,38 @@ int p4c_forecast_frames(const float* pred, int64_t pred_bs, int64_t pred_ts, con
                         const float* mean, const int32_t* features, const float* display, int auto_range, unsigned char* frames,
                         float* vrange, void* workspace, int B, int n, int T, int H, int W, int F, int K, p4c_stream_t stream);
 
+/* GRIB2 simple packing (data representation template 5.0) of the inference path (predict_step's save_gribs: lightning.py:1183-1187,
+ * io/outputs.py:116-220) on the device; the message headers stay with the caller (py4cast_amd/grib2.py).
+ *
+ * p4c_grib_pack: of the NORMALISED prediction (B,T,N,F) features-last, N = H*W (strides as p4c_forecast_frames takes them), the
+ * samples `samples` (HOST int32, n of them, each 0 .. B-1) and the K features `features` (device int32, each 0 .. F-1: the caller
+ * checks), with `spec` (HOST int32 (K,2): decimal scale factor D and width nbits per packed feature):
+ *   params (n,T,K,5) int32: vmin, vmax, R (the bits of three fp32), E, bad;
+ *   packed (n,T,K,pitch) bytes: the first ceil(N*nbits/8) bytes of a row are the field's bit stream, the rest is left alone.
+ * v = pred*std + mean in two rounded fp32 steps; vmin / vmax: min / max of the finite v ((NaN, NaN) without one); bad: how many v
+ * are not finite (the stream of such a field is unspecified).  In float64, one rounded operation each: s(v) = v * 10^D (D >= 0) or
+ * v / 10^-D; R the largest fp32 <= s(vmin); E the smallest integer with ldexp(s(vmax) - R, -E) <= 2^nbits - 1 (0 when vmax == vmin);
+ * X = min(floor(ldexp(s(v) - R, -E) + 0.5), 2^nbits - 1).  The stream holds X of stream point 0, 1, .. in nbits bits each, most
+ * significant bit first, the last octet zero-padded; stream point r*W + x is grid point (r, x), or (H-1-r, x) with flip_rows.
+ * A decoded value is (R + X * 2^E) / 10^D.  Three launches (range partials in `workspace`, p4c_grib_pack_workspace_bytes(n,T,N,K);
+ * finish; pack), no atomics: two calls give the same bytes.
+ * Errors (nothing is launched): a null pointer, K > p4c_grib_max_features(), n > p4c_grib_max_samples(), n*T > 65535, a sample
+ * index outside 0 .. B-1, |D| > 15, nbits outside 1 .. 32, `packed` not 4-byte aligned, a pitch that is no multiple of 4 or
+ * shorter than the longest stream, more than 2^31 - 1 stream bytes (n*T*K*pitch) or grid points.
+ *
+ * p4c_grib_tile / p4c_grib_max_blocks: points per loop trip of a workgroup / workgroups per launch over all (sample, lead time)
+ * pairs: each pair gets min(tiles, max(1, max_blocks / (n*T))) workgroups, which stride over its tiles.
+ * p4c_grib_pack_dense(K, F): 1 when the call reads whole points and transposes through LDS, 0 when it gathers the K features. */
+int p4c_grib_tile(void);
+int p4c_grib_max_blocks(void);
+int p4c_grib_max_features(void);
+int p4c_grib_max_samples(void);
+int p4c_grib_pack_dense(int K, int F);
+size_t p4c_grib_pack_workspace_bytes(int n, int T, int64_t N, int K);
+int p4c_grib_pack(const float* pred, int64_t pred_bs, int64_t pred_ts, const int32_t* samples, const float* std, const float* mean,
+                  const int32_t* features, const int32_t* spec, int flip_rows, int32_t* params, unsigned char* packed, int64_t pitch,
+                  void* workspace, int B, int n, int T, int H, int W, int F, int K, p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

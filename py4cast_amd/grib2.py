@@ -1,0 +1,433 @@
+"""
+GRIB edition 2 on a regular latitude / longitude grid, as far as the forecast writer needs it (``outputs.ForecastGribWriter``):
+read a template file, find the message a feature is written with, and emit a new message around a simple-packed bit stream that
+``ops.grib_pack`` (csrc/grib_pack.hip) -- or ``pack_fields`` below, on the CPU -- produced.  numpy only: no eccodes, no epygram.
+
+The layout is the WMO one (Manual on Codes I.2, FM 92).  Octets are 1-based, integers big-endian, negative values sign-and-magnitude
+(the top bit of the field set): E, D, latitudes, longitudes, scale factors and scaled values.
+
+  section 0 (16)   "GRIB"; 7 discipline; 8 edition = 2; 9-16 total length
+  section 1        6-7 centre; 8-9 sub-centre; 10-11 table versions; 12 significance of the reference time; 13-14 year; 15 month;
+                   16 day; 17 hour; 18 minute; 19 second; 20 production status; 21 type of data
+  section 2        local use, optional: carried through untouched
+  section 3 (72)   grid definition template 3.0 only: 7-10 number of points; 11-12 must be 0; 13-14 template number; 31-34 Ni;
+                   35-38 Nj; 39-42 basic angle; 43-46 subdivisions; 47-50 La1; 51-54 Lo1; 56-59 La2; 60-63 Lo2; 64-67 Di; 68-71 Dj;
+                   72 scanning mode.  Angles in 1e-6 degree when basic angle and subdivisions are 0 or missing.
+  section 4        6-7 number of coordinate values (must be 0); 8-9 template number: 4.0 (34 octets) or 4.8 (58): 10 category;
+                   11 number; 18 unit of time range; 19-22 forecast time; 23 first surface type; 24 scale factor; 25-28 scaled value;
+                   29 second surface type; 4.8: 35-41 END of the interval; 42 number of time ranges (must be 1); 47 statistical
+                   process; 49 unit; 50-53 length of the time range
+  section 5 (21)   template 5.0: 6-9 number of packed values; 12-15 R (binary32); 16-17 E; 18-19 D; 20 nbits; 21 = 0
+  section 6        6 bitmap indicator: 0 = a bitmap follows (most significant bit first, 1 = value present), 255 = none
+  section 7        6.. the packed values;   section 8  "7777"
+
+A decoded value is ``Y = (R + X 2^E) / 10^D``.
+
+What ``Template.find`` compares, with the key names of the reference's ``feature2fid`` (io/outputs.py:325-433): ``discipline``,
+``parameterCategory``, ``parameterNumber``, ``typeOfFirstFixedSurface``, ``level`` (the first surface's scaled value with its scale
+factor applied; 0 where either is missing), ``typeOfSecondFixedSurface``, ``productDefinitionTemplateNumber`` and, for template 8,
+``lengthOfTimeRange`` and ``typeOfStatisticalProcessing``.  ``editionNumber`` (always 2 here), ``name``, ``shortName`` (eccodes'
+tables, not in the message) and ``tablesVersion`` are IGNORED.
+
+Refused, each with the octet in the message: a grid template other than 3.0; scanning-mode bits 0x80 (points run in the -i
+direction), 0x20 (adjacent points consecutive in j) and 0x10 (alternate rows reversed); a list of numbers of points; coordinate values
+in section 4; a product template other than 4.0 / 4.8; more than one time range; a data representation template other than 5.0,
+5.2, 5.3, 5.40, 5.41 as the source of D and nbits (these share octets 18-19 and 20); anything but 5.0 on decoding; a message with
+repeated sections.  Scanning-mode bit 0x40 (rows run south to north) is honoured.
+"""
+import datetime as dt
+import math
+import struct
+from functools import lru_cache
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+IGNORED_KEYS = ("editionNumber", "name", "shortName", "tablesVersion")
+MATCHED_KEYS = ("discipline", "parameterCategory", "parameterNumber", "typeOfFirstFixedSurface", "level", "typeOfSecondFixedSurface",
+                "productDefinitionTemplateNumber", "lengthOfTimeRange", "typeOfStatisticalProcessing")
+D_NBITS_TEMPLATES = (0, 2, 3, 40, 41)
+UNIT_MINUTE, UNIT_HOUR = 0, 1
+MAX_D = 15
+
+
+class GribError(ValueError):
+    pass
+
+
+# ------------------------------------------------------------------------------------------------ octets
+def _u(b: bytes, octet: int, n: int) -> int:
+    return int.from_bytes(b[octet - 1:octet - 1 + n], "big")
+
+
+def _s(b: bytes, octet: int, n: int) -> int:
+    raw = _u(b, octet, n)
+    top = 1 << (8 * n - 1)
+    return -(raw & (top - 1)) if raw & top else raw
+
+
+def _missing(b: bytes, octet: int, n: int) -> bool:
+    return _u(b, octet, n) == (1 << (8 * n)) - 1
+
+
+def _put_u(b: bytearray, octet: int, n: int, value: int) -> None:
+    if not 0 <= value < 1 << (8 * n):
+        raise GribError(f"{value} does not fit the {n} octets at {octet}")
+    b[octet - 1:octet - 1 + n] = int(value).to_bytes(n, "big")
+
+
+def _put_s(b: bytearray, octet: int, n: int, value: int) -> None:
+    top = 1 << (8 * n - 1)
+    if abs(value) >= top:
+        raise GribError(f"{value} does not fit the {n} octets at {octet}")
+    _put_u(b, octet, n, (top | -value) if value < 0 else value)
+
+
+# ------------------------------------------------------------------------------------------------ messages
+class Message:
+    """One GRIB2 message: ``discipline``, ``sections`` (number -> the section's bytes, length prefix included; 0 and 8 too) and the
+    parsed ``keys``."""
+
+    def __init__(self, raw: bytes):
+        if raw[:4] != b"GRIB" or len(raw) < 20:
+            raise GribError("not a GRIB message")
+        if raw[7] != 2:
+            raise GribError(f"section 0 octet 8: edition {raw[7]}, only edition 2 is read")
+        total = _u(raw, 9, 8)
+        if total != len(raw) or raw[-4:] != b"7777":
+            raise GribError(f"section 0 octets 9-16: length {total} of a message of {len(raw)} octets (or no 7777 at its end)")
+        self.raw = bytes(raw)
+        self.discipline = raw[6]
+        self.sections: Dict[int, bytes] = {0: bytes(raw[:16]), 8: b"7777"}
+        at = 16
+        while at < total - 4:
+            length, number = _u(raw, at + 1, 4), raw[at + 4]
+            if length < 5 or at + length > total - 4 or not 1 <= number <= 7:
+                raise GribError(f"section {number} of {length} octets at offset {at} does not fit the message")
+            if number in self.sections:
+                raise GribError(f"section {number} is repeated: messages with several fields are not read")
+            self.sections[number] = bytes(raw[at:at + length])
+            at += length
+        for number in (1, 3, 4, 5, 6, 7):
+            if number not in self.sections:
+                raise GribError(f"section {number} is missing")
+        self.keys = _keys(self)
+
+    def __repr__(self):
+        k = self.keys
+        return (f"Message(discipline={k['discipline']}, category={k['parameterCategory']}, number={k['parameterNumber']}, "
+                f"template=4.{k['productDefinitionTemplateNumber']})")
+
+
+def _datetime(b: bytes, octet: int) -> Optional[dt.datetime]:
+    try:
+        return dt.datetime(_u(b, octet, 2), b[octet + 1], b[octet + 2], b[octet + 3], b[octet + 4], b[octet + 5])
+    except ValueError:
+        return None
+
+
+def _keys(m: Message) -> dict:
+    s1, s3, s4, s5, s6 = (m.sections[i] for i in (1, 3, 4, 5, 6))
+    k = {"discipline": m.discipline, "editionNumber": 2, "centre": _u(s1, 6, 2), "subCentre": _u(s1, 8, 2), "tablesVersion": s1[9],
+         "referenceTime": _datetime(s1, 13), "hasLocalSection": 2 in m.sections,
+         "gridDefinitionTemplateNumber": _u(s3, 13, 2), "numberOfDataPoints": _u(s3, 7, 4),
+         "numberOfCoordinateValues": _u(s4, 6, 2), "productDefinitionTemplateNumber": _u(s4, 8, 2)}
+    if k["gridDefinitionTemplateNumber"] == 0 and len(s3) >= 72:
+        k.update(Ni=_u(s3, 31, 4), Nj=_u(s3, 35, 4), basicAngle=_u(s3, 39, 4), subdivisions=_u(s3, 43, 4), La1=_s(s3, 47, 4),
+                 Lo1=_s(s3, 51, 4), La2=_s(s3, 56, 4), Lo2=_s(s3, 60, 4), Di=_u(s3, 64, 4), Dj=_u(s3, 68, 4), scanningMode=s3[71])
+    if k["productDefinitionTemplateNumber"] in (0, 8) and len(s4) >= 34:
+        scale, value = _s(s4, 24, 1), _s(s4, 25, 4)
+        absent = _missing(s4, 24, 1) or _missing(s4, 25, 4)
+        k.update(parameterCategory=s4[9], parameterNumber=s4[10], indicatorOfUnitOfTimeRange=s4[17], forecastTime=_u(s4, 19, 4),
+                 typeOfFirstFixedSurface=s4[22], typeOfSecondFixedSurface=s4[28],
+                 level=0 if absent else value / 10 ** scale)
+        if k["productDefinitionTemplateNumber"] == 8 and len(s4) >= 58:
+            k.update(endOfInterval=_datetime(s4, 35), numberOfTimeRanges=s4[41], typeOfStatisticalProcessing=s4[46],
+                     indicatorOfUnitForTimeRange=s4[48], lengthOfTimeRange=_u(s4, 50, 4))
+    k.update(numberOfValues=_u(s5, 6, 4), dataRepresentationTemplateNumber=_u(s5, 10, 2), bitMapIndicator=s6[5])
+    if k["dataRepresentationTemplateNumber"] in D_NBITS_TEMPLATES and len(s5) >= 20:
+        k.update(referenceValue=struct.unpack(">f", s5[11:15])[0], binaryScaleFactor=_s(s5, 16, 2), decimalScaleFactor=_s(s5, 18, 2),
+                 bitsPerValue=s5[19])
+    return k
+
+
+def parse_messages(data: bytes) -> List[Message]:
+    out, at = [], 0
+    while True:
+        at = data.find(b"GRIB", at)
+        if at < 0 or at + 16 > len(data):
+            return out
+        total = _u(data[at:at + 16], 9, 8)
+        out.append(Message(data[at:at + total]))
+        at += total
+
+
+def read_messages(path) -> List[Message]:
+    """Walk a GRIB2 file into its messages."""
+    with open(path, "rb") as f:
+        return parse_messages(f.read())
+
+
+def check_grid(m: Message) -> None:
+    """Raise for a grid this module does not write on (module docstring)."""
+    s3 = m.sections[3]
+    number = _u(s3, 13, 2)
+    if number != 0 or len(s3) < 72:
+        raise GribError(f"section 3 octets 13-14: grid definition template 3.{number}; only 3.0 (regular latitude / longitude) is written")
+    if s3[10] != 0 or s3[11] != 0:
+        raise GribError(f"section 3 octets 11-12: a list of numbers of points ({s3[10]}, {s3[11]}) is not read")
+    mode = s3[71]
+    for bit, what in ((0x80, "points are scanned in the -i direction"), (0x20, "adjacent points are consecutive in j"),
+                      (0x10, "alternate rows are scanned in the opposite direction")):
+        if mode & bit:
+            raise GribError(f"section 3 octet 72: scanning mode 0x{mode:02x}: bit 0x{bit:02x} ({what}) is not written")
+    if m.keys["Ni"] * m.keys["Nj"] != m.keys["numberOfDataPoints"]:
+        raise GribError(f"section 3 octets 7-10: {m.keys['numberOfDataPoints']} points on a grid of {m.keys['Ni']} x {m.keys['Nj']}")
+
+
+def check_product(m: Message) -> None:
+    s4 = m.sections[4]
+    if _u(s4, 6, 2) != 0:
+        raise GribError(f"section 4 octets 6-7: {_u(s4, 6, 2)} coordinate values; vertical coordinate lists are not written")
+    number = _u(s4, 8, 2)
+    if number not in (0, 8) or len(s4) < (34 if number == 0 else 58):
+        raise GribError(f"section 4 octets 8-9: product definition template 4.{number}; only 4.0 and 4.8 are written")
+    if number == 8 and s4[41] != 1:
+        raise GribError(f"section 4 octet 42: {s4[41]} time ranges; exactly one is written")
+
+
+def spec_of(m: Message) -> Tuple[int, int]:
+    """(D, nbits) of a template message: octets 18-19 and 20 of section 5, where templates 5.0, 5.2, 5.3, 5.40 and 5.41 keep them"""
+    s5 = m.sections[5]
+    number = _u(s5, 10, 2)
+    if number not in D_NBITS_TEMPLATES or len(s5) < 20:
+        raise GribError(f"section 5 octets 10-11: data representation template 5.{number}: D and nbits are taken from 5.0, 5.2, 5.3, 5.40, 5.41")
+    D, nbits = _s(s5, 18, 2), s5[19]
+    if abs(D) > MAX_D or not 1 <= nbits <= 32:
+        raise GribError(f"section 5 octets 18-20: D = {D}, nbits = {nbits}: |D| <= {MAX_D} and 1 <= nbits <= 32 are packed")
+    return D, nbits
+
+
+def grid_of(m: Message):
+    """(Ni, Nj, lat, lon, scanning mode): ``lat[r]`` the latitude of stream row r, ``lon[c]`` the longitude of stream column c, degrees;
+    longitudes are wrapped into [-180, 180)"""
+    check_grid(m)
+    k = m.keys
+    basic, sub = k["basicAngle"], k["subdivisions"]
+    unit = 1e-6 if basic in (0, 0xFFFFFFFF) or sub in (0, 0xFFFFFFFF) else basic / sub
+    lat = np.linspace(k["La1"] * unit, k["La2"] * unit, k["Nj"])
+    lo1, lo2 = k["Lo1"] * unit, k["Lo2"] * unit
+    if lo2 < lo1:
+        lo2 += 360.0
+    lon = (np.linspace(lo1, lo2, k["Ni"]) + 180.0) % 360.0 - 180.0
+    south_to_north = bool(k["scanningMode"] & 0x40)
+    if k["Nj"] > 1 and (lat[-1] > lat[0]) != south_to_north:
+        raise GribError(f"section 3 octet 72: scanning mode 0x{k['scanningMode']:02x} against La1 = {lat[0]}, La2 = {lat[-1]}")
+    return k["Ni"], k["Nj"], lat, lon, k["scanningMode"]
+
+
+class Template:
+    """The messages of a template GRIB2 file; every one of them must be on a grid this module writes on."""
+
+    def __init__(self, path):
+        self.path = path
+        self.messages = read_messages(path)
+        if not self.messages:
+            raise GribError(f"{path}: no GRIB2 message")
+        for m in self.messages:
+            check_grid(m)
+
+    def find(self, fid: dict) -> Message:
+        """The first message whose keys equal those of ``fid`` (module docstring: which are compared, which ignored)."""
+        unknown = sorted(set(fid) - set(MATCHED_KEYS) - set(IGNORED_KEYS))
+        if unknown:
+            raise GribError(f"keys {unknown} are not matched")
+        wanted = {k: v for k, v in fid.items() if k in MATCHED_KEYS}
+        for m in self.messages:
+            if all(k in m.keys and m.keys[k] == v for k, v in wanted.items()):
+                return m
+        raise KeyError(f"{self.path}: no message with {wanted}")
+
+    def grid(self, message: Optional[Message] = None):
+        return grid_of(self.messages[0] if message is None else message)
+
+
+def match_latlon(grid_lat, grid_lon, lat: np.ndarray, lon: np.ndarray, what="dataset") -> Tuple[int, int, int, int]:
+    """io/outputs.py:269-322: where the forecast grid (``grid_lat``, ``grid_lon``: any shape) sits in the template's vectors, compared
+    after rounding to 5 decimals -> (first row, last row, first column, last column) of the template grid, in its stream order.  The
+    forecast grid must lie inside the template's or equal it."""
+    grid_lat, grid_lon = np.asarray(grid_lat, dtype=np.float64), np.asarray(grid_lon, dtype=np.float64)
+    error = ValueError(f"Lat/Lon dims of the {what} do not fit in template grid, cannot write grib.")
+    if not (lat.min() <= grid_lat.min() and lat.max() >= grid_lat.max() and lon.min() <= grid_lon.min() and lon.max() >= grid_lon.max()):
+        raise error
+    found = [np.where(np.round(vec, 5) == round(float(v), 5))[0]
+             for vec, v in ((lat, grid_lat.min()), (lat, grid_lat.max()), (lon, grid_lon.min()), (lon, grid_lon.max()))]
+    if any(len(f) != 1 for f in found):
+        raise error
+    a, b, c, d = (int(f[0]) for f in found)
+    return min(a, b), max(a, b), min(c, d), max(c, d)
+
+
+@lru_cache(maxsize=16)
+def _bitmap(Nj: int, Ni: int, window: Tuple[int, int, int, int]) -> Optional[bytes]:
+    r0, r1, c0, c1 = window
+    if (r0, r1, c0, c1) == (0, Nj - 1, 0, Ni - 1):
+        return None
+    present = np.zeros((Nj, Ni), dtype=np.uint8)
+    present[r0:r1 + 1, c0:c1 + 1] = 1
+    return np.packbits(present.reshape(-1)).tobytes()
+
+
+def _time_in_unit(delta: dt.timedelta, what: str) -> Tuple[int, int]:
+    seconds = delta.total_seconds()
+    if seconds < 0 or seconds != int(seconds) or int(seconds) % 60:
+        raise GribError(f"{what} {delta}: whole minutes, not negative, are written")
+    seconds = int(seconds)
+    return (UNIT_HOUR, seconds // 3600) if seconds % 3600 == 0 else (UNIT_MINUTE, seconds // 60)
+
+
+def encode(template_message: Message, basis: dt.datetime, term: dt.timedelta, *, cumulative: Optional[dt.timedelta] = None,
+           window: Tuple[int, int, int, int], packed: bytes, R: float, E: int, D: int, nbits: int) -> bytes:
+    """A new message: sections 0-4 of ``template_message`` with the reference time (``basis``) and the forecast time (``term``; for
+    template 4.8 the interval of length ``cumulative`` that ENDS at basis + term) patched in, and new sections 5-7 around ``packed``,
+    the simple-packed stream of the ``window`` (first row, last row, first column, last column of the template grid in stream order;
+    the points outside it are absent in the bitmap)."""
+    m = template_message
+    check_grid(m)
+    check_product(m)
+    Ni, Nj = m.keys["Ni"], m.keys["Nj"]
+    r0, r1, c0, c1 = window
+    if not (0 <= r0 <= r1 < Nj and 0 <= c0 <= c1 < Ni):
+        raise GribError(f"window {window} on a grid of {Nj} x {Ni}")
+    if abs(D) > MAX_D or not 1 <= nbits <= 32:
+        raise GribError(f"D = {D}, nbits = {nbits}: |D| <= {MAX_D} and 1 <= nbits <= 32 are packed")
+    count = (r1 - r0 + 1) * (c1 - c0 + 1)
+    packed = bytes(packed)
+    if len(packed) != (count * nbits + 7) // 8:
+        raise GribError(f"{len(packed)} packed octets for {count} values of {nbits} bits")
+    s1 = bytearray(m.sections[1])
+    _put_u(s1, 13, 2, basis.year)
+    for i, v in enumerate((basis.month, basis.day, basis.hour, basis.minute, basis.second)):
+        s1[14 + i] = v
+    s4 = bytearray(m.sections[4])
+    if m.keys["productDefinitionTemplateNumber"] == 8:
+        if cumulative is None:
+            raise GribError("template 4.8 needs the cumulative duration")
+        unit, value = _time_in_unit(term - cumulative, "start of the interval")
+        end = basis + term
+        _put_u(s4, 35, 2, end.year)
+        for i, v in enumerate((end.month, end.day, end.hour, end.minute, end.second)):
+            s4[36 + i] = v
+        lunit, length = _time_in_unit(cumulative, "cumulative duration")
+        s4[48] = lunit
+        _put_u(s4, 50, 4, length)
+    else:
+        unit, value = _time_in_unit(term, "term")
+    s4[17] = unit
+    _put_u(s4, 19, 4, value)
+    s5 = bytearray(21)
+    _put_u(s5, 1, 4, 21)
+    s5[4] = 5
+    _put_u(s5, 6, 4, count)
+    s5[11:15] = struct.pack(">f", R)
+    _put_s(s5, 16, 2, E)
+    _put_s(s5, 18, 2, D)
+    s5[19] = nbits
+    bitmap = _bitmap(Nj, Ni, (r0, r1, c0, c1))
+    s6 = bytearray(6)
+    _put_u(s6, 1, 4, 6 + (len(bitmap) if bitmap is not None else 0))
+    s6[4], s6[5] = 6, (255 if bitmap is None else 0)
+    s7 = bytearray(5)
+    _put_u(s7, 1, 4, 5 + len(packed))
+    s7[4] = 7
+    body = [bytes(s1)] + ([m.sections[2]] if 2 in m.sections else []) + [m.sections[3], bytes(s4), bytes(s5), bytes(s6), bitmap or b"",
+                                                                       bytes(s7), packed, b"7777"]
+    s0 = bytearray(m.sections[0])
+    _put_u(s0, 9, 8, 16 + sum(len(b) for b in body))
+    return bytes(s0) + b"".join(body)
+
+
+def unpack_bits(data: bytes, count: int, nbits: int) -> np.ndarray:
+    """``count`` unsigned integers of ``nbits`` bits, most significant bit first -> uint64"""
+    bits = np.unpackbits(np.frombuffer(data, dtype=np.uint8), count=count * nbits).reshape(count, nbits).astype(np.uint64)
+    return (bits << np.arange(nbits - 1, -1, -1, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+
+
+def decode(message) -> Tuple[np.ma.MaskedArray, dict]:
+    """A simple-packed (5.0) message on a 3.0 grid -> ((Nj, Ni) masked float64 in stream order, the parsed keys)."""
+    m = message if isinstance(message, Message) else Message(message)
+    check_grid(m)
+    k = m.keys
+    if k["dataRepresentationTemplateNumber"] != 0:
+        raise GribError(f"section 5 octets 10-11: data representation template 5.{k['dataRepresentationTemplateNumber']}; only 5.0 is decoded")
+    Ni, Nj, count, nbits = k["Ni"], k["Nj"], k["numberOfValues"], k["bitsPerValue"]
+    if k["bitMapIndicator"] == 255:
+        present = np.ones(Nj * Ni, dtype=bool)
+    elif k["bitMapIndicator"] == 0:
+        present = np.unpackbits(np.frombuffer(m.sections[6][6:], dtype=np.uint8), count=Nj * Ni).astype(bool)
+    else:
+        raise GribError(f"section 6 octet 6: bitmap indicator {k['bitMapIndicator']}")
+    if int(present.sum()) != count:
+        raise GribError(f"section 5 octets 6-9: {count} values for {int(present.sum())} points present")
+    X = unpack_bits(m.sections[7][5:], count, nbits).astype(np.float64) if nbits else np.zeros(count)
+    values = np.zeros(Nj * Ni, dtype=np.float64)
+    D = k["decimalScaleFactor"]
+    scaled = float(k["referenceValue"]) + np.ldexp(X, k["binaryScaleFactor"])
+    values[present] = scaled / float(10 ** D) if D >= 0 else scaled * float(10 ** -D)
+    return np.ma.MaskedArray(values.reshape(Nj, Ni), mask=~present.reshape(Nj, Ni)), k
+
+
+# ------------------------------------------------------------------------------------------------ the packer on the CPU
+def pack_simple(v: np.ndarray, D: int, nbits: int):
+    """The contract of csrc/grib_pack.hip for one field in stream order: v fp32 (N,) -> (vmin, vmax, R, E, bad, the stream's bytes)"""
+    if abs(D) > MAX_D or not 1 <= nbits <= 32:
+        raise GribError(f"D = {D}, nbits = {nbits}: |D| <= {MAX_D} and 1 <= nbits <= 32 are packed")
+    v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    finite = np.isfinite(v)
+    bad = int(v.size - finite.sum())
+    pw = float(10 ** abs(D))
+    with np.errstate(all="ignore"):
+        s = v.astype(np.float64) * pw if D >= 0 else v.astype(np.float64) / pw
+    xmax = float(2 ** nbits - 1)
+    if bad == v.size:
+        vmin = vmax = np.float32(np.nan)
+        R, E = np.float32(0.0), 0
+    else:
+        vmin, vmax = v[finite].min(), v[finite].max()
+        smin, smax = (float(x) * pw if D >= 0 else float(x) / pw for x in (vmin, vmax))
+        with np.errstate(all="ignore"):
+            R = np.float32(smin)
+        if float(R) > smin:
+            R = np.nextafter(R, np.float32(-np.inf))
+        E, span = 0, smax - float(R)
+        if vmax != vmin and 0.0 < span < math.inf:
+            E = math.frexp(span)[1] - nbits - 1
+            while math.ldexp(span, -E) > xmax:
+                E += 1
+    with np.errstate(all="ignore"):
+        X = np.floor(np.ldexp(s - float(R), -E) + 0.5)
+        X = np.where(X < xmax, np.where(X > 0.0, X, 0.0), xmax).astype(np.uint64)
+    bits = ((X[:, None] >> np.arange(nbits - 1, -1, -1, dtype=np.uint64)) & np.uint64(1)).astype(np.uint8)
+    return vmin, vmax, R, E, bad, np.packbits(bits.reshape(-1)).tobytes()
+
+
+def pack_fields(pred: np.ndarray, std: np.ndarray, mean: np.ndarray, spec: Sequence[Tuple[int, int]], samples: Sequence[int],
+                features: Sequence[int], H: int, W: int, flip_rows: bool, pitch: int):
+    """``ops.grib_pack`` on the CPU: pred (B,T,N,F) fp32 normalised -> params (n,T,K,5) int32, packed (n,T,K,pitch) uint8"""
+    pred = np.asarray(pred, dtype=np.float32)
+    std, mean = np.asarray(std, dtype=np.float32), np.asarray(mean, dtype=np.float32)
+    n, T, K = len(samples), pred.shape[1], len(features)
+    params = np.zeros((n, T, K, 5), dtype=np.int32)
+    packed = np.zeros((n, T, K, pitch), dtype=np.uint8)
+    for i, b in enumerate(samples):
+        for t in range(T):
+            for k, f in enumerate(features):
+                a = pred[b, t, :, f] * std[f]
+                v = (a + mean[f]).astype(np.float32).reshape(H, W)
+                if flip_rows:
+                    v = v[::-1]
+                vmin, vmax, R, E, bad, stream = pack_simple(v, spec[k][0], spec[k][1])
+                params[i, t, k, :3] = np.array([vmin, vmax, R], dtype=np.float32).view(np.int32)
+                params[i, t, k, 3:] = (E, bad)
+                packed[i, t, k, :len(stream)] = np.frombuffer(stream, dtype=np.uint8)
+    return params, packed

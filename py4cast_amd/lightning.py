@@ -827,8 +827,9 @@ class AutoRegressiveLightning(_Base):
 
     def _write_forecast_outputs(self, batch_idx: int, preds: NamedTensor, std: torch.Tensor, mean: torch.Tensor) -> None:
         """``io_conf`` is set: the GIFs of the accepted samples (lightning.py:1133-1188) through ``outputs.ForecastGifWriter``, kept
-        as ``self.forecast_writer`` -- whoever runs the loop drains it at the end (``Trainer.predict`` does)."""
-        from .outputs import ForecastGifWriter, OutputSavingSettings
+        as ``self.forecast_writer``, and with ``save_gribs`` their GRIB2 files through ``outputs.ForecastGribWriter``, kept as
+        ``self.grib_writer`` -- whoever runs the loop drains them at the end (``Trainer.predict`` does)."""
+        from .outputs import ForecastGifWriter, ForecastGribWriter, GribSample, OutputSavingSettings
 
         if getattr(self, "_output_settings", None) is None:
             self._output_settings = OutputSavingSettings.from_json(self.io_conf)   # read once
@@ -836,11 +837,21 @@ class AutoRegressiveLightning(_Base):
         runtimes, accepted = self.forecast_samples(batch_idx, preds.tensor.shape[0])
         if not any(accepted):
             return
-        if getattr(datamodule, "save_gribs", getattr(self, "save_gribs", False)) and not getattr(self, "_warned_gribs", False):
-            import warnings
+        if getattr(datamodule, "save_gribs", getattr(self, "save_gribs", False)):
+            if getattr(self, "grib_writer", None) is None and not getattr(self, "_warned_gribs", False):
+                # None unless the settings' template parses and infer_ds carries a sample_list and a grid
+                self.grib_writer = ForecastGribWriter.for_dataset(self._output_settings, self.infer_ds, preds.tensor.device)
+            if getattr(self, "grib_writer", None) is not None:
+                batch_size = preds.tensor.shape[0]
+                samples = self.infer_ds.sample_list
+                self.grib_writer.submit(preds, std, mean, [
+                    GribSample.from_sample(samples[batch_idx * batch_size + b], runtimes[b]) if accepted[b] else None
+                    for b in range(batch_size)])
+            elif not getattr(self, "_warned_gribs", False):
+                import warnings
 
-            self._warned_gribs = True
-            warnings.warn("save_gribs: writing GRIB files needs epygram and a template GRIB; none is written")
+                self._warned_gribs = True
+                warnings.warn("save_gribs: writing GRIB files needs epygram and a template GRIB; none is written")
         if not getattr(datamodule, "save_gifs", getattr(self, "save_gifs", True)):
             return
         if getattr(self, "forecast_writer", None) is None:

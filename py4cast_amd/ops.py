@@ -799,3 +799,82 @@ def forecast_frames(pred, std, mean, display, samples=None, features=None, out=N
            L.ptr(frames), L.ptr(vrange), L.ptr(ws), B, n, T, H, W, F, K, L.stream(dev),
            alg_bytes=n * T * N * ((2 if auto else 1) * per_point + K))
     return frames, vrange
+
+
+# ------------------------------------------------------------------------------------------------ GRIB2 simple packing
+# launch constants of csrc/grib_pack.hip (p4c_grib_tile() etc. report the same)
+GRIB_TILE = 128                # points per loop trip of a workgroup
+GRIB_MAX_BLOCKS = 1024         # workgroups of one launch, all (sample, lead time) pairs together
+GRIB_MAX_FEATURES = 256        # K of one call
+GRIB_MAX_SAMPLES = 256         # n of one call
+GRIB_PARAMS = 5                # int32 words of a params record: vmin, vmax, R (fp32 bits), E, bad
+
+
+@functools.lru_cache(maxsize=32)
+def _grib_features(features: tuple, device_index: int):
+    return torch.tensor(features, dtype=torch.int32, device=torch.device("cuda", device_index))
+
+
+def grib_pitch(N: int, spec) -> int:
+    """bytes between two fields of ``grib_pack``'s ``packed``: the longest stream, ceil(N nbits / 8), rounded up to a multiple of 4"""
+    return (max((N * int(nbits) + 7) // 8 for _, nbits in spec) + 3) // 4 * 4
+
+
+def grib_pack(pred, std, mean, spec, samples=None, features=None, flip_rows=False, out=None):
+    """The normalised prediction (B,T,H,W,F) -- or (B,T,N,F), one row of N points -- -> GRIB2 simple packing (p4c_grib_pack):
+    ``params`` (n,T,K,5) int32 -- vmin, vmax, R as the bits of fp32 values, E, bad -- and ``packed`` (n,T,K,pitch) uint8, of which the
+    first ceil(N nbits / 8) bytes of a row are the field's bit stream (``grib_pitch``).  ``spec``: one (D, nbits) per PACKED feature;
+    ``samples``: indices into B (default all); ``features``: indices into F to pack (default all); ``flip_rows``: stream row r holds
+    grid row H-1-r.  A value is ``v = pred*std + mean``, then X = min(floor((v 10^D - R) / 2^E + 0.5), 2^nbits - 1) in float64 with R
+    the largest fp32 below the field's scaled minimum and E the smallest exponent that fits its range (include/py4cast_hip.h).
+    ``out``: (params, packed) dense device tensors of those shapes to write into, packed 4-byte aligned.  Not differentiable."""
+    L.require_cuda(pred, std, mean)
+    if pred.dim() not in (4, 5):
+        raise L.P4CError(f"grib_pack: prediction {tuple(pred.shape)}: (B, T, H, W, F) or (B, T, N, F) expected")
+    B, T, F = pred.shape[0], pred.shape[1], pred.shape[-1]
+    H, W = (pred.shape[2], pred.shape[3]) if pred.dim() == 5 else (1, pred.shape[2])
+    if std.numel() != F or mean.numel() != F:
+        raise L.P4CError(f"grib_pack: {std.numel()} standard deviations / {mean.numel()} means for {F} features")
+    features = tuple(range(F)) if features is None else tuple(int(f) for f in features)
+    samples = tuple(range(B)) if samples is None else tuple(int(s) for s in samples)
+    spec = [(int(D), int(nbits)) for D, nbits in spec]
+    K, n = len(features), len(samples)
+    if not 1 <= K <= GRIB_MAX_FEATURES:
+        raise L.P4CError(f"grib_pack: {K} features: 1 .. at most {GRIB_MAX_FEATURES} per call")
+    if len(spec) != K:
+        raise L.P4CError(f"grib_pack: {len(spec)} (D, nbits) pairs for {K} packed features")
+    if min(features) < 0 or max(features) >= F:
+        raise L.P4CError(f"grib_pack: feature indices {features} leave 0 .. {F - 1}")
+    if not 1 <= n <= GRIB_MAX_SAMPLES or n * T > 65535:
+        raise L.P4CError(f"grib_pack: {n} samples: 1 .. at most {GRIB_MAX_SAMPLES} per call, n*T <= 65535")
+    if min(samples) < 0 or max(samples) >= B:
+        raise L.P4CError(f"grib_pack: sample indices {samples} leave 0 .. {B - 1}")
+    if any(abs(D) > 15 or not 1 <= nbits <= 32 for D, nbits in spec):
+        raise L.P4CError(f"grib_pack: spec {spec}: |D| <= 15 and 1 <= nbits <= 32 expected")
+    N = H * W
+    pitch = grib_pitch(N, spec)
+    if n * T * K * pitch >= 2 ** 31:
+        raise L.P4CError(f"grib_pack: {n * T * K * pitch} stream bytes: fewer than 2^31 per call")
+    p, (pbs, pts) = _rows(pred.detach().float(), 2)
+    dev = p.device
+    std, mean = std.to(p).contiguous(), mean.to(p).contiguous()
+    index = _grib_features(features, dev.index if dev.index is not None else torch.cuda.current_device())
+    pshape, sshape = (n, T, K, GRIB_PARAMS), (n, T, K, pitch)
+    if out is None:
+        params = torch.empty(pshape, dtype=torch.int32, device=dev)
+        packed = torch.empty(sshape, dtype=torch.uint8, device=dev)
+    else:
+        params, packed = out
+        if (tuple(params.shape) != pshape or params.dtype != torch.int32 or not params.is_contiguous() or params.device != dev
+                or tuple(packed.shape) != sshape or packed.dtype != torch.uint8 or not packed.is_contiguous() or packed.device != dev
+                or packed.data_ptr() % 4):
+            raise L.P4CError(f"grib_pack: out: a dense int32 {pshape} and a dense, 4-byte aligned uint8 {sshape} on {dev} expected")
+    ws = torch.empty(L.lib().p4c_grib_pack_workspace_bytes(n, T, N, K) // 4, dtype=torch.float32, device=dev)
+    host_samples = (ctypes.c_int32 * n)(*samples)
+    host_spec = (ctypes.c_int32 * (2 * K))(*[x for pair in spec for x in pair])
+    dense = bool(L.lib().p4c_grib_pack_dense(K, F))
+    per_point = 4 * F if dense else min(4 * F, 64 * K)   # whole points, or a 64-byte line per packed feature, at most the point
+    L.call("p4c_grib_pack", L.ptr(p), pbs, pts, host_samples, L.ptr(std), L.ptr(mean), L.ptr(index), host_spec, int(bool(flip_rows)),
+           L.ptr(params), L.ptr(packed), pitch, L.ptr(ws), B, n, T, H, W, F, K, L.stream(dev),
+           alg_bytes=n * T * (N * 2 * per_point + sum((N * nbits + 7) // 8 for _, nbits in spec)))
+    return params, packed

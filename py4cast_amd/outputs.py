@@ -8,8 +8,12 @@ strided gather plus a synchronous device-to-host copy per plane (3 steps x 60 fe
 Here the un-normalisation kernel writes feature-major planes (``p4c_unnormalize_planes``: (B,T,*S,F) -> (B,T,F,*S), bit-exact
 with the reference's two rounded steps) and the planes travel to PINNED host buffers with ONE asynchronous copy per batch on a
 copy stream.  Two buffers rotate, so the next batch's rollout, the copy of this batch and the host-side writers (CPU-bound:
-epygram / matplotlib) of the previous one overlap.  The GRIB writer is the reference's host code (epygram and a template file) and
-stays out of scope; it would receive numpy views of the pinned planes -- no further copies.
+epygram / matplotlib) of the previous one overlap.
+
+The GRIB writer is native (``ForecastGribWriter``): ``ops.grib_pack`` finds every field's range and packs it on the device at the
+template's decimal scale factor and width (GRIB2 simple packing), params and bit streams leave with one asynchronous copy, and the
+host only wraps them into the template's messages (``grib2.py``: no epygram, no eccodes); ``grib_fid`` holds the reference's key
+table.
 
 The GIF writer is native (``ForecastGifWriter``): ``ops.forecast_frames`` turns the normalised prediction into palette-index
 frames on the device -- one byte per pixel, every feature of every lead time of the accepted samples, the reference's colour table
@@ -19,6 +23,7 @@ them into "P"-mode GIF frames; no figure is drawn.  ``OutputSavingSettings`` rea
 
 import json
 from dataclasses import dataclass, fields
+from datetime import datetime, timedelta
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -141,6 +146,15 @@ class OutputSavingSettings:
 
     def get_gif_path(self, runtime: str, feature: str) -> Path:
         return self._path(Path(self.dir_gif), runtime, self.gif_fmt, self.gif_identifiers, {"runtime": runtime, "feature": feature})
+
+    def get_grib_path(self, runtime: str, member: int, leadtime) -> Path:
+        """io/outputs.py:88-98: the identifiers ``leadtime`` and ``member`` (three digits); ``runtime`` and ``date`` name the runtime"""
+        values = {"leadtime": leadtime, "member": str(member).zfill(3), "runtime": runtime, "date": runtime}
+        return self._path(Path(self.dir_grib), runtime, self.grib_fmt, self.grib_identifiers, values)
+
+    @property
+    def template_path(self) -> Path:
+        return Path(self.dir_grib) / self.template_grib
 
 
 @dataclass(frozen=True)
@@ -299,6 +313,221 @@ class ForecastGifWriter:
                         "ranges": [[None if v != v else float(v) for v in ranges[i, t, k]] for t in range(T)]}
                 with open(str(path) + ".json", "w") as f:
                     json.dump(side, f)
+                paths.append(path)
+        self.written.extend(paths)
+        return paths
+
+    def drain(self) -> None:
+        for slot in list(self._pending):
+            self.finish(slot)
+
+
+# ------------------------------------------------------------------------------------------------ forecast GRIBs
+# the GRIB2 keys a feature is written with (io/outputs.py:325-433; WMO code tables 4.1, 4.2, 4.5, 4.10): Template.find compares them
+GRIB_FIDS = {
+    "temperature": {"editionNumber": 2, "name": "2 metre temperature", "shortName": "2t", "discipline": 0, "parameterCategory": 0,
+                    "parameterNumber": 0, "typeOfFirstFixedSurface": 103, "level": 2, "typeOfSecondFixedSurface": 255,
+                    "tablesVersion": 15, "productDefinitionTemplateNumber": 0},
+    "u10": {"editionNumber": 2, "name": "10 metre U wind component", "shortName": "10u", "discipline": 0, "parameterCategory": 2,
+            "parameterNumber": 2, "typeOfFirstFixedSurface": 103, "level": 10, "typeOfSecondFixedSurface": 255, "tablesVersion": 15,
+            "productDefinitionTemplateNumber": 0},
+    "v10": {"editionNumber": 2, "name": "10 metre V wind component", "shortName": "10v", "discipline": 0, "parameterCategory": 2,
+            "parameterNumber": 3, "typeOfFirstFixedSurface": 103, "level": 10, "typeOfSecondFixedSurface": 255, "tablesVersion": 15,
+            "productDefinitionTemplateNumber": 0},
+    "r2": {"editionNumber": 2, "name": "2 metre relative humidity", "shortName": "2r", "discipline": 0, "parameterCategory": 1,
+           "parameterNumber": 1, "typeOfFirstFixedSurface": 103, "level": 2, "typeOfSecondFixedSurface": 255, "tablesVersion": 15,
+           "productDefinitionTemplateNumber": 0},
+    "pmer": {"editionNumber": 2, "name": "Pressure reduced to MSL", "shortName": "prmsl", "discipline": 0, "parameterCategory": 3,
+             "parameterNumber": 1, "typeOfFirstFixedSurface": 101, "level": 0, "typeOfSecondFixedSurface": 255, "tablesVersion": 15,
+             "productDefinitionTemplateNumber": 0},
+    "tp": {"editionNumber": 2, "name": "Time integral of rain flux", "shortName": "tirf", "discipline": 0, "parameterCategory": 1,
+           "parameterNumber": 65, "typeOfFirstFixedSurface": 1, "level": 0, "typeOfSecondFixedSurface": 255, "tablesVersion": 15,
+           "productDefinitionTemplateNumber": 8, "lengthOfTimeRange": 1, "typeOfStatisticalProcessing": 1},
+}
+GRIB_FEATURES = {
+    "aro_t2m_2m": "temperature", "t2m_2_heightAboveGround": "temperature", "u10_10_heightAboveGround": "u10", "aro_u10_10m": "u10",
+    "v10_10_heightAboveGround": "v10", "aro_v10_10m": "v10", "aro_prmsl_0hpa": "pmer", "aro_r2_2m": "r2", "aro_tp_0m": "tp",
+}
+
+
+def grib_fid(feature: str, time_step: int):
+    """(the GRIB2 keys of a feature, its cumulative duration) as the reference's ``feature2fid`` gives them: (None, None) for a feature
+    that is not written; the duration -- ``time_step`` seconds -- only for the accumulated one (precipitation), else None."""
+    key = GRIB_FEATURES.get(feature)
+    if key is None:
+        return None, None
+    return dict(GRIB_FIDS[key]), (timedelta(seconds=time_step) if key == "tp" else None)
+
+
+@dataclass
+class GribSample:
+    """What the file names and the headers of one sample's GRIBs need (io/outputs.py:132-160)"""
+
+    runtime: str
+    basis: datetime                  # of the initial state: section 1's reference time
+    terms: List[timedelta]           # one per lead time
+    time_step: int                   # seconds between two steps: the cumulative duration
+    member: int                      # as in the file name: the dataset's member + 1
+
+    @classmethod
+    def from_sample(cls, sample, runtime: str) -> "GribSample":
+        deltas = sample.timestamps.timedeltas
+        return cls(runtime, sample.output_timestamps.datetime, list(sample.output_timestamps.timedeltas),
+                   int((deltas[1] - deltas[0]).total_seconds()), getattr(sample, "member") + 1)
+
+
+class ForecastGribWriter:
+    """One GRIB2 file per (accepted sample, lead time) of a predicted batch, one message per feature ``grib_fid`` accepts, in the
+    prediction's feature order (io/outputs.py:116-220), each message the template's with new times and a new simple-packed field.
+
+    ``submit`` enqueues ``ops.grib_pack`` on the current stream and ONE asynchronous copy of params + bit streams into a pinned
+    buffer on the copy stream, then assembles what an earlier ``submit`` left pending: batch i's files are written by the host while
+    batch i+1 is on the device.  ``finish(slot)`` waits for that batch's copy only; ``drain`` finishes what is pending.  On a CPU
+    tensor the fields are packed by ``grib2.pack_fields`` (the same contract in numpy) and everything else is the same code.
+
+    ``grid_lat`` / ``grid_lon``: the forecast grid, (H, W) or vectors; its place in the template's grid follows ``match_latlon``,
+    the points of the template outside it are absent in the bitmap."""
+
+    def __init__(self, settings: OutputSavingSettings, device: torch.device, grid_lat, grid_lon, template=None, slots: int = 2):
+        from . import grib2
+
+        self.settings, self.device, self.slots = settings, torch.device(device), slots
+        self.template = grib2.Template(settings.template_path) if template is None else template
+        self.grid_lat, self.grid_lon = np.asarray(grid_lat, dtype=np.float64), np.asarray(grid_lon, dtype=np.float64)
+        self.copy_stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
+        self._host: List[Optional[torch.Tensor]] = [None] * slots
+        self._dev: List[Optional[torch.Tensor]] = [None] * slots
+        self._done = [None] * slots
+        self._meta = [None] * slots
+        self._pending: List[int] = []
+        self._next = 0
+        self._plans: Dict[tuple, tuple] = {}
+        self.written: List[Path] = []          # every file written so far, in order
+
+    @classmethod
+    def for_dataset(cls, settings: OutputSavingSettings, infer_ds, device) -> Optional["ForecastGribWriter"]:
+        """The writer of an inference dataset, or None when something it needs is missing: the settings' template file (it must exist
+        and parse), ``infer_ds.sample_list`` (dates, terms, member) or ``infer_ds.grid`` (``lat``, ``lon``)."""
+        from . import grib2
+
+        grid = getattr(infer_ds, "grid", None)
+        if getattr(infer_ds, "sample_list", None) is None or getattr(grid, "lat", None) is None or getattr(grid, "lon", None) is None:
+            return None
+        if not settings.template_path.is_file():
+            return None
+        try:
+            template = grib2.Template(settings.template_path)
+        except (grib2.GribError, OSError):
+            return None
+        return cls(settings, device, grid.lat, grid.lon, template=template)
+
+    def _buffers(self, slot: int, nbytes: int):
+        if self._host[slot] is None or self._host[slot].numel() < nbytes:
+            self._host[slot] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            self._dev[slot] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._host[slot][:nbytes], self._dev[slot][:nbytes]
+
+    def _plan(self, names: tuple, H: int, W: int):
+        """(feature indices, template messages, (D, nbits) each, window, flip_rows) of a prediction with these feature names"""
+        from . import grib2
+
+        key = (names, H, W)
+        if key not in self._plans:
+            index, messages, spec = [], [], []
+            for f, name in enumerate(names):
+                fid, _ = grib_fid(name, 0)
+                if fid is None:
+                    continue
+                m = self.template.find(fid)
+                grib2.check_product(m)
+                index.append(f)
+                messages.append(m)
+                spec.append(grib2.spec_of(m))
+            window, flip = None, False
+            if messages:
+                if any(m.sections[3] != messages[0].sections[3] for m in messages):
+                    raise ValueError(f"{self.template.path}: the messages of the written features are not on one grid")
+                Ni, Nj, lat, lon, _ = grib2.grid_of(messages[0])
+                window = grib2.match_latlon(self.grid_lat, self.grid_lon, lat, lon)
+                if (window[1] - window[0] + 1, window[3] - window[2] + 1) != (H, W):
+                    raise ValueError("Lat/Lon dims of the dataset do not fit in template grid, cannot write grib.")
+                column = self.grid_lat[:, 0] if self.grid_lat.ndim == 2 else self.grid_lat.reshape(-1)
+                # the stream follows the template's rows: flipped when it runs north to south over a grid whose row 0 is the southern one
+                flip = bool(H > 1 and (column[-1] > column[0]) != (lat[-1] > lat[0]))
+            self._plans[key] = (tuple(index), messages, spec, window, flip)
+        return self._plans[key]
+
+    def submit(self, preds: NamedTensor, std: torch.Tensor, mean: torch.Tensor, samples: Sequence[Optional[GribSample]]) -> Optional[int]:
+        """preds: the NORMALISED prediction (B,T,H,W,F); ``samples[b]``: sample b's GribSample, or None when it is not written.
+        Returns the slot for ``finish``, or None when nothing is to be written (nothing is launched)."""
+        from . import grib2
+
+        accepted = [b for b, s in enumerate(samples) if s is not None]
+        earlier = list(self._pending)
+        slot = None
+        t = preds.tensor
+        H, W = (t.shape[2], t.shape[3]) if t.dim() == 5 else (1, t.shape[2])
+        index, messages, spec, window, flip = self._plan(tuple(preds.feature_names), H, W) if accepted else ((), [], [], None, False)
+        if accepted and index:
+            slot = self._next
+            self._next = (self._next + 1) % self.slots
+            if slot in self._pending:          # the rotation came round: its files are written before its buffers are reused
+                self.finish(slot)
+                earlier.remove(slot)
+            n, T, K, N = len(accepted), t.shape[1], len(index), H * W
+            pitch = ops.grib_pitch(N, spec)
+            pbytes = n * T * K * ops.GRIB_PARAMS * 4
+            if t.is_cuda:
+                host, dev = self._buffers(slot, pbytes + n * T * K * pitch)
+                out = (dev[:pbytes].view(torch.int32).view(n, T, K, ops.GRIB_PARAMS), dev[pbytes:].view(n, T, K, pitch))
+                ops.grib_pack(t, std, mean, spec, samples=accepted, features=index, flip_rows=flip, out=out)   # compute stream
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(self.copy_stream):
+                    self.copy_stream.wait_event(ready)
+                    host.copy_(dev, non_blocking=True)                                # one DMA: params and streams together
+                    done = torch.cuda.Event()
+                    done.record(self.copy_stream)
+                self._done[slot] = done
+                raw = host.numpy()
+                params, packed = raw[:pbytes].view(np.int32).reshape(n, T, K, ops.GRIB_PARAMS), raw[pbytes:].reshape(n, T, K, pitch)
+            else:
+                x = t.detach().float().reshape(t.shape[0], T, N, t.shape[-1]).numpy()
+                params, packed = grib2.pack_fields(x, std.detach().float().numpy(), mean.detach().float().numpy(), spec, accepted, index,
+                                                   H, W, flip, pitch)
+                self._done[slot] = None
+            self._meta[slot] = (params, packed, N, [samples[b] for b in accepted], [preds.feature_names[f] for f in index], messages,
+                                spec, window)
+            self._pending.append(slot)
+        for s in earlier:                      # the host writes the earlier batch while this one is on the device
+            self.finish(s)
+        return slot
+
+    def finish(self, slot: int) -> List[Path]:
+        import warnings
+
+        from . import grib2
+
+        if slot not in self._pending:
+            return []
+        if self._done[slot] is not None:
+            self._done[slot].synchronize()
+        self._pending.remove(slot)
+        params, packed, N, samples, names, messages, spec, window = self._meta[slot]
+        reals = params[..., :3].view(np.float32)
+        paths = []
+        for i, sample in enumerate(samples):
+            for t, term in enumerate(sample.terms):
+                path = self.settings.get_grib_path(sample.runtime, sample.member, int(term.total_seconds() / 60 ** 2))
+                with open(path, "wb") as f:
+                    for k, name in enumerate(names):
+                        if params[i, t, k, 4]:
+                            warnings.warn(f"{path}: {name} holds {int(params[i, t, k, 4])} values that are not finite; the field is not written")
+                            continue
+                        D, nbits = spec[k]
+                        f.write(grib2.encode(messages[k], sample.basis, term, cumulative=grib_fid(name, sample.time_step)[1], window=window,
+                                             packed=packed[i, t, k, :(N * nbits + 7) // 8].tobytes(), R=float(reals[i, t, k, 2]),
+                                             E=int(params[i, t, k, 3]), D=D, nbits=nbits))
                 paths.append(path)
         self.written.extend(paths)
         return paths

@@ -992,8 +992,8 @@ class Trainer:
         return self.callback_metrics
 
     def predict(self, module, dataloader: Iterable):
-        """``predict_step`` over the batches, in eval mode under no_grad; the module's forecast writer (``io_conf``: the GIFs of batch i
-        are encoded while batch i+1 is on the device) is drained at the end.  Returns the list of un-normalised predictions."""
+        """``predict_step`` over the batches, in eval mode under no_grad; the module's forecast writers (``io_conf``: the GIFs and GRIBs
+        of batch i are written while batch i+1 is on the device) are drained at the end.  Returns the list of un-normalised predictions."""
         module.trainer = self
         module.eval()
         predictions = []
@@ -1002,7 +1002,7 @@ class Trainer:
                 for i, batch in enumerate(dataloader):
                     predictions.append(module.predict_step(self._to_device(batch, self.device), i))
         finally:
-            writer = getattr(module, "forecast_writer", None)
-            if writer is not None:
-                writer.drain()
+            for writer in (getattr(module, "forecast_writer", None), getattr(module, "grib_writer", None)):
+                if writer is not None:
+                    writer.drain()
         return predictions
