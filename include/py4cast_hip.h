@@ -419,6 +419,53 @@ int p4c_grib_pack(const float* pred, int64_t pred_bs, int64_t pred_ts, const int
                   const int32_t* features, const int32_t* spec, int flip_rows, int32_t* params, unsigned char* packed, int64_t pitch,
                   void* workspace, int B, int n, int T, int H, int W, int F, int K, p4c_stream_t stream);
 
+/* Reading GRIB2 on the device: the decode of simple packing (data representation template 5.0), the other end of p4c_grib_pack.
+ * The bit streams (section 7) and bitmaps (section 6) of a batch lie in ONE device byte buffer as they are on disk; the message
+ * headers stay with the caller (py4cast_amd/grib2.py: field_of).
+ *
+ * p4c_grib_unpack: `nfields` fields, of any sizes, -> fp32 planes.  One field, N = ni*nj stream points:
+ *   stream point p is plane element (r, c) = (p / ni, p % ni), or (nj-1-r, c) with flip_rows: planes[dst_off + r*ni + c];
+ *   p is present when bitmap_off < 0, or when bit 7 - p%8 of octet bitmap_off + p/8 is 1 (most significant bit first);
+ *   the k-th present point takes X = the unsigned nbits-bit integer at bit k*nbits of the stream, most significant bit first
+ *   (nbits == 0: X = 0, the stream is not read);
+ *   in float64, one rounded operation each: t = R + ldexp(X, E); y = t / 10^D (D >= 0) or t * 10^-D; the plane gets (float)y.
+ *   An absent point is NaN; so is a present point of rank >= count.  No byte outside [stream_off, stream_off + stream_len) and
+ *   the ceil(N/8) bitmap bytes is read; nothing outside [dst_off, dst_off + N) is written.
+ * Launches: when a field has a bitmap, a count launch (population of the bitmap per tile -> `workspace`,
+ * p4c_grib_unpack_workspace_bytes(tiles) bytes) and the unpack launch, in which a workgroup adds up the counts of the field's
+ * earlier tiles; without any bitmap one launch, and `workspace` may be null.  No atomics: two calls give the same bits.
+ * `fields` is the table in DEVICE memory, `fields_host` the same table in host memory, which the checks read.
+ * Errors (nothing is launched): a null pointer; `bytes` not 4-byte aligned; nfields < 1; ni or nj < 1; more than 2^31 - 1 points
+ * in a field or tiles in the call; nbits outside 0 .. 32; |D| > 15; count < 0 or > ni*nj; no bitmap and count != ni*nj;
+ * stream_len < ceil(count*nbits/8); a stream or a bitmap that does not lie inside [0, nbytes); stream_off, bitmap_off or dst_off
+ * that is negative (bitmap_off: other than -1) or no multiple of 4; tile0 that is not the running sum of ceil(ni*nj / tile).
+ *
+ * p4c_grib_unpack_tile / p4c_grib_unpack_max_blocks: points per loop trip of a workgroup / the most workgroups of one launch: a
+ * workgroup takes ceil(tiles / max_blocks) consecutive tiles of the call.
+ * p4c_grib_unpack_fast(nbits, has_bitmap): 1 when such a field takes the specialised path (16 bits without bitmap: one 16-byte
+ * load per lane), 0 for the generic one. */
+typedef struct p4c_grib_field {
+    int64_t stream_off; /* byte offset of the section-7 payload in `bytes`, a multiple of 4 */
+    int64_t stream_len; /* its length in bytes, >= ceil(count*nbits/8) */
+    int64_t bitmap_off; /* byte offset of the section-6 bitmap, a multiple of 4; -1: every point present */
+    int64_t dst_off;    /* offset in floats of the field's plane in `planes`, a multiple of 4 */
+    int32_t ni, nj;     /* stream row length and number of rows */
+    int32_t count;      /* number of packed values (section 5 octets 6-9) */
+    int32_t nbits;      /* 0 .. 32 */
+    int32_t E, D;       /* binary and decimal scale factors */
+    float R;            /* reference value */
+    int32_t flip_rows;  /* 1: stream row r goes to plane row nj-1-r */
+    int32_t tile0;      /* index of the field's first tile among all tiles of the call */
+    int32_t pad;
+} p4c_grib_field;
+
+int p4c_grib_unpack_tile(void);
+int p4c_grib_unpack_max_blocks(void);
+int p4c_grib_unpack_fast(int nbits, int has_bitmap);
+size_t p4c_grib_unpack_workspace_bytes(int64_t tiles);
+int p4c_grib_unpack(const unsigned char* bytes, int64_t nbytes, const p4c_grib_field* fields, const p4c_grib_field* fields_host,
+                    int nfields, float* planes, void* workspace, p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

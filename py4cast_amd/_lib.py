@@ -65,6 +65,8 @@ SIGNATURES = {
     "p4c_forecast_frames": [P, L, L, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, P],
     # pred, bs, ts, samples (host), std, mean, features, spec (host), flip_rows, params, packed, pitch, ws, B, n, T, H, W, F, K, stream
     "p4c_grib_pack": [P, L, L, P, P, P, P, P, I, P, P, L, P, I, I, I, I, I, I, I, P],
+    # bytes, nbytes, fields (device), fields (host), nfields, planes, ws, stream
+    "p4c_grib_unpack": [P, L, P, P, I, P, P, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],
@@ -118,6 +120,10 @@ OTHER = {
     "p4c_grib_max_features": ([], c_int),
     "p4c_grib_max_samples": ([], c_int),
     "p4c_grib_pack_dense": ([I, I], c_int),
+    "p4c_grib_unpack_tile": ([], c_int),
+    "p4c_grib_unpack_max_blocks": ([], c_int),
+    "p4c_grib_unpack_fast": ([I, I], c_int),
+    "p4c_grib_unpack_workspace_bytes": ([L], c_size_t),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

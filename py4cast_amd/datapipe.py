@@ -84,7 +84,8 @@ def load_native_batch(groups, io_names: List[str], forcing: NamedTensor, stats, 
         if plan.key not in keys:
             keys[plan.key] = len(plans)
             plans.append(plan)
-        src, window = regrid.blurred(raw.contiguous().float(), plan)
+        raw = raw.float()
+        src, window = regrid.blurred(raw if ops.planes_dense(raw) else raw.contiguous(), plan)     # planes at a pitch stay where they are
         sources.append(src)
         windows.append(window)
         src_bytes += regrid.source_bytes(plan, len(names) * B * T)

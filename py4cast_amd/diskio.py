@@ -10,10 +10,13 @@ On-disk formats either side of the hot path, host side.
 * Statistics files: ``parameters_stats.pt`` / ``diff_stats.pt`` = ``torch.save`` of ``{name: {"mean","std","min","max": 0-d
   tensor}}`` (datasets/compute_dataset_stats.py:71-127, read by ``Stats`` at datasets/access.py:355-390, written by the dummy
   dataset at datasets/dummy.py:24-42).
+* Titan's GRIB layout (``file_format="grib"``, the reference's default: datasets/titan/__init__.py:112-152): ``GribPlaneReader``
+  ships the packed bit streams of a batch as they lie in the files and ``ops.grib_unpack`` decodes them on the device.
 """
 
 import datetime as dt
 import os
+from collections import OrderedDict
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -131,3 +134,159 @@ def load_titan_batch(dataset_path, params: List[Tuple[str, int, str]], dates: Li
     raw = reader.read(paths)
     names = [f"{n}_{lv}{'m' if lt in ('surface', 'heightAboveGround') else 'hpa'}" for (n, lv, lt) in params]
     return datapipe.load_batch(raw, names, forcing, stats, num_input_steps, standardize)
+
+
+# ------------------------------------------------------------------------------------------ GRIB2 files
+def titan_grib_path(dataset_path, grib_name: str, date: dt.datetime) -> Path:
+    """datasets/titan/__init__.py:93-109 (grib branch): ``<dataset>/grib/<date>/<grib_name>``."""
+    return Path(dataset_path) / "grib" / date.strftime(TITAN_FORMATSTR) / grib_name
+
+
+class GribPlaneReader:
+    """Reads (F, B, T) fields out of GRIB2 files and returns ``(planes (F, B, T, Nj, Ni) fp32, lat (Nj,), lon (Ni,))``.
+
+    On a device the packed bit streams and bitmaps of all selected messages are copied, as they lie in the files, into one pinned
+    byte buffer at 4-byte aligned offsets (grown when needed; a message selected twice is copied once), shipped in one non-blocking
+    copy on a copy stream and decoded by ``ops.grib_unpack``: no value is computed on the host.  With ``device=None`` the planes are
+    ``grib2.unpack_fields`` of the same fields, on the host.  An absent point (bitmap) is NaN.
+
+    Plane row 0 is the NORTHERNMOST row and ``lat`` descends, whichever way the file scans: a file whose rows run south to north
+    (scanning-mode bit 0x40) is flipped while it is decoded (``flip_rows``).  This is a deliberate difference from the reference,
+    which flips unconditionally after ``fit_to_grid`` (datasets/titan/__init__.py:211-226) and would turn such a file upside down;
+    ``datapipe.load_native_batch`` applies that flip to north-first planes.
+
+    Messages are selected by the numeric keys of ``grib2.MATCHED_KEYS`` (``outputs.grib_fid``), not by ``shortName``.  All fields of
+    one call must lie on one grid.  ``cache``: how many parsed files are kept (the reference's ``read_grib`` keeps 50)."""
+
+    def __init__(self, device=None, pin: Optional[bool] = None, cache: int = 50):
+        self.device = device
+        self.cuda = device is not None and torch.device(device).type == "cuda"
+        self.pin = (torch.cuda.is_available() and self.cuda) if pin is None else pin
+        self.cache = int(cache)
+        self.files: "OrderedDict[str, object]" = OrderedDict()
+        self.host: Optional[torch.Tensor] = None
+        self.copy_stream = torch.cuda.Stream(device) if self.cuda else None
+        self._copied = None     # the event behind the last copy out of ``host``
+        self.parsed = 0         # files parsed so far (a cache hit does not count)
+
+    def file(self, path):
+        from . import grib2
+
+        key = str(path)
+        if key in self.files:
+            self.files.move_to_end(key)
+            return self.files[key]
+        f = grib2.GribFile(path)
+        self.parsed += 1
+        self.files[key] = f
+        while len(self.files) > max(self.cache, 1):
+            self.files.popitem(last=False)
+        return f
+
+    def _select(self, selections):
+        from . import grib2
+
+        F = len(selections)
+        B = len(selections[0]) if F else 0
+        T = len(selections[0][0]) if B else 0
+        if not F or not B or not T or any(len(sb) != B or any(len(st) != T for st in sb) for sb in selections):
+            raise ValueError("GribPlaneReader: expected selections[F][B][T] of (path, fid), none of the three empty")
+        chosen, grid, first = [], None, None
+        for sf in selections:
+            for sb in sf:
+                for path, fid in sb:
+                    m, field = self.file(path).field(fid)
+                    ni, nj, lat, lon, _ = grib2.grid_of(m)
+                    lat = lat[::-1] if field.south_to_north else lat
+                    if grid is None:
+                        grid, first = (ni, nj, lat, lon), path
+                    elif (ni, nj) != grid[:2] or not (np.array_equal(np.round(lat, 5), np.round(grid[2], 5))
+                                                      and np.array_equal(np.round(lon, 5), np.round(grid[3], 5))):
+                        raise ValueError(f"GribPlaneReader: {path} is on a grid of {nj} x {ni} from ({lat[0]:.5f}, {lon[0]:.5f}), {first} on "
+                                         f"{grid[1]} x {grid[0]} from ({grid[2][0]:.5f}, {grid[3][0]:.5f}): one call reads one grid")
+                    chosen.append((str(path), m, field))
+        return (F, B, T), chosen, grid
+
+    def read(self, selections: Sequence[Sequence[Sequence]]):
+        """selections[f][b][t] = (path, fid) -> (planes (F, B, T, Nj, Ni), lat (Nj,) descending, lon (Ni,)): planes on ``device``, or a
+        host tensor when it is None.  On a device every plane is dense and starts at a multiple of 4 floats (16-byte stores): where
+        Nj * Ni is no multiple of 4 the tensor is a view with that pitch between planes, not contiguous."""
+        from . import grib2, ops
+
+        (F, B, T), chosen, (ni, nj, lat, lon) = self._select(selections)
+        if not self.cuda:
+            planes = grib2.unpack_fields([f for _, _, f in chosen], flip=[f.south_to_north for _, _, f in chosen])
+            host = torch.from_numpy(np.stack(planes).reshape(F, B, T, nj, ni))
+            return (host if self.device is None else host.to(self.device)), lat.copy(), lon.copy()
+        # where every distinct message's stream and bitmap go in the byte buffer
+        place, at = {}, 0
+        for path, m, f in chosen:
+            if (path, id(m)) not in place:
+                s_off, at = at, at + (len(f.stream) + 3) // 4 * 4
+                b_off = -1
+                if f.bitmap is not None:
+                    b_off, at = at, at + (len(f.bitmap) + 3) // 4 * 4
+                place[path, id(m)] = (s_off, b_off, f)
+        if self._copied is not None:
+            self._copied.synchronize()          # the last call's copy has left the buffer
+        if self.host is None or self.host.numel() < at:
+            self.host = torch.empty(max(at, 4), dtype=torch.uint8, pin_memory=self.pin)
+        buf = self.host.numpy()
+        for s_off, b_off, f in place.values():
+            buf[s_off:s_off + len(f.stream)] = np.frombuffer(f.stream, dtype=np.uint8)
+            if b_off >= 0:
+                buf[b_off:b_off + len(f.bitmap)] = np.frombuffer(f.bitmap, dtype=np.uint8)
+        N = ni * nj
+        pitch = (N + 3) // 4 * 4
+        table = np.zeros(len(chosen), dtype=ops.GRIB_FIELD)
+        for i, (path, m, f) in enumerate(chosen):
+            s_off, b_off, _ = place[path, id(m)]
+            table[i] = (s_off, len(f.stream), b_off, i * pitch, f.ni, f.nj, f.count, f.nbits, f.E, f.D, f.R, int(f.south_to_north), 0, 0)
+        current = torch.cuda.current_stream(self.device)
+        self.copy_stream.wait_stream(current)
+        with torch.cuda.stream(self.copy_stream):
+            dev = self.host[:max(at, 4)].to(self.device, non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record(self.copy_stream)
+        current.wait_stream(self.copy_stream)      # the unpack launch runs after the transfer
+        dev.record_stream(current)
+        with torch.cuda.device(dev.device):
+            flat = ops.grib_unpack(dev, table, out=torch.empty(len(chosen) * pitch, dtype=torch.float32, device=dev.device))
+        # no copy: where Nj * Ni is no multiple of 4 the planes keep their pitch (dense planes, which load_native_batch takes as they are)
+        planes = flat.as_strided((F, B, T, nj, ni), (B * T * pitch, T * pitch, pitch, ni, 1))
+        return planes, lat.copy(), lon.copy()
+
+
+def load_titan_grib_batch(dataset_path, params: List[Tuple[str, str, dict, str]], dates: List[List[dt.datetime]], stats: Stats,
+                          num_input_steps: int, forcing, plans: Dict[str, object], reader: Optional[GribPlaneReader] = None, device=None,
+                          standardize: bool = True):
+    """``load_titan_batch`` for Titan's GRIB layout (``file_format="grib"``, the reference's default): one ``GribPlaneReader`` call per
+    native grid, then ``datapipe.load_native_batch`` (fit_to_grid, the latitude flip, the sub-domain, the standardisation and the
+    pack in one launch).  params: (feature name, grib_name, fid, native grid name), ``fid`` the numeric keys of the message
+    (``outputs.grib_fid``); dates[b][t]: validity times of sample b; plans: native grid name -> ``regrid.RegridPlan``.  Returns the
+    ItemBatch of ``load_titan_batch`` on the reader's device.  There is no host path: the regrid runs on the device only."""
+    from . import datapipe
+
+    if not params:
+        raise ValueError("load_titan_grib_batch: no parameters")
+    if not dates or not dates[0] or any(len(d) != len(dates[0]) for d in dates):
+        raise ValueError("load_titan_grib_batch: dates[b][t] must have the same, non-zero number of steps for every sample")
+    names = [p[0] for p in params]
+    if len(set(names)) != len(names):
+        raise ValueError(f"load_titan_grib_batch: feature names {sorted(n for n in set(names) if names.count(n) > 1)} appear twice")
+    missing = sorted({p[3] for p in params} - set(plans))
+    if missing:
+        raise ValueError(f"load_titan_grib_batch: no plan for the native grids {missing}")
+    if not 0 < num_input_steps <= len(dates[0]):
+        raise ValueError(f"load_titan_grib_batch: {num_input_steps} input steps of {len(dates[0])} dates")
+    if reader is None:
+        reader = GribPlaneReader(device=device)
+    if not reader.cuda:
+        raise ValueError("load_titan_grib_batch: a CUDA device (or a reader on one) is needed: the regrid has no host path")
+    groups = []
+    for grid in dict.fromkeys(p[3] for p in params):          # the grids in the order of their first parameter
+        mine = [p for p in params if p[3] == grid]
+        selections = [[[(titan_grib_path(dataset_path, grib_name, d), fid) for d in sample] for sample in dates] for (_, grib_name, fid, _) in mine]
+        planes, _, _ = reader.read(selections)
+        groups.append((planes, [p[0] for p in mine], plans[grid]))
+    return datapipe.load_native_batch(groups, names, forcing, stats, num_input_steps, standardize)

@@ -34,10 +34,16 @@ direction), 0x20 (adjacent points consecutive in j) and 0x10 (alternate rows rev
 in section 4; a product template other than 4.0 / 4.8; more than one time range; a data representation template other than 5.0,
 5.2, 5.3, 5.40, 5.41 as the source of D and nbits (these share octets 18-19 and 20); anything but 5.0 on decoding; a message with
 repeated sections.  Scanning-mode bit 0x40 (rows run south to north) is honoured.
+
+Reading (``diskio.GribPlaneReader``): ``GribFile`` indexes a file, ``field_of`` hands out a message's packed stream and bitmap as
+they lie in it, ``ops.grib_unpack`` (csrc/grib_unpack.hip) decodes a batch of them on the device and ``unpack_fields`` in numpy.
+Only simple packing (5.0) is decoded; 5.2, 5.3, 5.40, 5.41 and 5.42 are out of scope and refused.  Messages are found by the numeric
+keys above, never by ``shortName``.
 """
 import datetime as dt
 import math
 import struct
+from dataclasses import dataclass
 from functools import lru_cache
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -226,6 +232,19 @@ def grid_of(m: Message):
     return k["Ni"], k["Nj"], lat, lon, k["scanningMode"]
 
 
+def find_message(messages: Sequence[Message], fid: dict, where) -> Message:
+    """The first of ``messages`` whose keys equal those of ``fid``: MATCHED_KEYS are compared, IGNORED_KEYS are not, any other key is
+    refused.  ``where`` names the file in the KeyError."""
+    unknown = sorted(set(fid) - set(MATCHED_KEYS) - set(IGNORED_KEYS))
+    if unknown:
+        raise GribError(f"keys {unknown} are not matched")
+    wanted = {k: v for k, v in fid.items() if k in MATCHED_KEYS}
+    for m in messages:
+        if all(k in m.keys and m.keys[k] == v for k, v in wanted.items()):
+            return m
+    raise KeyError(f"{where}: no message with {wanted}")
+
+
 class Template:
     """The messages of a template GRIB2 file; every one of them must be on a grid this module writes on."""
 
@@ -239,14 +258,7 @@ class Template:
 
     def find(self, fid: dict) -> Message:
         """The first message whose keys equal those of ``fid`` (module docstring: which are compared, which ignored)."""
-        unknown = sorted(set(fid) - set(MATCHED_KEYS) - set(IGNORED_KEYS))
-        if unknown:
-            raise GribError(f"keys {unknown} are not matched")
-        wanted = {k: v for k, v in fid.items() if k in MATCHED_KEYS}
-        for m in self.messages:
-            if all(k in m.keys and m.keys[k] == v for k, v in wanted.items()):
-                return m
-        raise KeyError(f"{self.path}: no message with {wanted}")
+        return find_message(self.messages, fid, self.path)
 
     def grid(self, message: Optional[Message] = None):
         return grid_of(self.messages[0] if message is None else message)
@@ -375,6 +387,124 @@ def decode(message) -> Tuple[np.ma.MaskedArray, dict]:
     scaled = float(k["referenceValue"]) + np.ldexp(X, k["binaryScaleFactor"])
     values[present] = scaled / float(10 ** D) if D >= 0 else scaled * float(10 ** -D)
     return np.ma.MaskedArray(values.reshape(Nj, Ni), mask=~present.reshape(Nj, Ni)), k
+
+
+# ------------------------------------------------------------------------------------------------ reading: the host side
+# Reading keeps the numeric work off the host: ``field_of`` hands out the packed stream and the bitmap of a message as they lie in
+# the file, ``ops.grib_unpack`` (csrc/grib_unpack.hip) decodes a whole batch of them on the device, ``unpack_fields`` does the
+# same in numpy.  Messages are found by the numeric MATCHED_KEYS only: ``shortName``, which the reference selects by, comes from
+# eccodes' tables and is not in a message (``outputs.grib_fid`` gives the numeric keys of the Titan features).
+@dataclass(frozen=True)
+class PackedField:
+    """What the decoder needs of one simple-packed message; ``stream`` (section 7 from octet 6) and ``bitmap`` (section 6 from
+    octet 7, None without one) are memoryviews into the message's sections, not copies."""
+    stream: memoryview
+    bitmap: Optional[memoryview]
+    ni: int
+    nj: int
+    count: int
+    nbits: int
+    R: float
+    E: int
+    D: int
+    scanning_mode: int
+
+    @property
+    def south_to_north(self) -> bool:
+        return bool(self.scanning_mode & 0x40)
+
+
+def field_of(message) -> PackedField:
+    """The packed field of a message on a 3.0 grid.  Refused, each with its octet: everything ``check_grid`` refuses; a data
+    representation template other than 5.0 (5.2, 5.3, 5.40, 5.41, 5.42 are out of scope); a bitmap indicator other than 0 or 255;
+    nbits > 32; |D| > 15; a bitmap shorter than the grid or whose population differs from the number of packed values; without a
+    bitmap, a number of values other than the number of points; a section 7 shorter than ceil(count * nbits / 8)."""
+    m = message if isinstance(message, Message) else Message(message)
+    check_grid(m)
+    k = m.keys
+    number = k["dataRepresentationTemplateNumber"]
+    if number != 0 or len(m.sections[5]) < 20:
+        raise GribError(f"section 5 octets 10-11: data representation template 5.{number}; only 5.0 (simple packing) is decoded, "
+                        f"5.2, 5.3, 5.40, 5.41 and 5.42 are out of scope")
+    ni, nj, count, nbits, D = k["Ni"], k["Nj"], k["numberOfValues"], k["bitsPerValue"], k["decimalScaleFactor"]
+    if nbits > 32:
+        raise GribError(f"section 5 octet 20: {nbits} bits per value; 0 .. 32 are decoded")
+    if abs(D) > MAX_D:
+        raise GribError(f"section 5 octets 18-19: D = {D}; |D| <= {MAX_D} is decoded")
+    points = ni * nj
+    s6, s7 = m.sections[6], m.sections[7]
+    bitmap = None
+    if k["bitMapIndicator"] == 0:
+        need = (points + 7) // 8
+        if len(s6) - 6 < need:
+            raise GribError(f"section 6 octets 1-4: a bitmap of {len(s6) - 6} octets for {points} points")
+        bitmap = memoryview(s6)[6:6 + need]
+        present = (int.from_bytes(bitmap, "big") >> (8 * need - points)).bit_count()
+        if present != count:
+            raise GribError(f"section 5 octets 6-9: {count} values for {present} points present in the bitmap")
+    elif k["bitMapIndicator"] == 255:
+        if count != points:
+            raise GribError(f"section 5 octets 6-9: {count} values for {points} points and no bitmap")
+    else:
+        raise GribError(f"section 6 octet 6: bitmap indicator {k['bitMapIndicator']}; 0 (a bitmap follows) and 255 (none) are read")
+    if len(s7) - 5 < (count * nbits + 7) // 8:
+        raise GribError(f"section 7 octets 1-4: {len(s7) - 5} octets of data for {count} values of {nbits} bits")
+    return PackedField(memoryview(s7)[5:], bitmap, ni, nj, count, nbits, float(k["referenceValue"]), k["binaryScaleFactor"], D,
+                       k["scanningMode"])
+
+
+def unpack_fields(fields: Sequence[PackedField], flip=False) -> List[np.ndarray]:
+    """The contract of csrc/grib_unpack.hip in numpy -> one (nj, ni) float32 plane per field.  The k-th present point takes the k-th
+    value X of the stream; Y = (R + ldexp(X, E)) / 10^D (``* 10^-D`` for D < 0) in float64, rounded to float32; an absent point, and
+    a present one of rank >= count, is NaN.  ``flip`` (one bool, or one per field): stream row r becomes plane row nj-1-r."""
+    flips = [bool(flip)] * len(fields) if isinstance(flip, (bool, np.bool_)) else [bool(f) for f in flip]
+    if len(flips) != len(fields):
+        raise ValueError(f"{len(flips)} flip flags for {len(fields)} fields")
+    out = []
+    for f, fl in zip(fields, flips):
+        points = f.ni * f.nj
+        if f.bitmap is None:
+            present = np.ones(points, dtype=bool)
+        else:
+            present = np.unpackbits(np.frombuffer(f.bitmap, dtype=np.uint8), count=points).astype(bool)
+        where = np.flatnonzero(present)[:f.count]           # ranks past count stay NaN
+        n = min(f.count, where.size)
+        X = unpack_bits(bytes(f.stream[:(n * f.nbits + 7) // 8]), n, f.nbits).astype(np.float64) if f.nbits and n else np.zeros(n)
+        with np.errstate(all="ignore"):
+            scaled = float(f.R) + np.ldexp(X, f.E)
+            y = scaled / float(10 ** f.D) if f.D >= 0 else scaled * float(10 ** -f.D)
+            plane = np.full(points, np.nan, dtype=np.float32)
+            plane[where[:n]] = y.astype(np.float32)
+        plane = plane.reshape(f.nj, f.ni)
+        out.append(np.ascontiguousarray(plane[::-1]) if fl else plane)
+    return out
+
+
+class GribFile:
+    """An index over the messages of one GRIB2 file for reading: ``find(fid)`` matches as ``Template.find`` does (numeric
+    MATCHED_KEYS only, no ``shortName``), ``field(fid)`` is ``field_of`` of that message, parsed once."""
+
+    def __init__(self, path):
+        self.path = path
+        self.messages = read_messages(path)
+        if not self.messages:
+            raise GribError(f"{path}: no GRIB2 message")
+        self._fields: Dict[int, PackedField] = {}
+
+    def find(self, fid: dict) -> Message:
+        if not set(fid) - set(IGNORED_KEYS):
+            raise GribError(f"{self.path}: keys {sorted(fid)} hold none of {MATCHED_KEYS}: matching by shortName (eccodes' tables) is "
+                            f"out of scope, messages are found by their numeric keys")
+        return find_message(self.messages, fid, self.path)
+
+    def field(self, fid: dict) -> Tuple[Message, PackedField]:
+        m = self.find(fid)
+        if id(m) not in self._fields:
+            try:
+                self._fields[id(m)] = field_of(m)
+            except GribError as e:
+                raise GribError(f"{self.path}: {e}") from None
+        return m, self._fields[id(m)]
 
 
 # ------------------------------------------------------------------------------------------------ the packer on the CPU

@@ -542,11 +542,16 @@ REGRID_FEATURE = np.dtype([("src", "<u8"), ("b_stride", "<i8"), ("t_stride", "<i
 REGRID_MAX_FEATURES = 144
 
 
+def planes_dense(t: torch.Tensor) -> bool:
+    """every (H, W) plane of ``t`` (..., H, W) is dense; the strides of the leading dimensions are free (planes at a pitch)"""
+    return t.is_contiguous() or (t.dim() >= 2 and t.stride(-1) == 1 and t.stride(-2) == t.shape[-1])
+
+
 def regrid_features(sources, feats, table_dims, B: int, T: int) -> torch.Tensor:
     """The device descriptors (p4c_regrid_feature) of ``regrid_pack``, checked on the host: everything the kernel will index lies
     inside its plane, and the output channels are 0 .. F-1, each once.
 
-    sources: device tensors (Fg, B, T, Hs, Ws) fp32, dense.  feats: one tuple per output feature, (index into sources, plane of
+    sources: device tensors (Fg, B, T, Hs, Ws) fp32, every plane dense (``planes_dense``: the planes may lie at a pitch).  feats: one tuple per output feature, (index into sources, plane of
     that source, window row origin, window column origin, tap table, mean, std, output channel).  table_dims: per tap table the
     (rows, columns) of the windowed source it indexes.  The result holds raw pointers into ``sources``: keep them alive."""
     L.require_cuda(*sources)
@@ -555,7 +560,7 @@ def regrid_features(sources, feats, table_dims, B: int, T: int) -> torch.Tensor:
         raise L.P4CError(f"regrid_pack: {F} features: 1 .. at most {REGRID_MAX_FEATURES} per call (LDS tile)")
     dev = sources[0].device
     for s in sources:
-        if s.dim() != 5 or tuple(s.shape[1:3]) != (B, T) or s.dtype != torch.float32 or not s.is_contiguous() or s.device != dev:
+        if s.dim() != 5 or tuple(s.shape[1:3]) != (B, T) or s.dtype != torch.float32 or not planes_dense(s) or s.device != dev:
             raise L.P4CError(f"regrid_pack: source {tuple(s.shape)} {s.dtype} is not a dense fp32 (Fg, {B}, {T}, Hs, Ws) on {dev}")
     if sorted(f[7] for f in feats) != list(range(F)):
         raise L.P4CError(f"regrid_pack: the output channels {sorted(f[7] for f in feats)} are not 0 .. {F - 1}, each once")
@@ -878,3 +883,79 @@ def grib_pack(pred, std, mean, spec, samples=None, features=None, flip_rows=Fals
            L.ptr(params), L.ptr(packed), pitch, L.ptr(ws), B, n, T, H, W, F, K, L.stream(dev),
            alg_bytes=n * T * (N * 2 * per_point + sum((N * nbits + 7) // 8 for _, nbits in spec)))
     return params, packed
+
+
+# ------------------------------------------------------------------------------------------------ GRIB2 simple packing, decoded
+# launch constants of csrc/grib_unpack.hip (p4c_grib_unpack_tile() / p4c_grib_unpack_max_blocks() report the same)
+GRIB_UNPACK_TILE = 2048        # points per loop trip of a workgroup, 8 per lane
+GRIB_UNPACK_MAX_BLOCKS = 2048  # the most workgroups of one launch: each takes ceil(tiles / this) consecutive tiles of the call
+# host mirror of p4c_grib_field (include/py4cast_hip.h)
+GRIB_FIELD = np.dtype([("stream_off", "<i8"), ("stream_len", "<i8"), ("bitmap_off", "<i8"), ("dst_off", "<i8"), ("ni", "<i4"), ("nj", "<i4"),
+                       ("count", "<i4"), ("nbits", "<i4"), ("E", "<i4"), ("D", "<i4"), ("R", "<f4"), ("flip_rows", "<i4"), ("tile0", "<i4"),
+                       ("pad", "<i4")])
+
+
+def grib_fields(records) -> np.ndarray:
+    """A GRIB_FIELD table from a sequence of mappings with its column names; ``bitmap_off`` defaults to -1 (no bitmap), ``flip_rows``
+    and ``dst_off`` to 0.  A GRIB_FIELD array is copied."""
+    if isinstance(records, np.ndarray):
+        if records.dtype != GRIB_FIELD:
+            raise L.P4CError(f"grib_unpack: a table of dtype {records.dtype}, GRIB_FIELD expected")
+        return records.reshape(-1).copy()
+    table = np.zeros(len(records), dtype=GRIB_FIELD)
+    table["bitmap_off"] = -1
+    for i, rec in enumerate(records):
+        for name, value in rec.items():
+            if name not in GRIB_FIELD.names:
+                raise L.P4CError(f"grib_unpack: field {i}: {name!r} is no column of GRIB_FIELD")
+            table[i][name] = value
+    return table
+
+
+def grib_table(fields, dense: bool) -> np.ndarray:
+    """The table ``grib_unpack`` launches with: ``grib_fields(fields)`` with ``tile0`` filled in and, with ``dense``, ``dst_off`` too:
+    the planes one after the other in the order of the table, each at a multiple of 4 floats."""
+    table = grib_fields(fields)
+    if table.size < 1:
+        raise L.P4CError("grib_unpack: no fields")
+    points = table["ni"].astype(np.int64) * table["nj"].astype(np.int64)
+    if points.min() < 1 or points.max() >= 2 ** 31:
+        raise L.P4CError(f"grib_unpack: fields of {points.min()} .. {points.max()} points: 1 .. 2^31 - 1 expected")
+    tiles = (points + GRIB_UNPACK_TILE - 1) // GRIB_UNPACK_TILE
+    if int(tiles.sum()) >= 2 ** 31:
+        raise L.P4CError(f"grib_unpack: {int(tiles.sum())} tiles: fewer than 2^31 per call")
+    table["tile0"] = np.cumsum(tiles) - tiles
+    if dense:
+        padded = (points + 3) // 4 * 4
+        table["dst_off"] = np.cumsum(padded) - padded
+    return table
+
+
+def grib_unpack(bytes_dev: torch.Tensor, fields, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The simple-packed (5.0) bit streams and bitmaps of GRIB2 fields, lying in the device byte buffer ``bytes_dev`` (uint8, dense,
+    4-byte aligned) as they do in the files -> their fp32 planes in one flat device tensor (p4c_grib_unpack; the contract is in
+    include/py4cast_hip.h and, in numpy, ``grib2.unpack_fields``).  ``fields``: a GRIB_FIELD array or a sequence of mappings
+    (``grib_fields``); ``tile0`` is filled in here.  Without ``out`` the planes lie one after the other in the order of the table,
+    each at a multiple of 4 floats (``grib_table(fields, dense=True)`` tells where); with ``out`` (flat fp32, dense) each plane goes to
+    its ``dst_off`` and nothing else is written.  Returns ``out``.  The records are checked by the library, not here.  Not
+    differentiable."""
+    L.require_cuda(bytes_dev, out)
+    if bytes_dev.dtype != torch.uint8 or bytes_dev.dim() != 1 or not bytes_dev.is_contiguous() or bytes_dev.data_ptr() % 4:
+        raise L.P4CError(f"grib_unpack: bytes {tuple(bytes_dev.shape)} {bytes_dev.dtype}: a dense, 4-byte aligned 1-D uint8 tensor expected")
+    table = grib_table(fields, dense=out is None)
+    points = table["ni"].astype(np.int64) * table["nj"].astype(np.int64)
+    total = int(((points + GRIB_UNPACK_TILE - 1) // GRIB_UNPACK_TILE).sum())
+    dev = bytes_dev.device
+    if out is None:
+        out = torch.empty(int(((points + 3) // 4 * 4).sum()), dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous() or out.device != dev
+          or int((table["dst_off"] + points).max()) > out.numel() or int(table["dst_off"].min()) < 0):
+        raise L.P4CError(f"grib_unpack: out {tuple(out.shape)} {out.dtype} on {out.device}: a dense 1-D fp32 tensor on {dev} that holds "
+                         f"every plane at its dst_off expected")
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+    has_bitmap = bool((table["bitmap_off"] >= 0).any())
+    ws = torch.empty(L.lib().p4c_grib_unpack_workspace_bytes(total) // 4, dtype=torch.int32, device=dev) if has_bitmap else None
+    read = int(((table["count"].astype(np.int64) * table["nbits"] + 7) // 8).sum() + ((points + 7) // 8)[table["bitmap_off"] >= 0].sum())
+    L.call("p4c_grib_unpack", L.ptr(bytes_dev), bytes_dev.numel(), L.ptr(table_dev), ctypes.c_void_p(table.ctypes.data), int(table.size),
+           L.ptr(out), L.ptr(ws), L.stream(dev), alg_bytes=read + 4 * int(points.sum()))
+    return out
