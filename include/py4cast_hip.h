@@ -466,6 +466,71 @@ size_t p4c_grib_unpack_workspace_bytes(int64_t tiles);
 int p4c_grib_unpack(const unsigned char* bytes, int64_t nbytes, const p4c_grib_field* fields, const p4c_grib_field* fields_host,
                     int nfields, float* planes, void* workspace, p4c_stream_t stream);
 
+/* Complex packing (data representation templates 5.2 and 5.3, general group splitting, no missing-value management), decoded on
+ * the device beside p4c_grib_unpack.  The section-7 payload of a field holds, each zero-padded to an octet: the descriptors (5.3
+ * only: ival1, ival2 at order 2, gmin; nbytes octets each, sign and magnitude -- the HOST parses them into the record), ng group
+ * references of ref_bits bits, ng widths of w_bits bits, ng scaled lengths of l_bits bits, then the values in group order with no
+ * padding between groups.  A table of 0 bits is absent and its entries are 0.
+ *
+ * p4c_grib_unpack_complex: `nfields` fields, of any sizes, -> fp32 planes and one status word per field.  One field:
+ *   width[g] = w_ref + w[g];  len[g] = l_ref + l_inc * l[g], len[ng-1] = l_last whatever its stored length says;
+ *   value k lies in group g: X[k] = ref[g] + its width[g]-bit integer (0 at width 0);
+ *   order 0 (5.2): f = X;  order 1: f[0] = ival1, f[k] = f[k-1] + X[k] + gmin;  order 2: f[0] = ival1, f[1] = ival2,
+ *   f[k] = X[k] + gmin + 2 f[k-1] - f[k-2] (the first `order` X are placeholders);  all modulo 2^64, f read as a signed 64-bit integer;
+ *   in float64, one rounded operation each: t = R + ldexp((double)f, E); y = t / 10^D (D >= 0) or t * 10^-D; the plane gets (float)y;
+ *   stream points, the bitmap, the rank of a point, flip_rows and dst_off as in p4c_grib_unpack: the k-th present point takes f[k];
+ *   an absent point is NaN, so is a present point of rank >= count.
+ * status[i] (device, int32, written for every field), an OR of: 1 the group lengths do not sum to count; 2 a group width above
+ * 32; 4 the values need more bits than the stream holds.  A field whose status is not 0 gets an all-NaN plane.  Whatever the
+ * bytes hold, nothing outside [stream_off, stream_off + stream_len) and the ceil(N/8) bitmap bytes is read and nothing outside
+ * [dst_off, dst_off + N) of `planes` is written.
+ * Launches, in stream order, workgroups depending on each other through the launch boundaries only: sums (per chunk of
+ * p4c_grib_complex_chunk() groups: sum of len, of len * width), scan (first value and first bit of every group; status), tiles
+ * (only with an order >= 1 or a bitmap in the call: the sums of d and j d per tile of p4c_grib_complex_tile() values, the
+ * population of the bitmap per tile), decode, scatter (only with a bitmap in the call: value array -> plane by rank).  A
+ * workgroup takes ceil(n / p4c_grib_complex_max_blocks()) consecutive chunks or tiles of the call.  No atomics: two calls give the
+ * same bits.  `workspace`: p4c_grib_unpack_complex_workspace_bytes(tiles, chunks, has_bitmap) bytes, 8-byte aligned, tiles = the
+ * sum of ceil(ni*nj / tile), chunks = the sum of max(1, ceil(ng / chunk)) over the fields.
+ * Errors (nothing is launched, nothing written): those of p4c_grib_unpack on the offsets, the grid, count, D, the bitmap and
+ * tile0; ref_bits, w_bits or l_bits outside 0 .. 32; w_ref or l_inc outside 0 .. 255; order outside 0 .. 2; nbytes outside
+ * 0 .. 4; ng >= 2^31; ng == 0 with count > 0; a stream shorter than the descriptors and the three padded tables; chunk0 that is
+ * not the running sum of the chunks. */
+typedef struct p4c_grib_cfield {
+    int64_t stream_off; /* byte offset of the section-7 payload in `bytes`, a multiple of 4 */
+    int64_t stream_len; /* its length in bytes */
+    int64_t bitmap_off; /* byte offset of the section-6 bitmap, a multiple of 4; -1: every point present */
+    int64_t dst_off;    /* offset in floats of the field's plane in `planes`, a multiple of 4 */
+    int64_t ival1;      /* 5.3: the first value of the field (0 for 5.2) */
+    int64_t ival2;      /* 5.3 order 2: the second value (0 otherwise) */
+    int64_t gmin;       /* 5.3: the overall minimum of the differences (0 for 5.2) */
+    int32_t ni, nj;     /* stream row length and number of rows */
+    int32_t count;      /* number of packed values (section 5 octets 6-9) */
+    uint32_t ng;        /* number of groups (octets 32-35) */
+    int32_t ref_bits;   /* bits of a group reference (octet 20), 0 .. 32 */
+    int32_t w_ref;      /* reference of the group widths (octet 36) */
+    int32_t w_bits;     /* bits of a stored group width (octet 37), 0 .. 32 */
+    uint32_t l_ref;     /* reference of the group lengths (octets 38-41) */
+    int32_t l_inc;      /* length increment (octet 42) */
+    uint32_t l_last;    /* true length of the last group (octets 43-46) */
+    int32_t l_bits;     /* bits of a stored scaled group length (octet 47), 0 .. 32 */
+    int32_t order;      /* order of the spatial differencing: 0 for template 5.2, 1 or 2 for 5.3 (octet 48) */
+    int32_t nbytes;     /* octets of each descriptor in front of the tables (octet 49), 0 .. 4; not read at order 0 */
+    int32_t E, D;       /* binary and decimal scale factors */
+    float R;            /* reference value */
+    int32_t flip_rows;  /* 1: stream row r goes to plane row nj-1-r */
+    int32_t tile0;      /* index of the field's first tile among all tiles of the call */
+    int32_t chunk0;     /* index of the field's first chunk of groups among all chunks of the call */
+    int32_t pad;
+} p4c_grib_cfield;
+
+int p4c_grib_complex_tile(void);       /* values per tile */
+int p4c_grib_complex_chunk(void);      /* groups per chunk */
+int p4c_grib_complex_max_blocks(void); /* the most workgroups of one launch */
+size_t p4c_grib_unpack_complex_workspace_bytes(int64_t tiles, int64_t chunks, int has_bitmap);
+int p4c_grib_unpack_complex(const unsigned char* bytes, int64_t nbytes, const p4c_grib_cfield* fields,
+                            const p4c_grib_cfield* fields_host, int nfields, float* planes, int32_t* status, void* workspace,
+                            p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

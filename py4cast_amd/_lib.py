@@ -67,6 +67,8 @@ SIGNATURES = {
     "p4c_grib_pack": [P, L, L, P, P, P, P, P, I, P, P, L, P, I, I, I, I, I, I, I, P],
     # bytes, nbytes, fields (device), fields (host), nfields, planes, ws, stream
     "p4c_grib_unpack": [P, L, P, P, I, P, P, P],
+    # bytes, nbytes, fields (device), fields (host), nfields, planes, status, ws, stream
+    "p4c_grib_unpack_complex": [P, L, P, P, I, P, P, P, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],
@@ -124,6 +126,10 @@ OTHER = {
     "p4c_grib_unpack_max_blocks": ([], c_int),
     "p4c_grib_unpack_fast": ([I, I], c_int),
     "p4c_grib_unpack_workspace_bytes": ([L], c_size_t),
+    "p4c_grib_complex_tile": ([], c_int),
+    "p4c_grib_complex_chunk": ([], c_int),
+    "p4c_grib_complex_max_blocks": ([], c_int),
+    "p4c_grib_unpack_complex_workspace_bytes": ([L, L, I], c_size_t),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

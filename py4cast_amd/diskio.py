@@ -147,8 +147,15 @@ class GribPlaneReader:
 
     On a device the packed bit streams and bitmaps of all selected messages are copied, as they lie in the files, into one pinned
     byte buffer at 4-byte aligned offsets (grown when needed; a message selected twice is copied once), shipped in one non-blocking
-    copy on a copy stream and decoded by ``ops.grib_unpack``: no value is computed on the host.  With ``device=None`` the planes are
+    copy on a copy stream and decoded by ``ops.grib_unpack`` (simple packing, template 5.0) and ``ops.grib_unpack_complex`` (complex
+    packing, 5.2 / 5.3; a call may mix them): no value is computed on the host.  With ``device=None`` the planes are
     ``grib2.unpack_fields`` of the same fields, on the host.  An absent point (bitmap) is NaN.
+
+    Whether the stream of a complex-packed message agrees with its header shows on the device only (``ops.GRIB_STATUS_*``).
+    ``check=True``: after a call that held such messages the reader copies their status words back -- one blocking copy -- and raises
+    ``grib2.GribError`` naming the file and the condition, as the host path does.  ``check=False``: no synchronisation; the words stay
+    in ``last_status`` (device, one per complex-packed field in the order of the selection; None after a call without any) and a
+    malformed field is an all-NaN plane.
 
     Plane row 0 is the NORTHERNMOST row and ``lat`` descends, whichever way the file scans: a file whose rows run south to north
     (scanning-mode bit 0x40) is flipped while it is decoded (``flip_rows``).  This is a deliberate difference from the reference,
@@ -158,8 +165,10 @@ class GribPlaneReader:
     Messages are selected by the numeric keys of ``grib2.MATCHED_KEYS`` (``outputs.grib_fid``), not by ``shortName``.  All fields of
     one call must lie on one grid.  ``cache``: how many parsed files are kept (the reference's ``read_grib`` keeps 50)."""
 
-    def __init__(self, device=None, pin: Optional[bool] = None, cache: int = 50):
+    def __init__(self, device=None, pin: Optional[bool] = None, cache: int = 50, check: bool = True):
         self.device = device
+        self.check = bool(check)
+        self.last_status: Optional[torch.Tensor] = None   # the status words of the last call's complex-packed fields, on the device
         self.cuda = device is not None and torch.device(device).type == "cuda"
         self.pin = (torch.cuda.is_available() and self.cuda) if pin is None else pin
         self.cache = int(cache)
@@ -215,10 +224,15 @@ class GribPlaneReader:
 
         (F, B, T), chosen, (ni, nj, lat, lon) = self._select(selections)
         if not self.cuda:
-            planes = grib2.unpack_fields([f for _, _, f in chosen], flip=[f.south_to_north for _, _, f in chosen])
+            planes = []
+            for path, _, f in chosen:
+                try:
+                    planes += grib2.unpack_fields([f], flip=f.south_to_north)
+                except grib2.GribError as e:
+                    raise grib2.GribError(f"{path}: {e}") from None
             host = torch.from_numpy(np.stack(planes).reshape(F, B, T, nj, ni))
             return (host if self.device is None else host.to(self.device)), lat.copy(), lon.copy()
-        # where every distinct message's stream and bitmap go in the byte buffer
+        # where every distinct message's stream and bitmap go in the byte buffer, simple- and complex-packed alike
         place, at = {}, 0
         for path, m, f in chosen:
             if (path, id(m)) not in place:
@@ -238,20 +252,46 @@ class GribPlaneReader:
                 buf[b_off:b_off + len(f.bitmap)] = np.frombuffer(f.bitmap, dtype=np.uint8)
         N = ni * nj
         pitch = (N + 3) // 4 * 4
-        table = np.zeros(len(chosen), dtype=ops.GRIB_FIELD)
-        for i, (path, m, f) in enumerate(chosen):
+        # plane i of the output belongs to chosen[i], whichever of the two tables it is decoded from
+        simple = [i for i, (_, _, f) in enumerate(chosen) if not isinstance(f, grib2.ComplexField)]
+        packed = [i for i, (_, _, f) in enumerate(chosen) if isinstance(f, grib2.ComplexField)]
+        table = np.zeros(len(simple), dtype=ops.GRIB_FIELD)
+        for j, i in enumerate(simple):
+            path, m, f = chosen[i]
             s_off, b_off, _ = place[path, id(m)]
-            table[i] = (s_off, len(f.stream), b_off, i * pitch, f.ni, f.nj, f.count, f.nbits, f.E, f.D, f.R, int(f.south_to_north), 0, 0)
+            table[j] = (s_off, len(f.stream), b_off, i * pitch, f.ni, f.nj, f.count, f.nbits, f.E, f.D, f.R, int(f.south_to_north), 0, 0)
+        ctable = np.zeros(len(packed), dtype=ops.GRIB_CFIELD)
+        for j, i in enumerate(packed):
+            path, m, f = chosen[i]
+            rec = ctable[j]
+            rec["stream_off"], rec["bitmap_off"], _ = place[path, id(m)]
+            rec["stream_len"], rec["dst_off"], rec["flip_rows"] = len(f.stream), i * pitch, int(f.south_to_north)
+            for name in ("ni", "nj", "count", "ng", "ref_bits", "w_ref", "w_bits", "l_ref", "l_inc", "l_last", "l_bits", "order", "nbytes",
+                         "ival1", "ival2", "gmin", "E", "D", "R"):
+                rec[name] = getattr(f, name)
         current = torch.cuda.current_stream(self.device)
         self.copy_stream.wait_stream(current)
         with torch.cuda.stream(self.copy_stream):
             dev = self.host[:max(at, 4)].to(self.device, non_blocking=True)
             self._copied = torch.cuda.Event()
             self._copied.record(self.copy_stream)
-        current.wait_stream(self.copy_stream)      # the unpack launch runs after the transfer
+        current.wait_stream(self.copy_stream)      # the unpack launches run after the transfer
         dev.record_stream(current)
+        self.last_status = None
         with torch.cuda.device(dev.device):
-            flat = ops.grib_unpack(dev, table, out=torch.empty(len(chosen) * pitch, dtype=torch.float32, device=dev.device))
+            flat = torch.empty(len(chosen) * pitch, dtype=torch.float32, device=dev.device)
+            if simple:
+                ops.grib_unpack(dev, table, out=flat)
+            if packed:
+                _, self.last_status = ops.grib_unpack_complex(dev, ctable, out=flat)
+        if packed and self.check:
+            # one blocking copy of len(packed) ints: the price of naming a malformed file here instead of handing on a NaN plane
+            for j, st in enumerate(self.last_status.cpu().tolist()):
+                if st:
+                    what = [text for bit, text in ((ops.GRIB_STATUS_LENGTHS, "the group lengths do not sum to the number of values"),
+                                                   (ops.GRIB_STATUS_WIDTH, "a group width above 32 bits"),
+                                                   (ops.GRIB_STATUS_STREAM, "the values need more bits than section 7 holds")) if st & bit]
+                    raise grib2.GribError(f"{chosen[packed[j]][0]}: complex-packed message {chosen[packed[j]][1]!r}: {'; '.join(what)}")
         # no copy: where Nj * Ni is no multiple of 4 the planes keep their pitch (dense planes, which load_native_batch takes as they are)
         planes = flat.as_strided((F, B, T, nj, ni), (B * T * pitch, T * pitch, pitch, ni, 1))
         return planes, lat.copy(), lon.copy()

@@ -32,13 +32,28 @@ tables, not in the message) and ``tablesVersion`` are IGNORED.
 Refused, each with the octet in the message: a grid template other than 3.0; scanning-mode bits 0x80 (points run in the -i
 direction), 0x20 (adjacent points consecutive in j) and 0x10 (alternate rows reversed); a list of numbers of points; coordinate values
 in section 4; a product template other than 4.0 / 4.8; more than one time range; a data representation template other than 5.0,
-5.2, 5.3, 5.40, 5.41 as the source of D and nbits (these share octets 18-19 and 20); anything but 5.0 on decoding; a message with
-repeated sections.  Scanning-mode bit 0x40 (rows run south to north) is honoured.
+5.2, 5.3, 5.40, 5.41 as the source of D and nbits (these share octets 18-19 and 20); anything but 5.0, 5.2 and 5.3 on decoding; a
+message with repeated sections.  Scanning-mode bit 0x40 (rows run south to north) is honoured.
 
 Reading (``diskio.GribPlaneReader``): ``GribFile`` indexes a file, ``field_of`` hands out a message's packed stream and bitmap as
 they lie in it, ``ops.grib_unpack`` (csrc/grib_unpack.hip) decodes a batch of them on the device and ``unpack_fields`` in numpy.
-Only simple packing (5.0) is decoded; 5.2, 5.3, 5.40, 5.41 and 5.42 are out of scope and refused.  Messages are found by the numeric
-keys above, never by ``shortName``.
+Complex packing (5.2) and complex packing with spatial differencing (5.3), as g2clib's ``comunpack`` reads them, go the same way:
+``complex_field_of`` -> ``ComplexField``, ``ops.grib_unpack_complex`` (csrc/grib_complex.hip), ``unpack_fields``:
+
+  section 5 (47)   template 5.2: 6-9 number of values; 12-15 R; 16-17 E; 18-19 D; 20 bits of a group reference; 21 type of original
+                   values (ignored); 22 group splitting method (1 = general); 23 missing value management (0 = none); 24-31 missing
+                   value substitutes (unused); 32-35 NG, number of groups; 36 reference of the group widths; 37 bits of a group width;
+                   38-41 reference of the group lengths; 42 length increment; 43-46 true length of the last group; 47 bits of a
+                   scaled group length
+  section 5 (49)   template 5.3 adds: 48 order of the spatial differencing (1 or 2); 49 octets of each extra descriptor
+  section 7        6.. 5.3 only: ival1, ival2 (order 2), gmin, sign and magnitude; then, each zero-padded to an octet: NG group
+                   references, NG widths, NG scaled lengths, the values in group order (group g: len[g] integers of width[g] bits)
+
+``width[g] = w_ref + w[g]``, ``len[g] = l_ref + l_inc * l[g]``, the last group's length is octets 43-46 whatever its stored length
+says, a table of 0 bits is absent (all 0).  ``X[k] = ref[g] + value``; 5.2: f = X; 5.3 order 1: f[0] = ival1, f[k] = f[k-1] + X[k] +
+gmin; order 2: f[0] = ival1, f[1] = ival2, f[k] = X[k] + gmin + 2 f[k-1] - f[k-2]; integer arithmetic modulo 2^64, f signed;
+``Y = (R + f 2^E) / 10^D``.  Still out of scope and refused: 5.40, 5.41, 5.42, missing value management 1 and 2, group splitting
+other than the general one.  Messages are found by the numeric keys above, never by ``shortName``.
 """
 import datetime as dt
 import math
@@ -55,6 +70,7 @@ MATCHED_KEYS = ("discipline", "parameterCategory", "parameterNumber", "typeOfFir
 D_NBITS_TEMPLATES = (0, 2, 3, 40, 41)
 UNIT_MINUTE, UNIT_HOUR = 0, 1
 MAX_D = 15
+COMPLEX_TEMPLATES = (2, 3)
 
 
 class GribError(ValueError):
@@ -366,12 +382,23 @@ def unpack_bits(data: bytes, count: int, nbits: int) -> np.ndarray:
 
 
 def decode(message) -> Tuple[np.ma.MaskedArray, dict]:
-    """A simple-packed (5.0) message on a 3.0 grid -> ((Nj, Ni) masked float64 in stream order, the parsed keys)."""
+    """A simple-packed (5.0) or complex-packed (5.2, 5.3) message on a 3.0 grid -> ((Nj, Ni) masked float64 in stream order, the
+    parsed keys).  For 5.2 / 5.3 this is the float64 statement of the decode's contract (``complex_integers``)."""
     m = message if isinstance(message, Message) else Message(message)
     check_grid(m)
     k = m.keys
+    if k["dataRepresentationTemplateNumber"] in COMPLEX_TEMPLATES:
+        cf = complex_field_of(m)
+        present = np.ones(cf.nj * cf.ni, dtype=bool) if cf.bitmap is None else \
+            np.unpackbits(np.frombuffer(cf.bitmap, dtype=np.uint8), count=cf.nj * cf.ni).astype(bool)
+        values = np.zeros(cf.nj * cf.ni, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            scaled = float(cf.R) + np.ldexp(complex_integers(cf).astype(np.float64), cf.E)
+            values[present] = scaled / float(10 ** cf.D) if cf.D >= 0 else scaled * float(10 ** -cf.D)
+        return np.ma.MaskedArray(values.reshape(cf.nj, cf.ni), mask=~present.reshape(cf.nj, cf.ni)), k
     if k["dataRepresentationTemplateNumber"] != 0:
-        raise GribError(f"section 5 octets 10-11: data representation template 5.{k['dataRepresentationTemplateNumber']}; only 5.0 is decoded")
+        raise GribError(f"section 5 octets 10-11: data representation template 5.{k['dataRepresentationTemplateNumber']}; only 5.0, 5.2 "
+                        f"and 5.3 are decoded")
     Ni, Nj, count, nbits = k["Ni"], k["Nj"], k["numberOfValues"], k["bitsPerValue"]
     if k["bitMapIndicator"] == 255:
         present = np.ones(Nj * Ni, dtype=bool)
@@ -453,10 +480,176 @@ def field_of(message) -> PackedField:
                        k["scanningMode"])
 
 
-def unpack_fields(fields: Sequence[PackedField], flip=False) -> List[np.ndarray]:
-    """The contract of csrc/grib_unpack.hip in numpy -> one (nj, ni) float32 plane per field.  The k-th present point takes the k-th
-    value X of the stream; Y = (R + ldexp(X, E)) / 10^D (``* 10^-D`` for D < 0) in float64, rounded to float32; an absent point, and
-    a present one of rank >= count, is NaN.  ``flip`` (one bool, or one per field): stream row r becomes plane row nj-1-r."""
+@dataclass(frozen=True)
+class ComplexField:
+    """What the decoder needs of one complex-packed message (5.2: ``order`` 0; 5.3: ``order`` 1 or 2); ``stream`` (section 7 from
+    octet 6: descriptors, group tables and values) and ``bitmap`` (section 6 from octet 7, None without one) are memoryviews into
+    the message's sections, not copies.  ``ival1``, ``ival2`` and ``gmin`` are parsed here, like R, E and D; 0 where the template
+    has none."""
+    stream: memoryview
+    bitmap: Optional[memoryview]
+    ni: int
+    nj: int
+    count: int
+    R: float
+    E: int
+    D: int
+    scanning_mode: int
+    ng: int          # octets 32-35
+    ref_bits: int    # octet 20
+    w_ref: int       # octet 36
+    w_bits: int      # octet 37
+    l_ref: int       # octets 38-41
+    l_inc: int       # octet 42
+    l_last: int      # octets 43-46
+    l_bits: int      # octet 47
+    order: int       # octet 48; 0 for template 5.2
+    nbytes: int      # octet 49; 0 for template 5.2
+    ival1: int
+    ival2: int
+    gmin: int
+
+    @property
+    def south_to_north(self) -> bool:
+        return bool(self.scanning_mode & 0x40)
+
+    @property
+    def template(self) -> int:
+        return 3 if self.order else 2
+
+    @property
+    def descriptor_octets(self) -> int:
+        return (self.order + 1) * self.nbytes if self.order else 0
+
+    def table_bits(self) -> Tuple[int, int, int, int]:
+        """the first bit of the group references, of the widths, of the scaled lengths and of the values in ``stream``"""
+        ref = 8 * self.descriptor_octets
+        width = ref + 8 * ((self.ng * self.ref_bits + 7) // 8)
+        length = width + 8 * ((self.ng * self.w_bits + 7) // 8)
+        return ref, width, length, length + 8 * ((self.ng * self.l_bits + 7) // 8)
+
+
+def complex_field_of(message) -> ComplexField:
+    """The packed field of a complex-packed message on a 3.0 grid.  Refused, each with its octet: everything ``check_grid`` refuses; a
+    data representation template other than 5.2 / 5.3; a section 5 shorter than 47 / 49 octets; more than 32 bits for a group
+    reference, width or scaled length (octets 20, 37, 47); a group splitting method other than 1 (octet 22); missing value management
+    (octet 23); an order outside 1 .. 2 (octet 48); descriptors of more than 4 octets (octet 49; with 0 the three are 0); no group for
+    count > 0; |D| > 15; the bitmap conditions of ``field_of``; a section 7 shorter than the descriptors and the three padded tables."""
+    m = message if isinstance(message, Message) else Message(message)
+    check_grid(m)
+    k = m.keys
+    s5, s6, s7 = m.sections[5], m.sections[6], m.sections[7]
+    number = k["dataRepresentationTemplateNumber"]
+    if number not in COMPLEX_TEMPLATES:
+        raise GribError(f"section 5 octets 10-11: data representation template 5.{number}; 5.2 and 5.3 (complex packing) are decoded here")
+    octets = 47 if number == 2 else 49
+    if len(s5) < octets:
+        raise GribError(f"section 5 octets 1-4: {len(s5)} octets; template 5.{number} has {octets}")
+    ni, nj, count, D = k["Ni"], k["Nj"], k["numberOfValues"], k["decimalScaleFactor"]
+    for octet, what in ((20, "a group reference"), (37, "a group width"), (47, "a scaled group length")):
+        if s5[octet - 1] > 32:
+            raise GribError(f"section 5 octet {octet}: {s5[octet - 1]} bits for {what}; 0 .. 32 are decoded")
+    if s5[21] != 1:
+        raise GribError(f"section 5 octet 22: group splitting method {s5[21]}; only 1 (general group splitting) is decoded")
+    if s5[22] != 0:
+        raise GribError(f"section 5 octet 23: missing value management {s5[22]}; primary and secondary missing values are out of scope")
+    order = nbytes = 0
+    if number == 3:
+        order, nbytes = s5[47], s5[48]
+        if not 1 <= order <= 2:
+            raise GribError(f"section 5 octet 48: spatial differencing of order {order}; 1 and 2 are decoded")
+        if nbytes > 4:
+            raise GribError(f"section 5 octet 49: {nbytes} octets per extra descriptor; 0 .. 4 are decoded")
+    ng = _u(s5, 32, 4)
+    if ng == 0 and count > 0:
+        raise GribError(f"section 5 octets 32-35: no group for {count} values")
+    if abs(D) > MAX_D:
+        raise GribError(f"section 5 octets 18-19: D = {D}; |D| <= {MAX_D} is decoded")
+    points = ni * nj
+    bitmap = None
+    if k["bitMapIndicator"] == 0:
+        need = (points + 7) // 8
+        if len(s6) - 6 < need:
+            raise GribError(f"section 6 octets 1-4: a bitmap of {len(s6) - 6} octets for {points} points")
+        bitmap = memoryview(s6)[6:6 + need]
+        present = (int.from_bytes(bitmap, "big") >> (8 * need - points)).bit_count()
+        if present != count:
+            raise GribError(f"section 5 octets 6-9: {count} values for {present} points present in the bitmap")
+    elif k["bitMapIndicator"] == 255:
+        if count != points:
+            raise GribError(f"section 5 octets 6-9: {count} values for {points} points and no bitmap")
+    else:
+        raise GribError(f"section 6 octet 6: bitmap indicator {k['bitMapIndicator']}; 0 (a bitmap follows) and 255 (none) are read")
+    stream = memoryview(s7)[5:]
+    descriptors = [_s(stream, 1 + i * nbytes, nbytes) if nbytes and len(stream) >= (i + 1) * nbytes else 0 for i in range(order + 1 if order else 0)]
+    ival1 = descriptors[0] if order else 0
+    ival2 = descriptors[1] if order == 2 else 0
+    gmin = descriptors[-1] if order else 0
+    f = ComplexField(stream, bitmap, ni, nj, count, float(k["referenceValue"]), k["binaryScaleFactor"], D, k["scanningMode"], ng,
+                     s5[19], s5[35], s5[36], _u(s5, 38, 4), s5[41], _u(s5, 43, 4), s5[46], order, nbytes, ival1, ival2, gmin)
+    need = f.table_bits()[3] // 8
+    if len(stream) < need:
+        raise GribError(f"section 7 octets 1-4: {len(stream)} octets of data for {need} octets of descriptors and group tables")
+    return f
+
+
+def _integers_at(bits: np.ndarray, starts: np.ndarray, width: int) -> np.ndarray:
+    """the ``width``-bit integers that start at the bits ``starts`` of the 0/1 array ``bits``, most significant bit first -> uint64"""
+    if width == 0 or starts.size == 0:
+        return np.zeros(starts.size, dtype=np.uint64)
+    picked = bits[starts[:, None] + np.arange(width, dtype=np.int64)].astype(np.uint64)
+    return (picked << np.arange(width - 1, -1, -1, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+
+
+def complex_integers(f: ComplexField) -> np.ndarray:
+    """The ``count`` integers f[k] of a complex-packed field (module docstring) -> int64; all sums modulo 2^64.  Raises GribError when
+    the stream contradicts the header: the group lengths do not sum to count, a group width above 32, values past the stream's end
+    (bits 1, 2, 4 of the device's status word)."""
+    bits = np.unpackbits(np.frombuffer(f.stream, dtype=np.uint8))
+    at_ref, at_width, at_length, at_values = f.table_bits()
+    if at_values > bits.size:
+        raise GribError(f"a stream of {bits.size // 8} octets is shorter than its descriptors and group tables ({at_values // 8} octets)")
+    g = np.arange(f.ng, dtype=np.int64)
+    ref = _integers_at(bits, at_ref + g * f.ref_bits, f.ref_bits)
+    width = f.w_ref + _integers_at(bits, at_width + g * f.w_bits, f.w_bits).astype(np.int64)
+    length = f.l_ref + f.l_inc * _integers_at(bits, at_length + g * f.l_bits, f.l_bits).astype(np.int64)
+    if f.ng:
+        length[-1] = f.l_last                                  # whatever its stored scaled length says
+    if (width > 32).any():
+        raise GribError(f"a group width of {int(width.max())} bits: the widths of the groups go up to 32")
+    if int(length.sum()) != f.count:
+        raise GribError(f"the group lengths sum to {int(length.sum())}, the field has {f.count} values")
+    if at_values + int((length * width).sum()) > bits.size:
+        raise GribError(f"the values need {int((length * width).sum())} bits, the stream holds {bits.size - at_values} after its group tables")
+    first = np.cumsum(length) - length                         # the first value of a group
+    first_bit = at_values + np.cumsum(length * width) - length * width
+    group = np.repeat(g, length)                               # the group of value k
+    k = np.arange(f.count, dtype=np.int64)
+    value_width = width[group]
+    start = first_bit[group] + (k - first[group]) * value_width
+    X = ref[group].copy()
+    for w in np.unique(value_width):
+        mine = value_width == w
+        X[mine] += _integers_at(bits, start[mine], int(w))
+    if f.order == 0:
+        return X.view(np.int64)
+    wrap = lambda v: np.array([v % 2 ** 64], dtype=np.uint64)   # noqa: E731
+    d = X + wrap(f.gmin)
+    d[:f.order] = 0                                            # the first `order` values of the stream are placeholders
+    if f.order == 1:                                           # f[k] = f[k-1] + d[k]
+        return (wrap(f.ival1) + np.cumsum(d, dtype=np.uint64)).view(np.int64)
+    # order 2: the first differences g[k] = f[k] - f[k-1] obey g[1] = ival2 - ival1, g[k] = g[k-1] + d[k]; then f[k] = f[k-1] + g[k]
+    steps = wrap(f.ival2 - f.ival1) + np.cumsum(d, dtype=np.uint64)
+    steps[:1] = 0
+    return (wrap(f.ival1) + np.cumsum(steps, dtype=np.uint64)).view(np.int64)
+
+
+def unpack_fields(fields: Sequence, flip=False) -> List[np.ndarray]:
+    """The contract of csrc/grib_unpack.hip (``PackedField``) and csrc/grib_complex.hip (``ComplexField``) in numpy -> one (nj, ni)
+    float32 plane per field.  The k-th present point takes the k-th value X of the stream (f[k] of ``complex_integers`` for a
+    ComplexField); Y = (R + ldexp(X, E)) / 10^D (``* 10^-D`` for D < 0) in float64, rounded to float32; an absent point, and a present
+    one of rank >= count, is NaN.  ``flip`` (one bool, or one per field): stream row r becomes plane row nj-1-r.  A ComplexField whose
+    stream contradicts its header (the conditions of the device's status word) raises GribError."""
     flips = [bool(flip)] * len(fields) if isinstance(flip, (bool, np.bool_)) else [bool(f) for f in flip]
     if len(flips) != len(fields):
         raise ValueError(f"{len(flips)} flip flags for {len(fields)} fields")
@@ -469,7 +662,10 @@ def unpack_fields(fields: Sequence[PackedField], flip=False) -> List[np.ndarray]
             present = np.unpackbits(np.frombuffer(f.bitmap, dtype=np.uint8), count=points).astype(bool)
         where = np.flatnonzero(present)[:f.count]           # ranks past count stay NaN
         n = min(f.count, where.size)
-        X = unpack_bits(bytes(f.stream[:(n * f.nbits + 7) // 8]), n, f.nbits).astype(np.float64) if f.nbits and n else np.zeros(n)
+        if isinstance(f, ComplexField):
+            X = complex_integers(f)[:n].astype(np.float64)
+        else:
+            X = unpack_bits(bytes(f.stream[:(n * f.nbits + 7) // 8]), n, f.nbits).astype(np.float64) if f.nbits and n else np.zeros(n)
         with np.errstate(all="ignore"):
             scaled = float(f.R) + np.ldexp(X, f.E)
             y = scaled / float(10 ** f.D) if f.D >= 0 else scaled * float(10 ** -f.D)
@@ -482,14 +678,15 @@ def unpack_fields(fields: Sequence[PackedField], flip=False) -> List[np.ndarray]
 
 class GribFile:
     """An index over the messages of one GRIB2 file for reading: ``find(fid)`` matches as ``Template.find`` does (numeric
-    MATCHED_KEYS only, no ``shortName``), ``field(fid)`` is ``field_of`` of that message, parsed once."""
+    MATCHED_KEYS only, no ``shortName``), ``field(fid)`` is ``field_of`` of that message -- ``complex_field_of`` for templates 5.2 and
+    5.3 -- parsed once."""
 
     def __init__(self, path):
         self.path = path
         self.messages = read_messages(path)
         if not self.messages:
             raise GribError(f"{path}: no GRIB2 message")
-        self._fields: Dict[int, PackedField] = {}
+        self._fields: Dict[int, object] = {}
 
     def find(self, fid: dict) -> Message:
         if not set(fid) - set(IGNORED_KEYS):
@@ -497,11 +694,12 @@ class GribFile:
                             f"out of scope, messages are found by their numeric keys")
         return find_message(self.messages, fid, self.path)
 
-    def field(self, fid: dict) -> Tuple[Message, PackedField]:
+    def field(self, fid: dict) -> Tuple[Message, object]:
         m = self.find(fid)
         if id(m) not in self._fields:
             try:
-                self._fields[id(m)] = field_of(m)
+                complex_packed = m.keys["dataRepresentationTemplateNumber"] in COMPLEX_TEMPLATES
+                self._fields[id(m)] = complex_field_of(m) if complex_packed else field_of(m)
             except GribError as e:
                 raise GribError(f"{self.path}: {e}") from None
         return m, self._fields[id(m)]

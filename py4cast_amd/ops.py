@@ -959,3 +959,93 @@ def grib_unpack(bytes_dev: torch.Tensor, fields, out: Optional[torch.Tensor] = N
     L.call("p4c_grib_unpack", L.ptr(bytes_dev), bytes_dev.numel(), L.ptr(table_dev), ctypes.c_void_p(table.ctypes.data), int(table.size),
            L.ptr(out), L.ptr(ws), L.stream(dev), alg_bytes=read + 4 * int(points.sum()))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ GRIB2 complex packing, decoded
+# launch constants of csrc/grib_complex.hip (p4c_grib_complex_tile() / _chunk() / _max_blocks() report the same)
+GRIB_COMPLEX_TILE = 2048        # values per tile, 8 per lane
+GRIB_COMPLEX_CHUNK = 1024       # groups per chunk, 4 per lane
+GRIB_COMPLEX_MAX_BLOCKS = 1024  # the most workgroups of one launch
+GRIB_STATUS_LENGTHS, GRIB_STATUS_WIDTH, GRIB_STATUS_STREAM = 1, 2, 4   # the bits of a field's status
+# host mirror of p4c_grib_cfield (include/py4cast_hip.h)
+GRIB_CFIELD = np.dtype([("stream_off", "<i8"), ("stream_len", "<i8"), ("bitmap_off", "<i8"), ("dst_off", "<i8"), ("ival1", "<i8"),
+                        ("ival2", "<i8"), ("gmin", "<i8"), ("ni", "<i4"), ("nj", "<i4"), ("count", "<i4"), ("ng", "<u4"), ("ref_bits", "<i4"),
+                        ("w_ref", "<i4"), ("w_bits", "<i4"), ("l_ref", "<u4"), ("l_inc", "<i4"), ("l_last", "<u4"), ("l_bits", "<i4"),
+                        ("order", "<i4"), ("nbytes", "<i4"), ("E", "<i4"), ("D", "<i4"), ("R", "<f4"), ("flip_rows", "<i4"), ("tile0", "<i4"),
+                        ("chunk0", "<i4"), ("pad", "<i4")])
+
+
+def grib_cfields(records) -> np.ndarray:
+    """A GRIB_CFIELD table from a sequence of mappings with its column names; ``bitmap_off`` defaults to -1 (no bitmap), everything
+    else to 0.  A GRIB_CFIELD array is copied."""
+    if isinstance(records, np.ndarray):
+        if records.dtype != GRIB_CFIELD:
+            raise L.P4CError(f"grib_unpack_complex: a table of dtype {records.dtype}, GRIB_CFIELD expected")
+        return records.reshape(-1).copy()
+    table = np.zeros(len(records), dtype=GRIB_CFIELD)
+    table["bitmap_off"] = -1
+    for i, rec in enumerate(records):
+        for name, value in rec.items():
+            if name not in GRIB_CFIELD.names:
+                raise L.P4CError(f"grib_unpack_complex: field {i}: {name!r} is no column of GRIB_CFIELD")
+            table[i][name] = value
+    return table
+
+
+def grib_ctable(fields, dense: bool) -> np.ndarray:
+    """The table ``grib_unpack_complex`` launches with: ``grib_cfields(fields)`` with ``tile0`` and ``chunk0`` filled in and, with
+    ``dense``, ``dst_off`` too: the planes one after the other in the order of the table, each at a multiple of 4 floats."""
+    table = grib_cfields(fields)
+    if table.size < 1:
+        raise L.P4CError("grib_unpack_complex: no fields")
+    points = table["ni"].astype(np.int64) * table["nj"].astype(np.int64)
+    if points.min() < 1 or points.max() >= 2 ** 31:
+        raise L.P4CError(f"grib_unpack_complex: fields of {points.min()} .. {points.max()} points: 1 .. 2^31 - 1 expected")
+    tiles = (points + GRIB_COMPLEX_TILE - 1) // GRIB_COMPLEX_TILE
+    chunks = np.maximum((table["ng"].astype(np.int64) + GRIB_COMPLEX_CHUNK - 1) // GRIB_COMPLEX_CHUNK, 1)
+    if int(tiles.sum()) >= 2 ** 31 or int(chunks.sum()) >= 2 ** 31:
+        raise L.P4CError(f"grib_unpack_complex: {int(tiles.sum())} tiles, {int(chunks.sum())} chunks: fewer than 2^31 per call")
+    table["tile0"] = np.cumsum(tiles) - tiles
+    table["chunk0"] = np.cumsum(chunks) - chunks
+    if dense:
+        padded = (points + 3) // 4 * 4
+        table["dst_off"] = np.cumsum(padded) - padded
+    return table
+
+
+def grib_unpack_complex(bytes_dev: torch.Tensor, fields, out: Optional[torch.Tensor] = None,
+                        status: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The complex-packed (5.2 / 5.3) section-7 payloads and bitmaps of GRIB2 fields, lying in the device byte buffer ``bytes_dev``
+    (uint8, dense, 4-byte aligned) as they do in the files -> (their fp32 planes in one flat device tensor, one int32 status per field)
+    (p4c_grib_unpack_complex; the contract is in include/py4cast_hip.h and, in numpy, ``grib2.unpack_fields``).  ``fields``: a
+    GRIB_CFIELD array or a sequence of mappings (``grib_cfields``); ``tile0`` and ``chunk0`` are filled in here.  ``out`` as in
+    ``grib_unpack``.  ``status`` (int32, one per field, on the device) stays there: a field whose word is not 0 (GRIB_STATUS_*: its
+    stream contradicts its header) has an all-NaN plane; reading it is the caller's synchronisation.  The records are checked by the
+    library, not here.  Not differentiable."""
+    L.require_cuda(bytes_dev, out, status)
+    if bytes_dev.dtype != torch.uint8 or bytes_dev.dim() != 1 or not bytes_dev.is_contiguous() or bytes_dev.data_ptr() % 4:
+        raise L.P4CError(f"grib_unpack_complex: bytes {tuple(bytes_dev.shape)} {bytes_dev.dtype}: a dense, 4-byte aligned 1-D uint8 tensor "
+                         f"expected")
+    table = grib_ctable(fields, dense=out is None)
+    points = table["ni"].astype(np.int64) * table["nj"].astype(np.int64)
+    tiles = int(((points + GRIB_COMPLEX_TILE - 1) // GRIB_COMPLEX_TILE).sum())
+    chunks = int(np.maximum((table["ng"].astype(np.int64) + GRIB_COMPLEX_CHUNK - 1) // GRIB_COMPLEX_CHUNK, 1).sum())
+    dev = bytes_dev.device
+    if out is None:
+        out = torch.empty(int(((points + 3) // 4 * 4).sum()), dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous() or out.device != dev
+          or int((table["dst_off"] + points).max()) > out.numel() or int(table["dst_off"].min()) < 0):
+        raise L.P4CError(f"grib_unpack_complex: out {tuple(out.shape)} {out.dtype} on {out.device}: a dense 1-D fp32 tensor on {dev} that "
+                         f"holds every plane at its dst_off expected")
+    if status is None:
+        status = torch.empty(table.size, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.dim() != 1 or not status.is_contiguous() or status.device != dev or status.numel() != table.size:
+        raise L.P4CError(f"grib_unpack_complex: status {tuple(status.shape)} {status.dtype} on {status.device}: {table.size} int32 on {dev} "
+                         f"expected")
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+    has_bitmap = bool((table["bitmap_off"] >= 0).any())
+    ws = torch.empty((L.lib().p4c_grib_unpack_complex_workspace_bytes(tiles, chunks, int(has_bitmap)) + 7) // 8, dtype=torch.int64, device=dev)
+    read = int(table["stream_len"].sum() + ((points + 7) // 8)[table["bitmap_off"] >= 0].sum())
+    L.call("p4c_grib_unpack_complex", L.ptr(bytes_dev), bytes_dev.numel(), L.ptr(table_dev), ctypes.c_void_p(table.ctypes.data),
+           int(table.size), L.ptr(out), L.ptr(status), L.ptr(ws), L.stream(dev), alg_bytes=2 * read + 4 * int(points.sum()))
+    return out, status
