@@ -830,6 +830,17 @@ typedef struct p4c_halfunet_desc {
  * the stored y per sample.  W a multiple of 32, x_cs >= 72 a multiple of 8. */
 int p4c_first_conv_tail_slots(int B, int H, int W);
 int p4c_first_conv_tail(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W, p4c_stream_t stream);
+/* The same convolution in ONE launch (csrc/conv_rows.hip, THIN; what the plan runs): the row kernel also carries the channel octet beyond
+ * 64, so y = bf16(fp32 sum over all cin channels) is written and rounded once, and the statistics come from the row kernel's drain --
+ * p4c_first_conv_one_slots(B,H,W) slots of [2][64] per sample (stat_partial may be NULL).  Same envelope as the tail; the weight images
+ * are prepared into a stream-ordered temporary.  p4c_first_conv_two runs row launch + tail (the route of P4C_FIRST_CONV_ONE=0 in the
+ * diagnostic build; slots: p4c_first_conv_tail_slots) on the same arguments.  p4c_first_conv_launch_count: kernels this process has enqueued for this
+ * convolution, counted at the launch sites of the one-launch row kernel, the row launch on wide pixels and the tail (a model call on
+ * the one-launch route adds 1, row launch + tail 2; the single-op entry points above count too). */
+int p4c_first_conv_one_slots(int B, int H, int W);
+int p4c_first_conv_one(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W, p4c_stream_t stream);
+int p4c_first_conv_two(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W, p4c_stream_t stream);
+long long p4c_first_conv_launch_count(void);
 
 /* Side stream of the calling thread for p4c_halfunet_backward (weight gradients run beside the backward chain, ordered by
  * events and joined before the call returns control of `stream`): `side` a hipStream_t, `events` n_events >= 8 hipEvent_t

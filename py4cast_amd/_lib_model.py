@@ -71,6 +71,8 @@ SIGNATURES = {
     "p4c_out_conv_bwd": [P, P, P, P, P, P, P, P, P, I, P, P, I, L, P],
     "p4c_upsample_sum_bwd_x": [I, P, I, I, I, P, P, P, P, P],
     "p4c_first_conv_tail": [P, I, I, P, P, P, I, I, I, P],
+    "p4c_first_conv_one": [P, I, I, P, P, P, I, I, I, P],
+    "p4c_first_conv_two": [P, I, I, P, P, P, I, I, I, P],
     "p4c_halfunet_workspace_bytes": [DP, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)],
     "p4c_halfunet_layout": [DP, ctypes.POINTER(HalfUNetLayout)],
     "p4c_halfunet_prepare_weights": [DP, P, P, P],
@@ -156,6 +158,8 @@ OTHER = {
     "p4c_conv_wgrad_workspace_bytes": ([I, I], c_size_t),
     "p4c_out_conv_bwd_slots": ([I, L], c_int),
     "p4c_first_conv_tail_slots": ([I, I, I], c_int),
+    "p4c_first_conv_one_slots": ([I, I, I], c_int),
+    "p4c_first_conv_launch_count": ([], ctypes.c_longlong),
     "p4c_out_conv_bwd_workspace_bytes": ([I, L], c_size_t),
     "p4c_conv_stat_tiles": ([I, I, I, I, I, I], c_int),
     "p4c_conv_stat_tiles_ks": ([I, I, I, I, I, I, I], c_int),

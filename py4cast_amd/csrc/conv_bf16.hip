@@ -2405,7 +2405,10 @@ __global__ void __launch_bounds__(256) prep_weights_batch_kernel(PrepBatch pb) {
         const int mb = t / jb.ntaps;
         const int k = 2 * kv * ks + kv * h + j, m = 64 * mb + m_l;
         float v = 0.0f;
-        if (!jb.transpose_flip) {
+        if (jb.thin) {   // `tap` counts (tap row, slice); k = 8 h + j: column shift 2 * slice + h, channel 64 + j
+            const int ky = tap >> 1, kx = 2 * (tap & 1) + h;
+            if (kx < 3 && m < jb.CO && 64 + j < jb.CI) v = jb.w[((int64_t)m * jb.CI + 64 + j) * 9 + 3 * ky + kx];
+        } else if (!jb.transpose_flip) {
             if (m < jb.CO && k < jb.CI) v = jb.w[((int64_t)m * jb.CI + k) * jb.ntaps + tap];
         } else {
             if (k < jb.CO && m < jb.CI) v = jb.w[((int64_t)k * jb.CI + m) * jb.ntaps + (jb.ntaps - 1 - tap)];

@@ -132,11 +132,22 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // on entry operands 0..2 of this row are in flight in fb[0..2], on exit (pf) those of the next row are.
 // Step s: read operand s+3, P uses operand s, Q and S operand s-2 (P runs two operands ahead so that its last MFMA
 // is six MFMAs before the end of the row: the conversion below never waits for the matrix pipe).
-template <bool HP, bool HQ, bool HS>
+//
+// THIN (the first convolution at 65..72 input channels, see the kernel): the row also carries the ninth channel octet, which the
+// loaders keep in the pad slot of every ring pixel.  Per tap row that is K = 3 columns x 8 channels = 24, padded to 32: two more
+// MFMAs per accumulator and input row (42 instead of 36), on TWO more B operands that all three accumulators share -- slice 0: half-wave h
+// reads the octet of column shift h, slice 1: shift 2 (lower half; the upper half meets zero weights and re-reads shift 1).  Their six
+// A operands (tap row x slice) are not register-stationary: `tw` is the lane's address in an LDS image, read one step ahead of use
+// through a ring of two.  Thin step j = 0..5 = (slice j / 3, accumulator j % 3) runs at s = 4 + j: after S has been started (s = 2)
+// and before P is staged (s = 12).
+template <bool HP, bool HQ, bool HS, bool THIN = false>
 __device__ __forceinline__ void conv_row(const bf16x8 (&A)[9][4], f32x16& P, f32x16& Q, f32x16& S, bf16x8 (&fb)[6],
-                                         const char* rb, const char* rbn, bool pf, char* stg, const int (&soff)[4]) {
+                                         const char* rb, const char* rbn, bool pf, char* stg, const int (&soff)[4],
+                                         const char* tw = nullptr, int tl0 = 0, int tl1 = 0) {
     using namespace rows;
     constexpr int PIXB = Lay<32>::PIXB;
+    bf16x8 tb[2], ta[2];
+    auto thin_has = [](int j) { return j % 3 == 0 ? HP : (j % 3 == 1 ? HQ : HS); };
     auto stage = [&](int g) __attribute__((always_inline)) {
         // C[co][px]: lane = pixel column r (+ half h), register quad g -> channels 32ct + 8g + 4h .. +3
         const f32x2 lo = {P[4 * g], P[4 * g + 1]}, hi = {P[4 * g + 2], P[4 * g + 3]};
@@ -153,6 +164,12 @@ __device__ __forceinline__ void conv_row(const bf16x8 (&A)[9][4], f32x16& P, f32
                 fb[o % 6] = *reinterpret_cast<const bf16x8*>(rb + (o >> 2) * PIXB + (o & 3) * 32);
             } else if (o < 15) {
                 if (pf) fb[o % 6] = *reinterpret_cast<const bf16x8*>(rbn + ((o - 12) >> 2) * PIXB + ((o - 12) & 3) * 32);
+            }
+            if constexpr (THIN) {
+                if (s == 3) tb[0] = *reinterpret_cast<const bf16x8*>(rb + tl0);
+                if (s == 6) tb[1] = *reinterpret_cast<const bf16x8*>(rb + tl1);
+                if (s >= 3 && s < 9 && thin_has(s - 3))   // A operand of thin step j = s - 3: tap row 2 - j % 3 (P / Q / S), slice j / 3
+                    ta[(s - 3) & 1] = *reinterpret_cast<const bf16x8*>(tw + ((2 - (s - 3) % 3) * 2 + (s - 3) / 3) * 2048);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (HP && s < 12) {
@@ -179,6 +196,14 @@ __device__ __forceinline__ void conv_row(const bf16x8 (&A)[9][4], f32x16& P, f32
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (HP && s >= 12) { stage(2 * (s - 12) + 1); __builtin_amdgcn_sched_barrier(0); }
+        }
+        if constexpr (THIN) {
+            if (s >= 4 && s < 10 && thin_has(s - 4) && !(P4C_EXP & 16)) {
+                const int j = s - 4;
+                f32x16& T = j % 3 == 0 ? P : (j % 3 == 1 ? Q : S);
+                T = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ta[j & 1], tb[j / 3], T, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
 }
@@ -282,13 +307,19 @@ __device__ __forceinline__ T late_arg(size_t offset) {
 // (MODE 4 + BST: pass 2 of this block's on the way in, pass 1 of the next one's in the drain): its loader would hold 72 registers of
 // prefetched dA / y rows + 64 of output / y rows for the drain -- 137 spilled registers; with two rows per interval the images are
 // half that and the kernel has none (240 registers).
-template <int MODE, bool BST, int MF, int KS, bool CPT = false, int IV = 4>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-    conv3x3_bf16_rows_kernel(RowsArgs args) {
+// THIN (a CPT launch on pixels of >= 72 channels; conv3x3_bf16_rows_thin_kernel below): the first convolution of the HalfUNet plan at
+// 65..72 input channels in ONE launch.  The loaders also fetch the ninth channel octet (byte 128 of every source pixel) into the pad slot
+// of the LDS pixel -- IV x 66 more slots per interval: they take the 192 idle lanes of the ninth load and 72 lanes of a tenth -- and the
+// matrix phase adds the octet's K slices to the rolling accumulators before a row is rounded (conv_row).  `wp` is the row image of
+// input channels 0..63 FOLLOWED by the thin image [tap row][slice][k half][64 co] x 8 bf16 (12 KB; column shift 2 * slice + k half, the
+// fourth shift and the channels beyond the real ones zero), which the compute waves copy to LDS behind the staging rows.
+template <int MODE, bool BST, int MF, int KS, bool CPT, int IV, bool THIN>
+__device__ __forceinline__ void conv3x3_bf16_rows_body(const RowsArgs& args) {
     static_assert(!CPT || (MODE == 0 && !BST && MF == 32), "compact channels: plain launches only");
+    static_assert(!THIN || (CPT && KS == 3 && IV == 4), "ninth channel octet: a compact 3x3 launch");
     static_assert(IV == 4 || IV == 2, "rows per interval");
     using namespace rows;
-    constexpr int NLD = (IV * ROWSLOTS + 255) / 256, NST = IV * 2;
+    constexpr int NLD = (IV * ROWSLOTS + (THIN ? IV * LW : 0) + 255) / 256, NST = IV * 2;
     const __bf16* __restrict__ in = args.in;
     const __bf16* __restrict__ wp = args.wp;
     const float* __restrict__ in_scale = args.in_scale;
@@ -327,6 +358,29 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         // Column validity is static per lane (the strip is fixed): slots of columns outside the image get lim = "never active";
         // those LDS columns are zeroed once below and never written, so only ROWS outside the image need the checked path.
         int gofs[NLD], lofs[NLD], lim[NLD];
+        // THIN: slot idx of a staged group is (row, column, octet) = the 8-octet table below IV * ROWSLOTS, then the ninth octets row-major
+        // (IV * LW of them; the rest of the last load is idle)
+        auto thin_slot = [&](int it, int& row, int& col, int& oct) __attribute__((always_inline)) {
+            const int idx = ltid + it * 256;
+            if (idx < IV * ROWSLOTS) {
+                row = idx / ROWSLOTS; col = (idx - row * ROWSLOTS) >> 3; oct = c8;
+                return true;
+            }
+            const int p = idx - IV * ROWSLOTS;
+            row = p / LW; col = p - row * LW; oct = 8;
+            return p < IV * LW;
+        };
+        if constexpr (THIN) {
+#pragma unroll
+            for (int it = 0; it < NLD; ++it) {
+                int row, col, oct;
+                const bool ex = thin_slot(it, row, col, oct);
+                gofs[it] = ex ? (row * W + col) * ipb + 16 * oct : OOB;
+                lofs[it] = row * RROW + col * PIXB + 16 * oct;
+                // (compared with rows x ROWSLOTS: any value inside the row's range makes the slot active exactly while its row is)
+                lim[it] = (ex && (unsigned)(x0 - 1 + col) < (unsigned)W) ? row * ROWSLOTS + col * 8 + (oct & 7) : OOB;
+            }
+        } else {
         int rr = 0, rem = ltid;   // idx = ltid + 256 it = rr * ROWSLOTS + rem, kept incrementally (no divisions: 256 < ROWSLOTS)
 #pragma unroll
         for (int it = 0; it < NLD; ++it) {
@@ -337,6 +391,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             lofs[it] = rr * RROW + LY::slot_off(col, c8);
             lim[it] = ((unsigned)(x0 - 1 + col) < (unsigned)W) ? idx : OOB;
         }
+        }
         {
             const int left = x0 == 0 ? 1 : 0;
             const int c_hi = W - x0 + 1 < LW ? W - x0 + 1 : LW;       // first column at or beyond the right image edge
@@ -346,6 +401,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
                     const int s8 = j & 7, ci = j >> 3;
                     const int col = (left && ci == 0) ? 0 : c_hi + ci - left;
                     *reinterpret_cast<u32x4*>(lring + rz * RROW + col * PIXB + 16 * s8) = u32x4{0u, 0u, 0u, 0u};   // (all 8 slots of the pixel: any order)
+                    if (THIN && s8 == 0) *reinterpret_cast<u32x4*>(lring + rz * RROW + col * PIXB + 128) = u32x4{0u, 0u, 0u, 0u};   // (and the ninth)
                 }
         }
         int dofs[NST], sofs[NST];
@@ -396,6 +452,15 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
                     for (int it = 0; it < NLD; ++it)
                         ty.s[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_nby, (lim[it] < nact) ? gofs[it] : OOB, so, 0);
+                }
+            } else if constexpr (THIN) {
+#pragma unroll
+                for (int it = 0; it < NLD; ++it) {
+                    int row, col, oct;
+                    const bool ex = thin_slot(it, row, col, oct);
+                    const int gy = gy0 + row, gx = gx0 + col;
+                    const bool ok = ex & (row < nrows) & ((unsigned)gy < (unsigned)H) & ((unsigned)gx < (unsigned)W);
+                    im.s[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? (gy * W + gx) * ipb + 16 * oct : OOB, 0, 0);
                 }
             } else {
 #pragma unroll
@@ -716,6 +781,18 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
         for (int i = 0; i < 16; ++i) a[i] = bq[i] = c[i] = 0.f;
         bf16x8 fb[6];
+        // THIN: the thin weight image goes to LDS behind the staging rows (768 slots of 16 bytes, three per compute thread; the barrier
+        // below publishes it); tw: this lane's A operand of (tap row 0, slice 0); tl0 / tl1: the ninth octet of the pixel one column
+        // shift h / shift 2 - h to the right, relative to the lane's B operand base
+        const char* tw = nullptr;
+        const int tl0 = h * PIXB + 128 - 16 * h, tl1 = (2 - h) * PIXB + 128 - 16 * h;
+        if constexpr (THIN) {
+            char* lthin = lstg + STGB;
+            const u32x4* src = reinterpret_cast<const u32x4*>(wp + 9 * 64 * 64);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) *reinterpret_cast<u32x4*>(lthin + (threadIdx.x + 256 * j) * 16) = src[threadIdx.x + 256 * j];
+            tw = lthin + (h * 64 + ct * 32 + r) * 16;
+        }
         auto rbase = [&](int mm) __attribute__((always_inline)) { return lring + (mm & 7) * RROW + lane_base; };
         auto issue3 = [&](const char* rb) __attribute__((always_inline)) {
             if (!(P4C_EXP & 16)) {
@@ -731,7 +808,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     {                                                                                                                       \
         const bool pf = ((m & (IV - 1)) != IV - 1) && (m != last);                                                          \
         if (wv == 0) P4C_STAMP_ROW(300 + 2 * m);                                                                            \
-        conv_row<HP, HQ, HS>(A, P, Q, S, fb, rbase(m), rbase(m + 1), pf, lstg + (m & 7) * SROW, soff);                     \
+        conv_row<HP, HQ, HS, THIN>(A, P, Q, S, fb, rbase(m), rbase(m + 1), pf, lstg + (m & 7) * SROW, soff, tw, tl0, tl1); \
         if (wv == 0) P4C_STAMP_ROW(301 + 2 * m);                                                                            \
         if (m == last) {                                                                                                    \
             P4C_STAMP(700 + 8 * (m >> 2) + 2 * wv);                                                                         \
@@ -842,6 +919,19 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         if (P4C_EXP & 16) { asm volatile("" ::"v"(A[0][0][0]), "v"(A[8][1][1])); }
     }
     if (wv == 0) P4C_STAMP(12);
+}
+
+template <int MODE, bool BST, int MF, int KS, bool CPT = false, int IV = 4>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+    conv3x3_bf16_rows_kernel(RowsArgs args) {
+    conv3x3_bf16_rows_body<MODE, BST, MF, KS, CPT, IV, false>(args);
+}
+
+// the first convolution at 65..72 input channels in one launch (THIN above): LDS = ring + staging + the 12 KB thin weight image
+constexpr int THIN_IMG_BYTES = 3 * 2 * 2 * 64 * 16;
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+    conv3x3_bf16_rows_thin_kernel(RowsArgs args) {
+    conv3x3_bf16_rows_body<0, false, 32, 3, true, 4, true>(args);
 }
 
 static int rows_mfma_shape() {   // 32 (default): v_mfma_f32_32x32x16_bf16; P4C_ROWS_MFMA=16: v_mfma_f32_16x16x32_bf16 (A/B runs: 15 % faster in a bare MFMA loop, tools/diagnostics/mfma_power.hip, but 2-5 % slower here -- its 16-cycle MFMAs leave the memory-side waves half the issue slots)
@@ -962,7 +1052,33 @@ int launch_conv_bf16_rows_wide_pixels(const void* in, int pixel_channels, const 
     conv_rows_geometry(B, H, W, &nstrips, &nseg);
     const int rc = launch_rows_compact<3>((const __bf16*)in, pixel_channels, (const __bf16*)wp, (__bf16*)out, 64, B, H, W, nstrips, nseg, stream);
     if (rc != P4C_OK) return rc;
+    count_first_conv_launch();
     P4C_CHECK_LAUNCH("conv_bf16_rows_wide_pixels");
+    return P4C_OK;
+}
+
+// The first convolution at 65..72 input channels in ONE launch (conv3x3_bf16_rows_thin_kernel): in (B,H,W,pixel_channels >= 72) ->
+// out (B,H,W,64), rounded once from the fp32 sum over all channels; wp = first_conv_one_image_bytes() of prepared weights (the row image
+// of channels 0..63, then the thin image: prep_weights_batch with PrepJob::thin); stat_partial (or null): conv_rows_stat_slots(B,H,W)
+// slots of [2][64] sums / sums of squares of the stored values per sample, left by the drain like every row launch's.
+size_t first_conv_one_image_bytes() { return (size_t)9 * 64 * 64 * 2 + THIN_IMG_BYTES; }
+bool first_conv_one_ok(int pixel_channels, int B, int H, int W) {
+    return pixel_channels >= 72 && pixel_channels % 8 == 0 && conv_bf16_is_rows(P4C_BF16, 64, 3, 1, 64, B, H, W) &&
+           (int64_t)H * W * pixel_channels * 2 < (int64_t)1 << 31;
+}
+int launch_first_conv_one(const void* in, int pixel_channels, const void* wp, void* out, float* stat_partial, int B, int H, int W,
+                          hipStream_t stream) {
+    if (!first_conv_one_ok(pixel_channels, B, H, W))
+        return fail(P4C_ERR_UNSUPPORTED, "first_conv_one: unsupported shape (%d-channel pixels, %dx%dx%d)", pixel_channels, B, H, W);
+    int nstrips, nseg;
+    conv_rows_geometry(B, H, W, &nstrips, &nseg);
+    const RowsArgs args{(const __bf16*)in, (const __bf16*)wp, nullptr, nullptr, (__bf16*)out, stat_partial, 64, H, W, H / nseg, H % nseg, 0,
+                        pixel_channels, RingBwdStats{}, NormBwdCoef{}, BatchFin{}};
+    constexpr int smem = rows::Lay<32>::SMEM + THIN_IMG_BYTES;
+    P4C_TRY(ensure_dyn_smem((const void*)conv3x3_bf16_rows_thin_kernel, smem));
+    hipLaunchKernelGGL(conv3x3_bf16_rows_thin_kernel, dim3(nseg, nstrips, B), dim3(512), smem, stream, args);
+    count_first_conv_launch();
+    P4C_CHECK_LAUNCH("first_conv_one");
     return P4C_OK;
 }
 

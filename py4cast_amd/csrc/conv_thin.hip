@@ -10,9 +10,13 @@
 // The generic role-split kernel it replaces (conv_fwd_bf16_kernel<96, 3>) took 91-100 us per launch x 3 AR steps for 1.5 x the matrix
 // work of a 64-channel launch that takes 39-43.  Numerics: y1 is rounded to bf16 before the tail adds its fp32 product
 // -- a second rounding that the one-launch form does not have; inside every bar the bf16 flavour is held to (the fp32 flavour keeps the
-// one-launch kernel).  The backward: data gradient = a 64 -> 64 row launch on the state channels; weight gradient = the row-streaming
-// kernel's full chunk + conv3x3_wgrad_thin_bf16_kernel (below) for the rows of the channels beyond 64.
+// one-launch kernel).  Since then the plan runs the convolution as ONE launch of the row kernel that carries the octet beyond 64 itself
+// (conv_rows.hip: THIN; first_conv_one_routed below) -- this two-launch form stays as the route of P4C_FIRST_CONV_ONE=0 (diagnostic
+// build), as the reference of the parity tests and behind p4c_first_conv_tail / p4c_first_conv_two.  The backward: data gradient = a
+// 64 -> 64 row launch on the state channels; weight gradient = the row-streaming kernel's full chunk + conv3x3_wgrad_thin_bf16_kernel (below) for the rows of the channels beyond 64.
 #include <stdlib.h>
+
+#include <atomic>
 
 #include "kernels.hpp"
 
@@ -174,11 +178,25 @@ bool first_conv_split_ok(int compute, int storage, int cin, int cin_pad, int B, 
            conv_bf16_is_rows(storage, 64, 3, 1, 64, B, H, W) && (int64_t)H * W * 192 < ((int64_t)1 << 31);
 }
 
+// ... and of those shapes, the ones the plan runs as ONE launch of the row kernel (conv_rows.hip: THIN) instead of row launch + tail
+bool first_conv_one_routed(int compute, int storage, int cin, int cin_pad, int B, int H, int W) {
+    const char* e = diag_env("P4C_FIRST_CONV_ONE");         // (A/B switch of the diagnostic build: 0 = row launch + tail)
+    if (e && e[0] == '0') return false;
+    return first_conv_split_ok(compute, storage, cin, cin_pad, B, H, W) && first_conv_one_ok(cin_pad, B, H, W);
+}
+
 int first_conv_tail_slots(int B, int H, int W) { return tail_blocks(B, H, W) * 4; }
+
+// kernels this process has enqueued for the first convolution at 65..72 input channels, counted where they are launched (the
+// one-launch row kernel, the row launch on wide pixels, the tail): p4c_first_conv_launch_count, what the route test asserts on
+static std::atomic<long long> g_first_conv_launches{0};
+void count_first_conv_launch() { g_first_conv_launches.fetch_add(1); }
+long long first_conv_launches() { return g_first_conv_launches.load(); }
 
 int launch_first_conv_tail(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W, hipStream_t stream) {
     ThinArgs a{(const __bf16*)x, w, (__bf16*)y, stat_partial, x_cs, 64, cin - 64, cin, H, W, tail_blocks(B, H, W)};
     hipLaunchKernelGGL(first_conv_tail_kernel, dim3(a.nblk, B), dim3(256), 0, stream, a);
+    count_first_conv_launch();
     P4C_CHECK_LAUNCH("first_conv_tail");
     return P4C_OK;
 }
@@ -416,4 +434,53 @@ extern "C" int p4c_first_conv_tail(const void* x, int x_cs, int cin, const float
     P4C_CHECK_ARG(cin > 64 && cin <= 72 && x_cs >= 72 && x_cs % 8 == 0 && W % 32 == 0 && B > 0 && H > 0,
                   "p4c_first_conv_tail: 65..72 input channels on pixels of >= 72 channels (multiple of 8), W a multiple of 32");
     return p4c::launch_first_conv_tail(x, x_cs, cin, w, y, stat_partial, B, H, W, p4c::as_stream(stream));
+}
+
+// single-op entry points (tests, micro-benchmarks) of the whole first convolution: y (B,H,W,64) bf16 = conv3x3 of channels 0 .. cin-1 of
+// x (B,H,W,x_cs) bf16 with the fp32 master weight w [64][cin][3][3], prepared here into a stream-ordered temporary.
+//   p4c_first_conv_one: ONE launch of the row kernel (conv_rows.hip: THIN), y rounded once; stat_partial (or NULL):
+//                       p4c_first_conv_one_slots(B,H,W) slots of [2][64] per sample
+//   p4c_first_conv_two: row launch on channels 0..63 + tail, what P4C_FIRST_CONV_ONE=0 runs; slots: p4c_first_conv_tail_slots
+namespace p4c {
+namespace {
+int first_conv_single_op(bool one, const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W,
+                         hipStream_t st) {
+    void* img = nullptr;
+    P4C_CHECK_HIP(hipMallocAsync(&img, first_conv_one_image_bytes(), st));
+    PrepBatch pb;
+    pb.n = 0;
+    pb.bf16 = 1;
+    pb.zero_words = nullptr;
+    pb.n_zero = 0;
+    pb.job[pb.n++] = {w, img, 64, cin, 9, 0, 64, 64};
+    if (one) pb.job[pb.n++] = {w, (char*)img + 9 * 64 * 64 * 2, 64, cin, 6, 0, 64, 16, 1};
+    int rc = prep_weights_batch(pb, st);
+    if (rc == P4C_OK) {
+        if (one) {
+            rc = launch_first_conv_one(x, x_cs, img, y, stat_partial, B, H, W, st);
+        } else {
+            rc = launch_conv_bf16_rows_wide_pixels(x, x_cs, img, y, B, H, W, st);
+            if (rc == P4C_OK) rc = launch_first_conv_tail(x, x_cs, cin, w, y, stat_partial, B, H, W, st);
+        }
+    }
+    (void)hipFreeAsync(img, st);
+    return rc;
+}
+}  // namespace
+}  // namespace p4c
+extern "C" long long p4c_first_conv_launch_count(void) { return p4c::first_conv_launches(); }
+extern "C" int p4c_first_conv_one_slots(int B, int H, int W) { return p4c::conv_rows_stat_slots(B, H, W); }
+extern "C" int p4c_first_conv_one(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W,
+                                  p4c_stream_t stream) {
+    P4C_CHECK_ARG(x && w && y, "p4c_first_conv_one: NULL pointer");
+    P4C_CHECK_ARG(cin > 64 && cin <= 72 && x_cs >= 72 && x_cs % 8 == 0 && W % 32 == 0 && B > 0 && H > 0,
+                  "p4c_first_conv_one: 65..72 input channels on pixels of >= 72 channels (multiple of 8), W a multiple of 32");
+    return p4c::first_conv_single_op(true, x, x_cs, cin, w, y, stat_partial, B, H, W, p4c::as_stream(stream));
+}
+extern "C" int p4c_first_conv_two(const void* x, int x_cs, int cin, const float* w, void* y, float* stat_partial, int B, int H, int W,
+                                  p4c_stream_t stream) {
+    P4C_CHECK_ARG(x && w && y, "p4c_first_conv_two: NULL pointer");
+    P4C_CHECK_ARG(cin > 64 && cin <= 72 && x_cs >= 72 && x_cs % 8 == 0 && W % 32 == 0 && B > 0 && H > 0,
+                  "p4c_first_conv_two: 65..72 input channels on pixels of >= 72 channels (multiple of 8), W a multiple of 32");
+    return p4c::first_conv_single_op(false, x, x_cs, cin, w, y, stat_partial, B, H, W, p4c::as_stream(stream));
 }

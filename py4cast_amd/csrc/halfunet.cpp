@@ -233,7 +233,13 @@ int prepare_weights(const p4c_halfunet_desc& d, const WS& ws, const float* param
     if (which & 1) pb.job[pb.n++] = {params + L.wout, wslot(ws, 2 * NCONV), d.cout, NF, 1, 0, 64, NF};
     // the first convolution as a 64-channel row launch + tail (conv_thin.hip): the row kernel's image of input channels 0..63
     if ((which & 1) && first_conv_split_ok(d.compute, d.dtype, d.cin, d.cin_pad, d.B, d.H, d.W))
+    {
         pb.job[pb.n++] = {params + L.w[0], wslot(ws, 2 * NCONV + 2), NF, d.cin, 9, 0, 64, NF};
+        // ... and, behind it in the same slot, the thin image of channels 64..71 that the one-launch form multiplies in the row kernel
+        // (whenever the split applies, not only while the one-launch route is switched on: the diagnostic build re-reads its switch per call)
+        if (first_conv_one_ok(d.cin_pad, d.B, d.H, d.W))
+            pb.job[pb.n++] = {params + L.w[0], static_cast<char*>(wslot(ws, 2 * NCONV + 2)) + 9 * 64 * NF * 2, NF, d.cin, 6, 0, 64, 16, 1};
+    }
     if (which & 2) pb.job[pb.n++] = {params + L.wout, wslot(ws, 2 * NCONV + 1), d.cout, NF, 1, 1, 64, NF};
     pb.zero_words = reinterpret_cast<unsigned int*>(ws.f(L.tickets));
     pb.n_zero = 64;
@@ -296,6 +302,11 @@ int conv_block_fwd(const p4c_halfunet_desc& d, const WS& ws, int i, const void* 
                                           infin && handoff != 1 ? &fin : nullptr, handoff == 2 ? &pre : nullptr));
         if (handoff == 1) return P4C_OK;
         ntiles = conv_small_stat_slots(d.B, H, W);
+    } else if (i == 0 && !in_norm && first_conv_one_routed(d.compute, d.dtype, d.cin, d.cin_pad, d.B, H, W)) {
+        // 69 -> 64 at the benchmark's channel count in ONE launch: the row kernel on channels 0..63 of the 96-channel pixels also carries
+        // the octet beyond them, rounds y once and leaves the statistics from its drain, like every other row launch (conv_rows.hip: THIN)
+        P4C_TRY(launch_first_conv_one(in, d.cin_pad, wslot(ws, 2 * NCONV + 2), ws.act(L.Y[i]), statp, d.B, H, W, st));
+        ntiles = conv_rows_stat_slots(d.B, H, W);
     } else if (i == 0 && !in_norm && first_conv_split_ok(d.compute, d.dtype, d.cin, d.cin_pad, d.B, H, W)) {
         // 69 -> 64 at the benchmark's channel count: a 64-channel row launch on channels 0..63 of the 96-channel pixels, then the tail
         // adds the product of the channels beyond 64 and takes the statistics of the result (conv_thin.hip)

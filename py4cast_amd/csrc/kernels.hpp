@@ -46,6 +46,10 @@ struct PrepJob {
     const float* w;   // canonical torch weight [CO][CI][ks][ks]
     void* out;        // prepared operand stream
     int CO, CI, ntaps, transpose_flip, M_pad, K_pad;
+    // 1: the thin image of a 3x3 weight's input channels 64..71 for the one-launch first convolution (conv_rows.hip: THIN) --
+    // [tap row][slice][k half][64 co][8 channels] bf16, column shift 2 * slice + k half (the fourth shift and channels >= CI zero);
+    // set ntaps = 6 (tap row x slice), M_pad = 64, K_pad = 16
+    int thin = 0;
 };
 struct PrepBatch {
     PrepJob job[32];
@@ -191,6 +195,15 @@ int conv_wgrad_thin_slots(int G, int B, int H, int W, int* nseg_out = nullptr);
 int launch_conv3x3_wgrad_thin_bf16(const void* x, int in_cs, const void* dout, float* partial, int G, int B, int H, int W, hipStream_t stream,
                                    int* nslots_out);
 int launch_conv_bf16_rows_wide_pixels(const void* in, int pixel_channels, const void* wp, void* out, int B, int H, int W, hipStream_t stream);
+// conv_rows.hip: the same first convolution in ONE launch -- the row kernel also carries the channel octet beyond 64 (its loaders keep it
+// in the pad slot of the LDS pixels), rounds y once and takes the statistics in its drain: conv_rows_stat_slots(B,H,W) slots per sample.
+// wp: first_conv_one_image_bytes() = the row image of channels 0..63 followed by the thin image (PrepJob::thin)
+bool first_conv_one_ok(int pixel_channels, int B, int H, int W);
+bool first_conv_one_routed(int compute, int storage, int cin, int cin_pad, int B, int H, int W);   // the plan's route (P4C_FIRST_CONV_ONE=0: two launches)
+size_t first_conv_one_image_bytes();
+void count_first_conv_launch();   // conv_thin.hip: one per kernel enqueued for this convolution (p4c_first_conv_launch_count)
+int launch_first_conv_one(const void* in, int pixel_channels, const void* wp, void* out, float* stat_partial, int B, int H, int W,
+                          hipStream_t stream);
 
 // norm_pool.hip
 int norm_finalize(const float* partial, int tiles_per_sample, int B, int64_t hw, int mode, int groups, const float* gamma,
