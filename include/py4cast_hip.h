@@ -419,6 +419,45 @@ int p4c_grib_pack(const float* pred, int64_t pred_bs, int64_t pred_ts, const int
                   const int32_t* features, const int32_t* spec, int flip_rows, int32_t* params, unsigned char* packed, int64_t pitch,
                   void* workspace, int B, int n, int T, int H, int W, int F, int K, p4c_stream_t stream);
 
+/* GRIB2 complex packing (data representation template 5.2) and complex packing with spatial differencing (5.3) of the forecast: the
+ * opt-in route beside p4c_grib_pack, for templates whose messages are complex-packed (csrc/grib_pack_complex.hip).
+ *
+ * p4c_grib_pack_complex: arguments as p4c_grib_pack, but `spec` is HOST int32 (K,3): D, nbits and the order of the spatial
+ * differencing (0: template 5.2; 1, 2: template 5.3), and the streams go to ONE byte buffer `out` of `out_bytes` bytes:
+ *   params (n,T,K,P) int32, P = p4c_grib_pack_complex_params() = 11:
+ *       0 vmin, 1 vmax, 2 R (the bits of three fp32), 3 E, 4 bad -- the five words of p4c_grib_pack --, 5 ival1, 6 ival2, 7 gmin,
+ *       8 ref_bits (octet 20 of section 5), 9 the payload's length in octets, 10 its offset in `out`;
+ *   out: the section-7 payload of field (s,t,k) at out[offset .. offset + length).  Offsets are multiples of 4 and follow
+ *       (sample, lead time, feature) order: offset = the sum of the lengths, each rounded up to 4, of the fields before it.  A field
+ *       with bad > 0 has length 0.  No byte outside the payloads is written.
+ * One field: X as in p4c_grib_pack (so the field decodes to the same fp32 plane).  Order 0: d[q] = X[q]; 1: d[q] = X[q] - X[q-1] for
+ * q >= 1; 2: d[q] = X[q] - 2 X[q-1] + X[q-2] for q >= 2.  gmin = min of d over q >= order (0 at order 0 and without such a q);
+ * X'[q] = d[q] - gmin, 0 for q < order; ival1 = X[0], ival2 = X[1] (order 2; 0 where absent).  Groups of
+ * p4c_grib_pack_complex_group() = 32 values, the last one N - 32 (ng - 1), ng = ceil(N / 32): ref[g] = min X' of the group,
+ * width[g] = the bits of (max X' - min X'), ref_bits = the bits of the largest ref[g].  The payload, each part zero-padded to an
+ * octet: the descriptors (order >= 1: ival1, [ival2,] gmin; 4 octets each, sign and magnitude), ng references of ref_bits bits, ng
+ * widths of 6 bits, the values X' - ref[g] in width[g] bits, most significant bit first, group after group.  Section 5 around it:
+ * general group splitting, w_ref = 0, w_bits = 6, l_ref = 32, l_inc = 1, l_bits = 0 (no table of lengths), l_last = N - 32 (ng - 1),
+ * 4 octets per descriptor, no missing value management.
+ * p4c_grib_pack_complex_capacity(n,T,N,spec,K): the bytes `out` must hold: per field 4 (order + 1) descriptor octets at order >= 1,
+ * 4 per reference, ceil(6 ng / 8) for the widths, 4 ng (nbits + order) for the values, rounded up to 4; -1 for a spec outside the
+ * limits.  Seven launches (range and finish of p4c_grib_pack; group, scan, offsets, tables, pack), no atomics: two calls give the
+ * same bytes.  `workspace`: p4c_grib_pack_complex_workspace_bytes(n,T,N,K,F) bytes, 16-byte aligned (in the gather form it also
+ * holds the differences of the group pass, 4 bytes per value, which the pack pass reads instead of the prediction).  Tiles and workgroups per launch
+ * as p4c_grib_tile / p4c_grib_max_blocks say; the scan, offsets and tables launches take
+ * p4c_grib_pack_complex_scan_threads() groups (fields; 8 times as many groups) per loop trip of a workgroup.
+ * Errors (nothing is launched): those of p4c_grib_pack on pointers, dims, samples, D and nbits; an order outside 0 .. 2; at orders
+ * 1 and 2 nbits + order > 31; `out` not 4-byte aligned or out_bytes below the capacity; a capacity of 2^31 bytes or more. */
+int p4c_grib_pack_complex_group(void);
+int p4c_grib_pack_complex_params(void);
+int p4c_grib_pack_complex_scan_threads(void);
+int64_t p4c_grib_pack_complex_capacity(int n, int T, int64_t N, const int32_t* spec, int K);
+size_t p4c_grib_pack_complex_workspace_bytes(int n, int T, int64_t N, int K, int F);
+int p4c_grib_pack_complex(const float* pred, int64_t pred_bs, int64_t pred_ts, const int32_t* samples, const float* std,
+                          const float* mean, const int32_t* features, const int32_t* spec, int flip_rows, int32_t* params,
+                          unsigned char* out, int64_t out_bytes, void* workspace, int B, int n, int T, int H, int W, int F, int K,
+                          p4c_stream_t stream);
+
 /* Reading GRIB2 on the device: the decode of simple packing (data representation template 5.0), the other end of p4c_grib_pack.
  * The bit streams (section 7) and bitmaps (section 6) of a batch lie in ONE device byte buffer as they are on disk; the message
  * headers stay with the caller (py4cast_amd/grib2.py: field_of).

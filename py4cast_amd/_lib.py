@@ -65,6 +65,8 @@ SIGNATURES = {
     "p4c_forecast_frames": [P, L, L, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, P],
     # pred, bs, ts, samples (host), std, mean, features, spec (host), flip_rows, params, packed, pitch, ws, B, n, T, H, W, F, K, stream
     "p4c_grib_pack": [P, L, L, P, P, P, P, P, I, P, P, L, P, I, I, I, I, I, I, I, P],
+    # pred, bs, ts, samples (host), std, mean, features, spec (host, K x 3), flip_rows, params, out, out_bytes, ws, B, n, T, H, W, F, K, stream
+    "p4c_grib_pack_complex": [P, L, L, P, P, P, P, P, I, P, P, L, P, I, I, I, I, I, I, I, P],
     # bytes, nbytes, fields (device), fields (host), nfields, planes, ws, stream
     "p4c_grib_unpack": [P, L, P, P, I, P, P, P],
     # bytes, nbytes, fields (device), fields (host), nfields, planes, status, ws, stream
@@ -122,6 +124,11 @@ OTHER = {
     "p4c_grib_max_features": ([], c_int),
     "p4c_grib_max_samples": ([], c_int),
     "p4c_grib_pack_dense": ([I, I], c_int),
+    "p4c_grib_pack_complex_group": ([], c_int),
+    "p4c_grib_pack_complex_params": ([], c_int),
+    "p4c_grib_pack_complex_scan_threads": ([], c_int),
+    "p4c_grib_pack_complex_capacity": ([I, I, L, P, I], c_int64),
+    "p4c_grib_pack_complex_workspace_bytes": ([I, I, L, I, I], c_size_t),
     "p4c_grib_unpack_tile": ([], c_int),
     "p4c_grib_unpack_max_blocks": ([], c_int),
     "p4c_grib_unpack_fast": ([I, I], c_int),

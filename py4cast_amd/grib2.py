@@ -52,7 +52,10 @@ Complex packing (5.2) and complex packing with spatial differencing (5.3), as g2
 ``width[g] = w_ref + w[g]``, ``len[g] = l_ref + l_inc * l[g]``, the last group's length is octets 43-46 whatever its stored length
 says, a table of 0 bits is absent (all 0).  ``X[k] = ref[g] + value``; 5.2: f = X; 5.3 order 1: f[0] = ival1, f[k] = f[k-1] + X[k] +
 gmin; order 2: f[0] = ival1, f[1] = ival2, f[k] = X[k] + gmin + 2 f[k-1] - f[k-2]; integer arithmetic modulo 2^64, f signed;
-``Y = (R + f 2^E) / 10^D``.  Still out of scope and refused: 5.40, 5.41, 5.42, missing value management 1 and 2, group splitting
+``Y = (R + f 2^E) / 10^D``.  The writer's opt-in complex packing (``pack_complex``, ``encode(..., order=, ref_bits=)``,
+``ops.grib_pack_complex``, csrc/grib_pack_complex.hip) writes these templates with groups of 32 values: l_ref = 32, l_inc = 1, a
+table of lengths of 0 bits, w_ref = 0, widths in 6 bits, descriptors of 4 octets; ``packing_of`` tells which packing a template
+message asks for.  Still out of scope and refused: 5.40, 5.41, 5.42, missing value management 1 and 2, group splitting
 other than the general one.  Messages are found by the numeric keys above, never by ``shortName``.
 """
 import datetime as dt
@@ -314,12 +317,83 @@ def _time_in_unit(delta: dt.timedelta, what: str) -> Tuple[int, int]:
     return (UNIT_HOUR, seconds // 3600) if seconds % 3600 == 0 else (UNIT_MINUTE, seconds // 60)
 
 
+COMPLEX_GROUP = 32        # values of a group of the complex packing written here
+COMPLEX_W_BITS = 6        # bits of a stored group width
+COMPLEX_PARAMS = 11       # int32 words of a params record of ``ops.grib_pack_complex``
+
+
+def check_complex(nbits: int, order: int) -> None:
+    """The limits of the complex packing written here: order 0 (5.2) takes 1 .. 32 bits, orders 1 and 2 (5.3) need nbits + order <= 31,
+    so that every descriptor fits sign and magnitude in 4 octets and every X', reference and width fits 32 bits"""
+    if order not in (0, 1, 2):
+        raise GribError(f"spatial differencing of order {order}: 0 (template 5.2), 1 and 2 (template 5.3) are written")
+    if not 1 <= nbits <= 32 or (order and nbits + order > 31):
+        raise GribError(f"nbits = {nbits} at order {order}: 1 <= nbits <= 32 at order 0, nbits + order <= 31 at orders 1 and 2")
+
+
+def complex_capacity(N: int, nbits: int, order: int) -> int:
+    """the worst case of one field's payload, rounded up to 4 (p4c_grib_pack_complex_capacity sums these over a call's fields)"""
+    ng = (N + COMPLEX_GROUP - 1) // COMPLEX_GROUP
+    octets = (4 * (order + 1) if order else 0) + 4 * ng + (COMPLEX_W_BITS * ng + 7) // 8 + 4 * ng * (nbits + order)
+    return (octets + 3) // 4 * 4
+
+
+def packing_of(m: Message) -> Optional[int]:
+    """How a template message is packed, for the writer's ``packing="template"``: None for simple packing (5.0), the order of the
+    spatial differencing for complex packing: 0 for 5.2, octet 48 (1 or 2) for 5.3.  Anything else raises with its octet."""
+    s5 = m.sections[5]
+    number = _u(s5, 10, 2) if len(s5) >= 11 else -1
+    if number == 0:
+        return None
+    if number not in COMPLEX_TEMPLATES:
+        raise GribError(f"section 5 octets 10-11: data representation template 5.{number}; a template message in 5.0, 5.2 or 5.3 is followed")
+    octets = 47 if number == 2 else 49
+    if len(s5) < octets:
+        raise GribError(f"section 5 octets 1-4: {len(s5)} octets; template 5.{number} has {octets}")
+    if number == 2:
+        return 0
+    if s5[47] not in (1, 2):
+        raise GribError(f"section 5 octet 48: spatial differencing of order {s5[47]}; 1 and 2 are written")
+    return int(s5[47])
+
+
+def complex_section5(count: int, R: float, E: int, D: int, order: int, ref_bits: int) -> bytearray:
+    """Section 5 of a field as ``pack_complex`` lays it out: template 5.2 (order 0, 47 octets) or 5.3 (49 octets); general group
+    splitting, no missing value management, groups of 32 values with no table of lengths (l_ref = 32, l_inc = 1, l_bits = 0), widths in
+    6 bits from 0, descriptors of 4 octets"""
+    ng = (count + COMPLEX_GROUP - 1) // COMPLEX_GROUP
+    s5 = bytearray(49 if order else 47)
+    _put_u(s5, 1, 4, len(s5))
+    s5[4] = 5
+    _put_u(s5, 6, 4, count)
+    _put_u(s5, 10, 2, 3 if order else 2)
+    s5[11:15] = struct.pack(">f", R)
+    _put_s(s5, 16, 2, E)
+    _put_s(s5, 18, 2, D)
+    s5[19] = ref_bits
+    s5[20] = 0                         # type of original values: floating point
+    s5[21] = 1                         # general group splitting
+    s5[22] = 0                         # no missing value management
+    _put_u(s5, 32, 4, ng)
+    s5[35], s5[36] = 0, COMPLEX_W_BITS
+    _put_u(s5, 38, 4, COMPLEX_GROUP)
+    s5[41] = 1
+    _put_u(s5, 43, 4, count - COMPLEX_GROUP * (ng - 1) if ng else 0)
+    s5[46] = 0
+    if order:
+        s5[47], s5[48] = order, 4
+    return s5
+
+
 def encode(template_message: Message, basis: dt.datetime, term: dt.timedelta, *, cumulative: Optional[dt.timedelta] = None,
-           window: Tuple[int, int, int, int], packed: bytes, R: float, E: int, D: int, nbits: int) -> bytes:
+           window: Tuple[int, int, int, int], packed: bytes, R: float, E: int, D: int, nbits: int, order: Optional[int] = None,
+           ref_bits: int = 0) -> bytes:
     """A new message: sections 0-4 of ``template_message`` with the reference time (``basis``) and the forecast time (``term``; for
     template 4.8 the interval of length ``cumulative`` that ENDS at basis + term) patched in, and new sections 5-7 around ``packed``,
     the simple-packed stream of the ``window`` (first row, last row, first column, last column of the template grid in stream order;
-    the points outside it are absent in the bitmap)."""
+    the points outside it are absent in the bitmap).  With ``order`` (0: template 5.2; 1, 2: template 5.3) ``packed`` is the payload
+    of ``pack_complex`` / ``ops.grib_pack_complex`` and ``ref_bits`` its octet 20: section 5 then has 47 or 49 octets and says groups
+    of 32 values (``complex_section5``)."""
     m = template_message
     check_grid(m)
     check_product(m)
@@ -331,7 +405,14 @@ def encode(template_message: Message, basis: dt.datetime, term: dt.timedelta, *,
         raise GribError(f"D = {D}, nbits = {nbits}: |D| <= {MAX_D} and 1 <= nbits <= 32 are packed")
     count = (r1 - r0 + 1) * (c1 - c0 + 1)
     packed = bytes(packed)
-    if len(packed) != (count * nbits + 7) // 8:
+    if order is not None:
+        check_complex(nbits, order)
+        ng = (count + COMPLEX_GROUP - 1) // COMPLEX_GROUP
+        head = (4 * (order + 1) if order else 0) + (ng * ref_bits + 7) // 8 + (ng * COMPLEX_W_BITS + 7) // 8
+        if not 0 <= ref_bits <= 32 or not head <= len(packed) <= complex_capacity(count, nbits, order):
+            raise GribError(f"{len(packed)} octets of payload, {ref_bits} bits per group reference for {count} values of {nbits} bits "
+                            f"at order {order}")
+    elif len(packed) != (count * nbits + 7) // 8:
         raise GribError(f"{len(packed)} packed octets for {count} values of {nbits} bits")
     s1 = bytearray(m.sections[1])
     _put_u(s1, 13, 2, basis.year)
@@ -353,14 +434,17 @@ def encode(template_message: Message, basis: dt.datetime, term: dt.timedelta, *,
         unit, value = _time_in_unit(term, "term")
     s4[17] = unit
     _put_u(s4, 19, 4, value)
-    s5 = bytearray(21)
-    _put_u(s5, 1, 4, 21)
-    s5[4] = 5
-    _put_u(s5, 6, 4, count)
-    s5[11:15] = struct.pack(">f", R)
-    _put_s(s5, 16, 2, E)
-    _put_s(s5, 18, 2, D)
-    s5[19] = nbits
+    if order is not None:
+        s5 = complex_section5(count, R, E, D, order, ref_bits)
+    else:
+        s5 = bytearray(21)
+        _put_u(s5, 1, 4, 21)
+        s5[4] = 5
+        _put_u(s5, 6, 4, count)
+        s5[11:15] = struct.pack(">f", R)
+        _put_s(s5, 16, 2, E)
+        _put_s(s5, 18, 2, D)
+        s5[19] = nbits
     bitmap = _bitmap(Nj, Ni, (r0, r1, c0, c1))
     s6 = bytearray(6)
     _put_u(s6, 1, 4, 6 + (len(bitmap) if bitmap is not None else 0))
@@ -706,8 +790,8 @@ class GribFile:
 
 
 # ------------------------------------------------------------------------------------------------ the packer on the CPU
-def pack_simple(v: np.ndarray, D: int, nbits: int):
-    """The contract of csrc/grib_pack.hip for one field in stream order: v fp32 (N,) -> (vmin, vmax, R, E, bad, the stream's bytes)"""
+def _quantise(v: np.ndarray, D: int, nbits: int):
+    """the quantisation of csrc/grib_pack.hip: v fp32 (N,) -> (vmin, vmax, R, E, bad, X uint64)"""
     if abs(D) > MAX_D or not 1 <= nbits <= 32:
         raise GribError(f"D = {D}, nbits = {nbits}: |D| <= {MAX_D} and 1 <= nbits <= 32 are packed")
     v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
@@ -735,16 +819,107 @@ def pack_simple(v: np.ndarray, D: int, nbits: int):
     with np.errstate(all="ignore"):
         X = np.floor(np.ldexp(s - float(R), -E) + 0.5)
         X = np.where(X < xmax, np.where(X > 0.0, X, 0.0), xmax).astype(np.uint64)
+    return vmin, vmax, R, E, bad, X
+
+
+def pack_simple(v: np.ndarray, D: int, nbits: int):
+    """The contract of csrc/grib_pack.hip for one field in stream order: v fp32 (N,) -> (vmin, vmax, R, E, bad, the stream's bytes)"""
+    vmin, vmax, R, E, bad, X = _quantise(v, D, nbits)
     bits = ((X[:, None] >> np.arange(nbits - 1, -1, -1, dtype=np.uint64)) & np.uint64(1)).astype(np.uint8)
     return vmin, vmax, R, E, bad, np.packbits(bits.reshape(-1)).tobytes()
 
 
+def _bit_lengths(a: np.ndarray) -> np.ndarray:
+    """the bit length of every element of a non-negative int64 array below 2^33"""
+    out = np.zeros(a.shape, dtype=np.int64)
+    for b in range(33):
+        out[a >= (1 << b)] = b + 1
+    return out
+
+
+def _table_bits(values: np.ndarray, width: int) -> np.ndarray:
+    """the integers ``values`` in ``width`` bits each, most significant bit first, zero-padded to an octet -> 0/1 uint8"""
+    if width == 0 or values.size == 0:
+        return np.zeros(0, dtype=np.uint8)
+    v = values.astype(np.uint64)
+    bits = ((v[:, None] >> np.arange(width - 1, -1, -1, dtype=np.uint64)) & np.uint64(1)).astype(np.uint8).reshape(-1)
+    return np.concatenate([bits, np.zeros(-bits.size % 8, dtype=np.uint8)])
+
+
+def pack_complex(v: np.ndarray, D: int, nbits: int, order: int):
+    """The contract of csrc/grib_pack_complex.hip for one field in stream order: v fp32 (N,) -> (vmin, vmax, R, E, bad, numbers,
+    payload).  X is that of ``pack_simple``; order 0: d = X; 1: d[q] = X[q] - X[q-1]; 2: d[q] = X[q] - 2 X[q-1] + X[q-2]; gmin the
+    minimum of d over q >= order (0 at order 0 or without such a q); X' = d - gmin, 0 for q < order.  Groups of 32 values, the last one
+    shorter: reference min X', width the bits of max X' - min X'.  ``numbers``: ival1 = X[0], ival2 = X[1] (order 2), gmin, ref_bits
+    (the bits of the largest reference), ng, l_last.  ``payload``: the descriptors (order >= 1: ival1, [ival2,] gmin in 4 octets each,
+    sign and magnitude), the references in ref_bits bits, the widths in 6, the values X' - reference in their group's width, each part
+    zero-padded to an octet; empty for a field with bad > 0."""
+    check_complex(nbits, order)
+    vmin, vmax, R, E, bad, X = _quantise(v, D, nbits)
+    N = X.size
+    f = X.astype(np.int64)
+    d = f.copy()
+    if order == 1:
+        d[1:] = f[1:] - f[:-1]
+    elif order == 2:
+        d[2:] = f[2:] - 2 * f[1:-1] + f[:-2]
+    gmin = int(d[order:].min()) if order and N > order else 0
+    Xp = d - gmin
+    Xp[:order] = 0
+    starts = np.arange(0, N, COMPLEX_GROUP)
+    ng = starts.size
+    ref = np.minimum.reduceat(Xp, starts)
+    width = _bit_lengths(np.maximum.reduceat(Xp, starts) - ref)
+    ref_bits = int(_bit_lengths(ref.max(keepdims=True))[0])
+    numbers = dict(ival1=int(f[0]) if order else 0, ival2=int(f[1]) if order == 2 and N > 1 else 0, gmin=gmin, ref_bits=ref_bits, ng=ng,
+                   l_last=N - COMPLEX_GROUP * (ng - 1))
+    if bad:
+        return vmin, vmax, R, E, bad, numbers, b""
+    head = bytearray()
+    if order:
+        for value in ([numbers["ival1"], numbers["ival2"], gmin] if order == 2 else [numbers["ival1"], gmin]):
+            b = bytearray(4)
+            _put_s(b, 1, 4, value)
+            head += b
+    group = np.arange(N) // COMPLEX_GROUP
+    rest, wide = (Xp - ref[group]).astype(np.uint64), width[group]
+    length = np.diff(np.append(starts, N))
+    group_bits = length * width
+    first_bit = np.cumsum(group_bits) - group_bits                     # of a group: a multiple of 8, a full group is 4 w octets
+    at = first_bit[group] + (np.arange(N) - starts[group]) * wide
+    bits = np.zeros((int(group_bits.sum()) + 7) // 8 * 8, dtype=np.uint8)
+    for w in np.unique(wide):
+        if w:
+            mine = wide == w
+            idx = at[mine][:, None] + np.arange(w, dtype=np.int64)
+            bits[idx] = ((rest[mine][:, None] >> np.arange(w - 1, -1, -1, dtype=np.uint64)) & np.uint64(1)).astype(np.uint8)
+    stream = np.concatenate([_table_bits(ref, ref_bits), _table_bits(width, COMPLEX_W_BITS), bits])
+    return vmin, vmax, R, E, bad, numbers, bytes(head) + np.packbits(stream).tobytes()
+
+
 def pack_fields(pred: np.ndarray, std: np.ndarray, mean: np.ndarray, spec: Sequence[Tuple[int, int]], samples: Sequence[int],
-                features: Sequence[int], H: int, W: int, flip_rows: bool, pitch: int):
-    """``ops.grib_pack`` on the CPU: pred (B,T,N,F) fp32 normalised -> params (n,T,K,5) int32, packed (n,T,K,pitch) uint8"""
+                features: Sequence[int], H: int, W: int, flip_rows: bool, pitch: Optional[int] = None):
+    """``ops.grib_pack`` on the CPU: pred (B,T,N,F) fp32 normalised -> params (n,T,K,5) int32, packed (n,T,K,pitch) uint8.  With a
+    ``spec`` of (D, nbits, order) triples it is ``ops.grib_pack_complex``: params (n,T,K,11) int32 and one uint8 buffer of the call's
+    capacity with the payloads at their offsets, zero elsewhere."""
     pred = np.asarray(pred, dtype=np.float32)
     std, mean = np.asarray(std, dtype=np.float32), np.asarray(mean, dtype=np.float32)
     n, T, K = len(samples), pred.shape[1], len(features)
+    if len(spec) and len(spec[0]) == 3:
+        params = np.zeros((n, T, K, COMPLEX_PARAMS), dtype=np.int32)
+        out = np.zeros(n * T * sum(complex_capacity(H * W, nbits, order) for _, nbits, order in spec), dtype=np.uint8)
+        at = 0
+        for i, b in enumerate(samples):
+            for t in range(T):
+                for k, f in enumerate(features):
+                    a = pred[b, t, :, f] * std[f]
+                    v = (a + mean[f]).astype(np.float32).reshape(H, W)
+                    vmin, vmax, R, E, bad, nm, payload = pack_complex(v[::-1] if flip_rows else v, *spec[k])
+                    params[i, t, k, :3] = np.array([vmin, vmax, R], dtype=np.float32).view(np.int32)
+                    params[i, t, k, 3:] = (E, bad, nm["ival1"], nm["ival2"], nm["gmin"], nm["ref_bits"], len(payload), at)
+                    out[at:at + len(payload)] = np.frombuffer(payload, dtype=np.uint8)
+                    at += (len(payload) + 3) // 4 * 4
+        return params, out
     params = np.zeros((n, T, K, 5), dtype=np.int32)
     packed = np.zeros((n, T, K, pitch), dtype=np.uint8)
     for i, b in enumerate(samples):

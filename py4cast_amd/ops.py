@@ -885,6 +885,91 @@ def grib_pack(pred, std, mean, spec, samples=None, features=None, flip_rows=Fals
     return params, packed
 
 
+# ------------------------------------------------------------------------------------------------ GRIB2 complex packing
+# launch constants of csrc/grib_pack_complex.hip (p4c_grib_pack_complex_group() / _params() / _scan_threads() report the same); its
+# tiles and workgroups per launch are GRIB_TILE and GRIB_MAX_BLOCKS
+GRIB_COMPLEX_GROUP = 32         # values of a group
+GRIB_COMPLEX_PARAMS = 11        # int32 words of a params record: the five of grib_pack, ival1, ival2, gmin, ref_bits, length, offset
+GRIB_COMPLEX_SCAN_THREADS = 256  # groups (scan), fields (offsets), 8 groups each (tables) per loop trip of a workgroup
+
+
+def grib_complex_capacity(n: int, T: int, N: int, spec) -> int:
+    """bytes of ``grib_pack_complex``'s ``out``: the worst case of every field, each rounded up to 4 (p4c_grib_pack_complex_capacity)"""
+    from . import grib2
+
+    return n * T * sum(grib2.complex_capacity(N, int(nbits), int(order)) for _, nbits, order in spec)
+
+
+def grib_pack_complex(pred, std, mean, spec, samples=None, features=None, flip_rows=False, out=None):
+    """The normalised prediction (B,T,H,W,F) -- or (B,T,N,F) -- -> GRIB2 complex packing (templates 5.2 / 5.3; p4c_grib_pack_complex):
+    ``params`` (n,T,K,11) int32 -- the five words of ``grib_pack``, then ival1, ival2, gmin, ref_bits, the payload's length in octets
+    and its offset -- and ``stream``, one uint8 buffer of ``grib_complex_capacity`` bytes in which field (s,t,k)'s section-7 payload
+    lies at ``offset .. offset + length``; payloads follow each other in (sample, lead time, feature) order at multiples of 4, a field
+    with bad > 0 has length 0, no other byte is written.  ``spec``: one (D, nbits, order) per PACKED feature, order 0 (5.2), 1 or 2
+    (5.3); nbits 1 .. 32 at order 0, nbits + order <= 31 otherwise.  The integers are those of ``grib_pack``: a field decodes to the
+    same fp32 plane.  The contract is in include/py4cast_hip.h and, in numpy, ``grib2.pack_complex``.  ``samples``, ``features``,
+    ``flip_rows`` as in ``grib_pack``; ``out``: (params, stream) dense device tensors, stream 4-byte aligned and at least the capacity
+    long.  Not differentiable."""
+    L.require_cuda(pred, std, mean)
+    if pred.dim() not in (4, 5):
+        raise L.P4CError(f"grib_pack_complex: prediction {tuple(pred.shape)}: (B, T, H, W, F) or (B, T, N, F) expected")
+    B, T, F = pred.shape[0], pred.shape[1], pred.shape[-1]
+    H, W = (pred.shape[2], pred.shape[3]) if pred.dim() == 5 else (1, pred.shape[2])
+    if std.numel() != F or mean.numel() != F:
+        raise L.P4CError(f"grib_pack_complex: {std.numel()} standard deviations / {mean.numel()} means for {F} features")
+    features = tuple(range(F)) if features is None else tuple(int(f) for f in features)
+    samples = tuple(range(B)) if samples is None else tuple(int(s) for s in samples)
+    if any(len(tuple(entry)) != 3 for entry in spec):
+        raise L.P4CError(f"grib_pack_complex: spec {spec}: one (D, nbits, order) per packed feature expected")
+    spec = [(int(D), int(nbits), int(order)) for D, nbits, order in spec]
+    K, n = len(features), len(samples)
+    if not 1 <= K <= GRIB_MAX_FEATURES:
+        raise L.P4CError(f"grib_pack_complex: {K} features: 1 .. at most {GRIB_MAX_FEATURES} per call")
+    if len(spec) != K:
+        raise L.P4CError(f"grib_pack_complex: {len(spec)} (D, nbits, order) triples for {K} packed features")
+    if min(features) < 0 or max(features) >= F:
+        raise L.P4CError(f"grib_pack_complex: feature indices {features} leave 0 .. {F - 1}")
+    if not 1 <= n <= GRIB_MAX_SAMPLES or n * T > 65535:
+        raise L.P4CError(f"grib_pack_complex: {n} samples: 1 .. at most {GRIB_MAX_SAMPLES} per call, n*T <= 65535")
+    if min(samples) < 0 or max(samples) >= B:
+        raise L.P4CError(f"grib_pack_complex: sample indices {samples} leave 0 .. {B - 1}")
+    if any(abs(D) > 15 or not 1 <= nbits <= 32 or order not in (0, 1, 2) or (order and nbits + order > 31) for D, nbits, order in spec):
+        raise L.P4CError(f"grib_pack_complex: spec {spec}: |D| <= 15, an order of 0 .. 2, 1 <= nbits <= 32 at order 0 and "
+                         f"nbits + order <= 31 at orders 1 and 2 expected")
+    N = H * W
+    capacity = grib_complex_capacity(n, T, N, spec)
+    if capacity >= 2 ** 31:
+        raise L.P4CError(f"grib_pack_complex: {capacity} payload bytes in the worst case: fewer than 2^31 per call")
+    p, (pbs, pts) = _rows(pred.detach().float(), 2)
+    dev = p.device
+    std, mean = std.to(p).contiguous(), mean.to(p).contiguous()
+    index = _grib_features(features, dev.index if dev.index is not None else torch.cuda.current_device())
+    pshape = (n, T, K, GRIB_COMPLEX_PARAMS)
+    if out is None:
+        params = torch.empty(pshape, dtype=torch.int32, device=dev)
+        stream = torch.empty(capacity, dtype=torch.uint8, device=dev)
+    else:
+        params, stream = out
+        if (tuple(params.shape) != pshape or params.dtype != torch.int32 or not params.is_contiguous() or params.device != dev
+                or stream.dim() != 1 or stream.numel() < capacity or stream.dtype != torch.uint8 or not stream.is_contiguous()
+                or stream.device != dev or stream.data_ptr() % 4):
+            raise L.P4CError(f"grib_pack_complex: out: a dense int32 {pshape} and a dense, 4-byte aligned 1-D uint8 tensor of at least "
+                             f"{capacity} bytes on {dev} expected")
+    ws = torch.empty((L.lib().p4c_grib_pack_complex_workspace_bytes(n, T, N, K, F) + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    host_samples = (ctypes.c_int32 * n)(*samples)
+    host_spec = (ctypes.c_int32 * (3 * K))(*[x for triple in spec for x in triple])
+    dense = bool(L.lib().p4c_grib_pack_dense(K, F))
+    per_point = 4 * F if dense else min(4 * F, 64 * K)
+    # dense: three reads of the prediction (range, group, pack); gather: two, and the differences (4 bytes per value) written and read;
+    # the group records (16 + 4 bytes per 32 values) written and read twice; the payloads at their worst case
+    ng = (N + GRIB_COMPLEX_GROUP - 1) // GRIB_COMPLEX_GROUP
+    passes = N * 3 * per_point if dense else N * (2 * per_point + 8 * K)
+    L.call("p4c_grib_pack_complex", L.ptr(p), pbs, pts, host_samples, L.ptr(std), L.ptr(mean), L.ptr(index), host_spec,
+           int(bool(flip_rows)), L.ptr(params), L.ptr(stream), stream.numel(), L.ptr(ws), B, n, T, H, W, F, K, L.stream(dev),
+           alg_bytes=n * T * (passes + K * ng * 60) + capacity)
+    return params, stream
+
+
 # ------------------------------------------------------------------------------------------------ GRIB2 simple packing, decoded
 # launch constants of csrc/grib_unpack.hip (p4c_grib_unpack_tile() / p4c_grib_unpack_max_blocks() report the same)
 GRIB_UNPACK_TILE = 2048        # points per loop trip of a workgroup, 8 per lane

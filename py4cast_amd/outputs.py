@@ -13,7 +13,8 @@ epygram / matplotlib) of the previous one overlap.
 The GRIB writer is native (``ForecastGribWriter``): ``ops.grib_pack`` finds every field's range and packs it on the device at the
 template's decimal scale factor and width (GRIB2 simple packing), params and bit streams leave with one asynchronous copy, and the
 host only wraps them into the template's messages (``grib2.py``: no epygram, no eccodes); ``grib_fid`` holds the reference's key
-table.
+table.  With ``packing="template"`` or ``"complex"`` (``OutputSavingSettings.grib_packing``) the fields of complex-packed template
+messages go through ``ops.grib_pack_complex`` (GRIB2 templates 5.2 / 5.3) instead, in the same submit.
 
 The GIF writer is native (``ForecastGifWriter``): ``ops.forecast_frames`` turns the normalised prediction into palette-index
 frames on the device -- one byte per pixel, every feature of every lead time of the accepted samples, the reference's colour table
@@ -122,6 +123,7 @@ class OutputSavingSettings:
     grib_identifiers: Tuple[str, ...] = ("date", "leadtime")
     gif_fmt: str = "{}_feature_{}.gif"
     gif_identifiers: Tuple[str, ...] = ("runtime", "feature")
+    grib_packing: str = "simple"        # ForecastGribWriter's ``packing``: "simple", "template" or "complex"
 
     @classmethod
     def from_json(cls, path) -> "OutputSavingSettings":
@@ -386,11 +388,27 @@ class ForecastGribWriter:
     tensor the fields are packed by ``grib2.pack_fields`` (the same contract in numpy) and everything else is the same code.
 
     ``grid_lat`` / ``grid_lon``: the forecast grid, (H, W) or vectors; its place in the template's grid follows ``match_latlon``,
-    the points of the template outside it are absent in the bitmap."""
+    the points of the template outside it are absent in the bitmap.
 
-    def __init__(self, settings: OutputSavingSettings, device: torch.device, grid_lat, grid_lon, template=None, slots: int = 2):
+    ``packing``: "simple" (the default) writes every field in simple packing (template 5.0) whatever the template message is packed
+    with; "template" follows each template message -- 5.0: simple; 5.2: complex packing; 5.3: complex packing with spatial
+    differencing of the message's order (octet 48) --; "complex" writes 5.3 at order 2 for every feature.  Complex-packed fields go
+    through ``ops.grib_pack_complex`` (``grib2.pack_fields`` on the CPU) in the same submit; a feature whose width leaves the limits
+    of that route (nbits + order <= 31) is written in 5.0, with one warning.  The complex streams' length is known on the device
+    only, so such a submit makes two copies: the params first and, once they are on the host -- after the earlier batch's files are
+    written --, exactly the bytes up to the end of the last payload."""
+
+    PACKINGS = ("simple", "template", "complex")
+
+    def __init__(self, settings: OutputSavingSettings, device: torch.device, grid_lat, grid_lon, template=None, slots: int = 2,
+                 packing: str = "simple"):
         from . import grib2
 
+        if packing not in self.PACKINGS:
+            raise ValueError(f"packing {packing!r}: one of {self.PACKINGS}")
+        self.packing = packing
+        self._warned_limits = False
+        self.copied: Optional[Tuple[int, int]] = None   # the bytes of the last mixed submit's two copies: params, streams
         self.settings, self.device, self.slots = settings, torch.device(device), slots
         self.template = grib2.Template(settings.template_path) if template is None else template
         self.grid_lat, self.grid_lon = np.asarray(grid_lat, dtype=np.float64), np.asarray(grid_lon, dtype=np.float64)
@@ -419,7 +437,7 @@ class ForecastGribWriter:
             template = grib2.Template(settings.template_path)
         except (grib2.GribError, OSError):
             return None
-        return cls(settings, device, grid.lat, grid.lon, template=template)
+        return cls(settings, device, grid.lat, grid.lon, template=template, packing=settings.grib_packing)
 
     def _buffers(self, slot: int, nbytes: int):
         if self._host[slot] is None or self._host[slot].numel() < nbytes:
@@ -427,13 +445,31 @@ class ForecastGribWriter:
             self._dev[slot] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._host[slot][:nbytes], self._dev[slot][:nbytes]
 
+    def _order(self, m, name: str, nbits: int) -> Optional[int]:
+        """None: the feature is written in simple packing; 0, 1, 2: in complex packing at that order"""
+        import warnings
+
+        from . import grib2
+
+        if self.packing == "simple":
+            return None
+        order = 2 if self.packing == "complex" else grib2.packing_of(m)
+        if order and nbits + order > 31:
+            if not self._warned_limits:
+                self._warned_limits = True
+                warnings.warn(f"{name}: {nbits} bits at order {order} leave the limits of the complex packing written here "
+                              f"(nbits + order <= 31); such features are written in simple packing (5.0)")
+            return None
+        return order
+
     def _plan(self, names: tuple, H: int, W: int):
-        """(feature indices, template messages, (D, nbits) each, window, flip_rows) of a prediction with these feature names"""
+        """(feature indices, template messages, (D, nbits) each, window, flip_rows, the order of the complex packing or None each) of a
+        prediction with these feature names"""
         from . import grib2
 
         key = (names, H, W)
         if key not in self._plans:
-            index, messages, spec = [], [], []
+            index, messages, spec, orders = [], [], [], []
             for f, name in enumerate(names):
                 fid, _ = grib_fid(name, 0)
                 if fid is None:
@@ -443,6 +479,7 @@ class ForecastGribWriter:
                 index.append(f)
                 messages.append(m)
                 spec.append(grib2.spec_of(m))
+                orders.append(self._order(m, name, spec[-1][1]))
             window, flip = None, False
             if messages:
                 if any(m.sections[3] != messages[0].sections[3] for m in messages):
@@ -454,7 +491,7 @@ class ForecastGribWriter:
                 column = self.grid_lat[:, 0] if self.grid_lat.ndim == 2 else self.grid_lat.reshape(-1)
                 # the stream follows the template's rows: flipped when it runs north to south over a grid whose row 0 is the southern one
                 flip = bool(H > 1 and (column[-1] > column[0]) != (lat[-1] > lat[0]))
-            self._plans[key] = (tuple(index), messages, spec, window, flip)
+            self._plans[key] = (tuple(index), messages, spec, window, flip, orders)
         return self._plans[key]
 
     def submit(self, preds: NamedTensor, std: torch.Tensor, mean: torch.Tensor, samples: Sequence[Optional[GribSample]]) -> Optional[int]:
@@ -467,8 +504,12 @@ class ForecastGribWriter:
         slot = None
         t = preds.tensor
         H, W = (t.shape[2], t.shape[3]) if t.dim() == 5 else (1, t.shape[2])
-        index, messages, spec, window, flip = self._plan(tuple(preds.feature_names), H, W) if accepted else ((), [], [], None, False)
-        if accepted and index:
+        index, messages, spec, window, flip, orders = self._plan(tuple(preds.feature_names), H, W) if accepted \
+            else ((), [], [], None, False, [])
+        second_copy = None
+        if accepted and index and any(o is not None for o in orders):
+            slot, second_copy = self._submit_mixed(preds, std, mean, samples, accepted, earlier)
+        elif accepted and index:
             slot = self._next
             self._next = (self._next + 1) % self.slots
             if slot in self._pending:          # the rotation came round: its files are written before its buffers are reused
@@ -497,11 +538,82 @@ class ForecastGribWriter:
                                                    H, W, flip, pitch)
                 self._done[slot] = None
             self._meta[slot] = (params, packed, N, [samples[b] for b in accepted], [preds.feature_names[f] for f in index], messages,
-                                spec, window)
+                                spec, window, None)
             self._pending.append(slot)
         for s in earlier:                      # the host writes the earlier batch while this one is on the device
             self.finish(s)
+        if second_copy is not None:
+            second_copy()
         return slot
+
+    def _submit_mixed(self, preds, std, mean, samples, accepted, earlier):
+        """``submit`` with complex-packed features: the simple-packed ones (if any) and the complex-packed ones go through one call
+        each, the params of both are copied at once.  -> (slot, what ``submit`` runs after the earlier batch's files are written: it
+        waits for the params and enqueues the copy of the streams, sized by the last payload's end; None on the CPU)"""
+        from . import grib2
+
+        t = preds.tensor
+        H, W = (t.shape[2], t.shape[3]) if t.dim() == 5 else (1, t.shape[2])
+        index, messages, spec, window, flip, orders = self._plan(tuple(preds.feature_names), H, W)
+        slot = self._next
+        self._next = (self._next + 1) % self.slots
+        if slot in self._pending:
+            self.finish(slot)
+            earlier.remove(slot)
+        n, T, N = len(accepted), t.shape[1], H * W
+        ks = [k for k, o in enumerate(orders) if o is None]          # written in simple packing
+        kc = [k for k, o in enumerate(orders) if o is not None]      # in complex packing
+        spec_s, spec_c = [spec[k] for k in ks], [(spec[k][0], spec[k][1], orders[k]) for k in kc]
+        index_s, index_c = [index[k] for k in ks], [index[k] for k in kc]
+        pitch = ops.grib_pitch(N, spec_s) if ks else 0
+        words_s, words_c = n * T * len(ks) * ops.GRIB_PARAMS, n * T * len(kc) * ops.GRIB_COMPLEX_PARAMS
+        pbytes, sbytes = 4 * (words_s + words_c), n * T * len(ks) * pitch
+        capacity = ops.grib_complex_capacity(n, T, N, spec_c)
+        shape_s, shape_c = (n, T, len(ks), ops.GRIB_PARAMS), (n, T, len(kc), ops.GRIB_COMPLEX_PARAMS)
+        second_copy = None
+        if t.is_cuda:
+            host, dev = self._buffers(slot, pbytes + sbytes + capacity)
+            if ks:
+                ops.grib_pack(t, std, mean, spec_s, samples=accepted, features=index_s, flip_rows=flip,
+                              out=(dev[:4 * words_s].view(torch.int32).view(shape_s), dev[pbytes:pbytes + sbytes].view(n, T, len(ks), pitch)))
+            ops.grib_pack_complex(t, std, mean, spec_c, samples=accepted, features=index_c, flip_rows=flip,
+                                  out=(dev[4 * words_s:pbytes].view(torch.int32).view(shape_c), dev[pbytes + sbytes:]))
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(ready)
+                host[:pbytes].copy_(dev[:pbytes], non_blocking=True)                  # copy 1: the params of both calls
+                have_params = torch.cuda.Event()
+                have_params.record(self.copy_stream)
+            self._done[slot] = have_params
+            raw = host.numpy()
+            params_c = raw[4 * words_s:pbytes].view(np.int32).reshape(shape_c)
+
+            def second_copy():
+                have_params.synchronize()
+                last = params_c.reshape(-1, ops.GRIB_COMPLEX_PARAMS)[-1]
+                used = sbytes + int(last[10]) + int(last[9])                          # copy 2: up to the end of the last payload
+                with torch.cuda.stream(self.copy_stream):
+                    if used:
+                        host[pbytes:pbytes + used].copy_(dev[pbytes:pbytes + used], non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(self.copy_stream)
+                self._done[slot] = done
+                self.copied = (pbytes, used)
+
+            params_s = raw[:4 * words_s].view(np.int32).reshape(shape_s)
+            packed = raw[pbytes:pbytes + sbytes].reshape(n, T, len(ks), pitch)
+            stream = raw[pbytes + sbytes:]
+        else:
+            x = t.detach().float().reshape(t.shape[0], T, N, t.shape[-1]).numpy()
+            sd, mu = std.detach().float().numpy(), mean.detach().float().numpy()
+            params_s, packed = grib2.pack_fields(x, sd, mu, spec_s, accepted, index_s, H, W, flip, pitch) if ks else (None, None)
+            params_c, stream = grib2.pack_fields(x, sd, mu, spec_c, accepted, index_c, H, W, flip)
+            self._done[slot] = None
+        self._meta[slot] = (params_s, packed, N, [samples[b] for b in accepted], [preds.feature_names[f] for f in index], messages, spec,
+                            window, (orders, params_c, stream))
+        self._pending.append(slot)
+        return slot, second_copy
 
     def finish(self, slot: int) -> List[Path]:
         import warnings
@@ -513,7 +625,9 @@ class ForecastGribWriter:
         if self._done[slot] is not None:
             self._done[slot].synchronize()
         self._pending.remove(slot)
-        params, packed, N, samples, names, messages, spec, window = self._meta[slot]
+        params, packed, N, samples, names, messages, spec, window, mixed = self._meta[slot]
+        if mixed is not None:
+            return self._finish_mixed(slot)
         reals = params[..., :3].view(np.float32)
         paths = []
         for i, sample in enumerate(samples):
@@ -528,6 +642,40 @@ class ForecastGribWriter:
                         f.write(grib2.encode(messages[k], sample.basis, term, cumulative=grib_fid(name, sample.time_step)[1], window=window,
                                              packed=packed[i, t, k, :(N * nbits + 7) // 8].tobytes(), R=float(reals[i, t, k, 2]),
                                              E=int(params[i, t, k, 3]), D=D, nbits=nbits))
+                paths.append(path)
+        self.written.extend(paths)
+        return paths
+
+    def _finish_mixed(self, slot: int) -> List[Path]:
+        """the files of a batch with complex-packed features: message k from the simple or from the complex call's output"""
+        import warnings
+
+        from . import grib2
+
+        params_s, packed, N, samples, names, messages, spec, window, (orders, params_c, stream) = self._meta[slot]
+        place, ns, nc = [], 0, 0                      # feature k -> its index in its call
+        for o in orders:
+            place.append(ns if o is None else nc)
+            ns, nc = ns + (o is None), nc + (o is not None)
+        paths = []
+        for i, sample in enumerate(samples):
+            for t, term in enumerate(sample.terms):
+                path = self.settings.get_grib_path(sample.runtime, sample.member, int(term.total_seconds() / 60 ** 2))
+                with open(path, "wb") as f:
+                    for k, name in enumerate(names):
+                        rec = (params_s if orders[k] is None else params_c)[i, t, place[k]]
+                        if rec[4]:
+                            warnings.warn(f"{path}: {name} holds {int(rec[4])} values that are not finite; the field is not written")
+                            continue
+                        D, nbits = spec[k]
+                        common = dict(cumulative=grib_fid(name, sample.time_step)[1], window=window, R=float(rec[2:3].view(np.float32)[0]),
+                                      E=int(rec[3]), D=D, nbits=nbits)
+                        if orders[k] is None:
+                            f.write(grib2.encode(messages[k], sample.basis, term, packed=packed[i, t, place[k], :(N * nbits + 7) // 8].tobytes(),
+                                                 **common))
+                        else:
+                            f.write(grib2.encode(messages[k], sample.basis, term, packed=stream[int(rec[10]):int(rec[10]) + int(rec[9])].tobytes(),
+                                                 order=orders[k], ref_bits=int(rec[8]), **common))
                 paths.append(path)
         self.written.extend(paths)
         return paths
