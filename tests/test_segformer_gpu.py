@@ -44,7 +44,10 @@ def bf(t):
 
 # ------------------------------------------------------------------------------------------------ spatial-reduction attention
 @pytest.mark.parametrize("Nk,Nq,heads", [(1, 64, 1), (64, 4096, 1), (80, 5120, 1), (256, 64, 8), (64, 1024, 2), (80, 256, 5),
-                                         (256, 4096, 2), (1, 5120, 8), (80, 64, 8), (64, 4096, 3)])
+                                         (256, 4096, 2), (1, 5120, 8), (80, 64, 8), (64, 4096, 3),
+                                         # off the default stages: masked tails of the 32-key chunk (3, 12, 31, 33, 255), whole chunks
+                                         # only (192), one query, a partial query tile, up to the entry point's 64 heads
+                                         (3, 1, 3), (12, 1536, 2), (31, 65, 1), (33, 63, 16), (192, 1536, 1), (255, 130, 10), (4, 64, 64)])
 def test_sr_attention_against_float64(gpu_device, Nk, Nq, heads):
     from py4cast_amd.segformer import sr_attention
 
@@ -71,7 +74,9 @@ def test_sr_attention_against_float64(gpu_device, Nk, Nq, heads):
 
 
 # ------------------------------------------------------------------------------------------------ channel LayerNorm (std + eps)
-@pytest.mark.parametrize("R,C", [(8192, 32), (2048, 64), (512, 160), (128, 256), (1000, 512)])
+@pytest.mark.parametrize("R,C", [(8192, 32), (2048, 64), (512, 160), (128, 256), (1000, 512),
+                                 # one row; one partial lane fill (8, 96); 5 and 7.875 values per lane (320, 504: the widest partial fill)
+                                 (1, 32), (257, 8), (130, 96), (67, 320), (33, 504)])
 def test_chan_layer_norm_against_float64(gpu_device, R, C):
     from py4cast_amd.segformer import chan_layer_norm
 
@@ -101,7 +106,11 @@ def test_chan_layer_norm_against_float64(gpu_device, R, C):
 
 # ------------------------------------------------------------------------------------------------ overlapping strided convolutions
 @pytest.mark.parametrize("B,H,W,C,D,k,s,p", [(2, 128, 128, 8, 32, 3, 2, 1), (2, 64, 96, 32, 64, 7, 4, 3), (1, 32, 32, 64, 160, 3, 2, 1),
-                                             (2, 64, 64, 32, 64, 8, 8, 0), (2, 16, 24, 160, 320, 2, 2, 0)])
+                                             (2, 64, 64, 32, 64, 8, 8, 0), (2, 16, 24, 160, 320, 2, 2, 0),
+                                             # reduction ratio 1 (no gather: the GEMM alone) and 16 (one key per sample: a 2-row GEMM
+                                             # over 16384 columns), the 7 x 7 embedding over 8 channels, ratio 1 at the widest dims
+                                             (2, 8, 24, 32, 64, 1, 1, 0), (2, 16, 16, 64, 128, 16, 16, 0), (1, 32, 64, 8, 32, 7, 4, 3),
+                                             (3, 4, 4, 512, 1024, 1, 1, 0)])
 def test_patch_conv_against_float64(gpu_device, B, H, W, C, D, k, s, p):
     from py4cast_amd.segformer import patch_conv
 
@@ -124,7 +133,10 @@ def test_patch_conv_against_float64(gpu_device, B, H, W, C, D, k, s, p):
 
 
 # ------------------------------------------------------------------------------------------------ depthwise 3x3
-@pytest.mark.parametrize("B,H,W,C", [(2, 64, 64, 256), (2, 32, 32, 512), (2, 16, 20, 640), (2, 8, 8, 1024), (1, 33, 7, 1024)])
+@pytest.mark.parametrize("B,H,W,C", [(2, 64, 64, 256), (2, 32, 32, 512), (2, 16, 20, 640), (2, 8, 8, 1024), (1, 33, 7, 1024),
+                                     # FFN widths of small expansions: one 8-channel group, less than one 512-channel block of the
+                                     # weight gradient, and exactly one group in its second block (520)
+                                     (2, 9, 7, 8), (2, 16, 12, 32), (1, 5, 33, 96), (2, 8, 8, 520)])
 def test_depthwise_against_float64(gpu_device, B, H, W, C):
     from py4cast_amd.segformer import depthwise3x3
 
@@ -147,7 +159,7 @@ def test_depthwise_against_float64(gpu_device, B, H, W, C):
 
 
 # ------------------------------------------------------------------------------------------------ decoder up-sampling sum
-@pytest.mark.parametrize("B,H,W,C", [(2, 64, 64, 256), (1, 8, 16, 8), (2, 64, 80, 64)])
+@pytest.mark.parametrize("B,H,W,C", [(2, 64, 64, 256), (1, 8, 16, 8), (2, 64, 80, 64), (1, 8, 24, 64), (3, 16, 8, 128)])
 def test_up_sum_against_float64(gpu_device, B, H, W, C):
     from py4cast_amd.segformer import up_sum
 

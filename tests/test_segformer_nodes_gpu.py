@@ -68,26 +68,23 @@ def recorded(request, gpu_device):
     return m, rec
 
 
-def test_layer_norm_nodes(recorded):
-    _, rec = recorded
+# the checks themselves: also run on the non-default configurations of tests/test_segformer_settings_bf16_gpu.py, at the same bars
+def check_layer_norm_nodes(rec):
     for i, r in enumerate(rec.norms):
         ref = N.ln(r["x"].double(), r["g"].double(), r["b"].double(), r["eps"])
         close_bf16(r["y"], ref, f"LayerNorm call {i}")
 
 
-def test_sra_core_nodes(recorded):
-    _, rec = recorded
+def check_sra_core_nodes(rec):
     for i, r in enumerate(rec.attns):
         ref = N.sra_core(r["q"].double(), r["kv"].double(), r["heads"], r["scale"])
         close_bf16(r["y"], ref, f"attention core call {i} (Nq {r['q'].shape[1]}, Nk {r['kv'].shape[1]}, heads {r['heads']})")
 
 
-@pytest.mark.parametrize("kind", ["attn", "ff"])
-def test_block_nodes(recorded, kind):
-    m, rec = recorded
+def check_block_nodes(m, rec, kind, count):
     orig = getattr(m, "_" + kind)
     calls = [r for r in rec.blocks if r["kind"] == kind]
-    assert len(calls) == 8
+    assert len(calls) == count
     for i, r in enumerate(calls):
         pn, x, dy = r["pn"], r["x"], r["dy"]
         what = f"{kind} block call {i} ({tuple(x.shape)})"
@@ -114,6 +111,11 @@ def test_block_nodes(recorded, kind):
         for n, gr in zip(names, grads[1:]):
             got = params[n].grad
             assert got is not None, f"{what}: {n} got no gradient"
+            if n == "fn.to_q.weight" and r["pn"].fn.reduction_ratio ** 2 == x.shape[1] * x.shape[2]:
+                # ONE key per sample: the softmax is 1 whatever the query, dS = P (dP - D) is zero term by term in float64 and in the
+                # kernel alike (o = v, so dP and D are the same fp32 sum) -- no direction to compare: exact zeros on both sides
+                assert not bool(gr.any()) and not bool(got.any()), f"{what}: {n} with one key: |got| {float(got.norm()):.2e}"
+                continue
             if n in ("fn.to_q.weight", "fn.to_kv.weight"):
                 cos = float(torch.nn.functional.cosine_similarity(got.double().flatten(), gr.flatten(), dim=0))
                 assert rel(got, gr) <= 1e-1 and cos >= 0.995, f"{what}: {n} {rel(got, gr):.2e}, cosine {cos:.5f}"
@@ -121,13 +123,24 @@ def test_block_nodes(recorded, kind):
                 assert rel(got, gr) <= 3e-2, f"{what}: {n} {rel(got, gr):.2e}"
 
 
-def test_sink_route_adds_into_grad(gpu_device):
+def test_layer_norm_nodes(recorded):
+    check_layer_norm_nodes(recorded[1])
+
+
+def test_sra_core_nodes(recorded):
+    check_sra_core_nodes(recorded[1])
+
+
+@pytest.mark.parametrize("kind", ["attn", "ff"])
+def test_block_nodes(recorded, kind):
+    check_block_nodes(*recorded, kind, 8)
+
+
+def check_sink_route(m, x, dy, gpu_device):
     """parameter gradients pre-filled (the GEMMs, LayerNorms and depthwise convolutions then ADD theirs into .grad in place; the decoder's
     weight slices, the padded downsampler and head go through autograd's accumulation), and under FlatDDP with a non-zero flat buffer:
     p.grad = prefill + the gradient of the .grad-is-None run, bit for bit"""
     from py4cast_amd.trainer import FlatDDP
-
-    m, x, dy = _model(gpu_device, (128, 128), seed=3)
 
     def step():
         m(x).float().backward(dy)
@@ -151,3 +164,7 @@ def test_sink_route_adds_into_grad(gpu_device):
     step()
     for n, p in m.named_parameters():
         assert torch.equal(p.grad, prefill[n] + g_none[n]), f"FlatDDP .grad: {n}"
+
+
+def test_sink_route_adds_into_grad(gpu_device):
+    check_sink_route(*_model(gpu_device, (128, 128), seed=3), gpu_device)
