@@ -313,6 +313,40 @@ typedef struct p4c_regrid_feature {
 int p4c_regrid_pack(const p4c_regrid_feature* feats, const p4c_regrid_tap* taps, float* out, int B, int T, int H_sub, int W_sub,
                     int F, p4c_stream_t stream);
 
+/* Planes in the files' own number format -> the standardised features-last batch, in one pass (the rainfall accessor's
+ * np.where(arr < 0, 0, arr) / 100 * 12 and arr[::-1], datasets/rainfall.py:116-164, + Sample.get_param_tensor's
+ * standardisation, datasets/base.py:431-453, + NamedTensor.concat + collate_fn).  out (B,T,H,W,F) fp32, row
+ * r = ((b*T + t)*H + y)*W + x:
+ *   raw = src[b*b_stride + t*t_stride + ys*W + x],  ys = flip_rows ? H-1-y : y      (every plane dense, H x W)
+ *   v = (float)raw                       round to nearest even: numpy's astype(float32)
+ *   if has_floor: v = v < floor ? floor : v          a NaN stays NaN
+ *   if div != 1: v = v / div;  if mul != 1: v = v * mul         two rounded fp32 steps, in this order
+ *   out[r*F + channel] = (v - mean) / std            the two rounded steps of p4c_pack_standardize
+ * With fp32 sources, no flip, no floor and div = mul = 1 the result is p4c_pack_standardize's, bit for bit.
+ * dtype: one P4C_SRC_* per call.  feats: F descriptors in DEVICE memory; their channels are a permutation of 0 .. F-1; the
+ *   caller guarantees that every plane lies inside its allocation and that every src is a multiple of 16 bytes.
+ * vec != 0: every 16 bytes of a source row are one load.  The caller guarantees that W, every b_stride and every t_stride are
+ *   multiples of 16 / sizeof(element); W is checked here.  vec == 0: one element per load, any W and strides.
+ * Limits: F <= 144 (the LDS tile of p4c_pack_standardize), B*T*H*W < 2^31, refused before any launch. */
+enum { P4C_SRC_U8 = 0, P4C_SRC_I16 = 1, P4C_SRC_U16 = 2, P4C_SRC_I32 = 3, P4C_SRC_F16 = 4, P4C_SRC_F32 = 5, P4C_SRC_F64 = 6 };
+enum { P4C_CONVERT_FLIP_ROWS = 1, P4C_CONVERT_HAS_FLOOR = 2 };
+
+typedef struct p4c_convert_feature {
+    const void* src;            /* the plane of (b, t) = (0, 0), device memory, 16-byte aligned */
+    int64_t b_stride, t_stride; /* in elements */
+    float floor, div, mul;
+    float mean, std;
+    int32_t flags;              /* P4C_CONVERT_* */
+    int32_t channel;            /* output column */
+    int32_t pad;
+} p4c_convert_feature;
+
+int p4c_pack_convert(const p4c_convert_feature* feats, float* out, int dtype, int vec, int B, int T, int H, int W, int F,
+                     p4c_stream_t stream);
+/* the launch arithmetic, for tests that size a second loop trip: rows per workgroup pass at F features, and the grid cap */
+int p4c_pack_convert_rows(int F);
+int p4c_pack_convert_max_blocks(void);
+
 /* The Gaussian of resize(anti_aliasing=True) over `planes` windowed planes: dst (planes, n, m) dense =
  * gaussian_filter(window, sigma, mode="mirror"), axis 0 then axis 1, window = src[p*plane_stride + (row0 + i)*pitch + col0 + j].
  * row_index: (n + 2*ry) ints, the mirrored source row (period 2(n-1)) of positions -ry .. n-1+ry; col_index: (m + 2*rx)

@@ -55,6 +55,8 @@ SIGNATURES = {
     "p4c_build_forcing": [P, L, P, P, P, P, P, P, P, I, I, L, I, P],
     # feats, taps, out, B, T, H_sub, W_sub, F, stream
     "p4c_regrid_pack": [P, P, P, I, I, I, I, I, P],
+    # feats (device), out, dtype, vec, B, T, H, W, F, stream
+    "p4c_pack_convert": [P, P, I, I, I, I, I, I, I, P],
     # src, plane_stride, pitch, row0, col0, dst, planes, n, m, row_index, col_index, row_w, ry, col_w, rx, stream
     "p4c_regrid_blur": [P, L, I, I, I, P, I, I, I, P, P, P, I, P, I, P],
     # pred, bs, ts, target, bs, ts, mask, mode, std, mean, features, planes, vrange, ws, n, T, N, F, K, stream
@@ -107,6 +109,8 @@ OTHER = {
     "p4c_psd_workspace_bytes": ([I, I, I, I], c_size_t),
     "p4c_eval_sums_workspace_bytes": ([I, I, L, I], c_size_t),
     "p4c_map_planes_workspace_bytes": ([I, I, L, I], c_size_t),
+    "p4c_pack_convert_rows": ([I], c_int),
+    "p4c_pack_convert_max_blocks": ([], c_int),
     "p4c_map_tile": ([], c_int),
     "p4c_map_max_blocks": ([], c_int),
     "p4c_map_gap": ([], c_int),

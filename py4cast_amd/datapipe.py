@@ -7,8 +7,9 @@ features-last batch layout the rollout consumes.
 """
 
 from datetime import datetime, timedelta
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import forcings, ops, regrid
@@ -37,6 +38,99 @@ def load_batch(raw_io: torch.Tensor, io_names: List[str], forcing: NamedTensor, 
     t = full.tensor
     inputs = NamedTensor(t[:, :num_input_steps], DIMS.copy(), list(io_names))
     outputs = NamedTensor(t[:, num_input_steps:], DIMS.copy(), list(io_names))
+    return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
+
+
+class PlaneTransform(NamedTuple):
+    """What an accessor does to a plane between the file and the standardisation: ``np.where(arr < floor, floor, arr)``, ``/ div``,
+    ``* mul`` and ``arr[::-1]``.  The default changes nothing."""
+    floor: Optional[float] = None
+    div: float = 1.0
+    mul: float = 1.0
+    flip: bool = False
+
+
+# datasets/rainfall.py:150-155: 0 outside of the radar field, mm 10^-2 in 5 minutes -> mm/h, latitude inverted
+RAINFALL_TRANSFORM = PlaneTransform(floor=0.0, div=100.0, mul=12.0, flip=True)
+
+
+def _transform_list(transforms, names) -> List[PlaneTransform]:
+    if transforms is None:
+        return [PlaneTransform()] * len(names)
+    if isinstance(transforms, PlaneTransform):
+        return [transforms] * len(names)
+    if isinstance(transforms, dict):
+        return [transforms.get(n) or PlaneTransform() for n in names]
+    transforms = [t or PlaneTransform() for t in transforms]
+    if len(transforms) != len(names):
+        raise ValueError(f"{len(transforms)} transforms for {len(names)} features")
+    return transforms
+
+
+def pack_typed_host(planes, transforms, mean, std) -> torch.Tensor:
+    """The host statement of ``p4c_pack_convert`` (include/py4cast_hip.h), numpy float32 step by step: what a loader on the CPU
+    device returns and what the kernel is tested against.  planes: per feature a (B, T, H, W) array in its file dtype."""
+    f4, cols = np.float32, []
+    with np.errstate(all="ignore"):
+        for x, tr, m, s in zip(planes, transforms, mean, std):
+            v = np.asarray(x).astype(f4)
+            if tr.floor is not None:
+                v = np.where(v < f4(tr.floor), f4(tr.floor), v)
+            if f4(tr.div) != f4(1):
+                v = v / f4(tr.div)
+            if f4(tr.mul) != f4(1):
+                v = v * f4(tr.mul)
+            if tr.flip:
+                v = v[..., ::-1, :]
+            cols.append((v - f4(m)) / f4(s))
+    return torch.from_numpy(np.ascontiguousarray(np.stack(cols, axis=-1), dtype=f4))
+
+
+def pack_typed(raw, names: Sequence[str], transforms, stats, standardize: bool = True, host: bool = False) -> torch.Tensor:
+    """Planes in their file dtype -> (B, T, H, W, F) fp32 standardised features-last.  raw: one (F, B, T, H, W) tensor or one
+    tensor per feature ((B, T, H, W) or (1, B, T, H, W)), all of one dtype on one device.  Planes that are not on a CUDA device
+    are refused like every other op of the package (no CPU fallback) unless ``host=True`` asks for the host statement
+    (``pack_typed_host``: numpy arrays and CPU tensors).  On a CUDA device this is one launch:
+    ``p4c_pack_standardize`` for untransformed fp32 planes in one tensor, ``p4c_pack_convert`` for everything else."""
+    names = list(names)
+    trs = _transform_list(transforms, names)
+    if standardize:
+        mean, std = stats.to_list("mean", names).tolist(), stats.to_list("std", names).tolist()
+    else:
+        mean, std = [0.0] * len(names), [1.0] * len(names)
+
+    def as_numpy(t):
+        return t if isinstance(t, np.ndarray) else (t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.uint16 else t.numpy())
+
+    single = isinstance(raw, (torch.Tensor, np.ndarray))
+    sources = [raw] if single else [r if r.ndim == 5 else r[None] for r in raw]
+    where = [(si, k) for si, s in enumerate(sources) for k in range(s.shape[0])]
+    if len(where) != len(names) or any(s.ndim != 5 for s in sources):
+        raise ValueError(f"pack_typed: {len(where)} planes of shapes {[tuple(s.shape) for s in sources]} for {len(names)} names")
+    B, T, H, W = sources[0].shape[1:]
+    if isinstance(sources[0], np.ndarray) or not sources[0].is_cuda:
+        if not host:
+            raise ops.L.P4CError("pack_typed: the planes are not on a CUDA device and the kernels run on the GPU only (no CPU fallback); "
+                                 "host=True asks for the numpy statement of the same arithmetic")
+        return pack_typed_host([as_numpy(sources[si])[k] for si, k in where], trs, mean, std)
+    plain = all(t == PlaneTransform() for t in trs)
+    if plain and len(sources) == 1 and sources[0].dtype == torch.float32 and sources[0].is_contiguous():
+        dev = sources[0].device
+        return ops.pack_standardize(sources[0], torch.tensor(mean, device=dev), torch.tensor(std, device=dev))
+    feats = [(si, k, tr.floor, tr.div, tr.mul, tr.flip, mean[c], std[c], c) for c, ((si, k), tr) in enumerate(zip(where, trs))]
+    return ops.pack_convert(sources, feats, B, T, H, W)
+
+
+def load_typed_batch(raw, io_names: List[str], transforms, forcing: NamedTensor, stats, num_input_steps: int,
+                     standardize: bool = True, host: bool = False) -> ItemBatch:
+    """``load_batch`` for planes that are still in their file's number format (u8, i16, u16, i32, f16, f32, f64) and still need the
+    accessor's transform (``PlaneTransform``; the rainfall accessor's is ``RAINFALL_TRANSFORM``): conversion, transform,
+    standardisation and pack are ONE pass of ``p4c_pack_convert``, no host ``astype``.  raw, transforms, host: as ``pack_typed``
+    takes them.  -> the ItemBatch of ``load_batch``."""
+    io_names = list(io_names)
+    full = pack_typed(raw, io_names, transforms, stats, standardize, host)
+    inputs = NamedTensor(full[:, :num_input_steps], DIMS.copy(), io_names)
+    outputs = NamedTensor(full[:, num_input_steps:], DIMS.copy(), list(io_names))
     return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
 
 

@@ -42,14 +42,24 @@ def load_stats(fname) -> Stats:
 
 
 def write_dataset_stats(dataset, cache_dir, device=None) -> Tuple[Path, Path]:
-    """compute_dataset_stats.py end to end on the device kernels: ``parameters_stats.pt`` then ``diff_stats.pt`` in ``cache_dir``."""
+    """compute_dataset_stats.py end to end on the device kernels, as the accessors' ``prepare`` runs it (datasets/rainfall.py:196-246):
+    ``parameters_stats.pt`` on the raw values (``settings.standardize`` off), then ``diff_stats.pt`` on values standardised with the
+    file just written (``settings.standardize`` on; pass the dataset's own ``cache_dir`` so that it is the file the dataset reads).
+    The dataset's setting is put back afterwards."""
     from . import dataset_stats as ds
 
     cache_dir = Path(cache_dir)
     os.makedirs(cache_dir, exist_ok=True)
     p1, p2 = cache_dir / "parameters_stats.pt", cache_dir / "diff_stats.pt"
-    save_stats(ds.compute_parameters_stats(dataset, device), p1)
-    save_stats(ds.compute_time_step_stats(dataset, device), p2)
+    keep = dataset.settings.standardize
+    try:
+        dataset.settings.standardize = False
+        save_stats(ds.compute_parameters_stats(dataset, device), p1)
+        dataset.settings.standardize = True
+        getattr(dataset, "__dict__", {}).pop("stats", None)      # a cached Stats of an earlier file
+        save_stats(ds.compute_time_step_stats(dataset, device), p2)
+    finally:
+        dataset.settings.standardize = keep
     return p1, p2
 
 
@@ -134,6 +144,81 @@ def load_titan_batch(dataset_path, params: List[Tuple[str, int, str]], dates: Li
     raw = reader.read(paths)
     names = [f"{n}_{lv}{'m' if lt in ('surface', 'heightAboveGround') else 'hpa'}" for (n, lv, lt) in params]
     return datapipe.load_batch(raw, names, forcing, stats, num_input_steps, standardize)
+
+
+class TypedNpyPlaneReader:
+    """``NpyPlaneReader`` for planes that are NOT ``<f4`` (which that reader converts on the host): the payloads go into the pinned
+    buffer in the files' own dtype ``dtype`` (u8, i16, u16, i32, f16, f32, f64) and ``read`` returns the typed (F, B, T, H, W) device
+    tensor ``datapipe.load_typed_batch`` consumes -- the conversion happens in ``p4c_pack_convert``.  Every feature's block of B x T
+    planes starts on a 16-byte boundary (the tensor is a view with that pitch between features)."""
+
+    def __init__(self, shape: Tuple[int, int], dtype, n_features: int, batch: int, steps: int, device=None, pin: Optional[bool] = None):
+        self.shape, self.dtype, self.dims, self.device = tuple(shape), np.dtype(dtype), (n_features, batch, steps), device
+        H, W = self.shape
+        self.block = (batch * steps * H * W * self.dtype.itemsize + 15) // 16 * 16
+        pin = torch.cuda.is_available() if pin is None else pin
+        self.host = torch.empty(max(self.block * n_features, 16), dtype=torch.uint8, pin_memory=pin)
+        per = self.block // self.dtype.itemsize
+        self._strides = (per, steps * H * W, H * W, W, 1)
+        self._np = np.lib.stride_tricks.as_strided(self.host.numpy().view(self.dtype), (n_features, batch, steps, H, W),
+                                                   tuple(v * self.dtype.itemsize for v in self._strides), writeable=True)
+        self.copy_stream = torch.cuda.Stream(device) if (device is not None and torch.device(device).type == "cuda") else None
+        self._copied = None     # the event behind the last copy out of ``host``: the buffer is refilled only after it
+
+    def _typed(self, flat: torch.Tensor) -> torch.Tensor:
+        tdtype = torch.uint16 if self.dtype == np.uint16 else torch.from_numpy(np.zeros(0, dtype=self.dtype)).dtype
+        return flat.view(tdtype).as_strided((*self.dims, *self.shape), self._strides)
+
+    def read(self, paths: Sequence[Sequence[Sequence]]) -> torch.Tensor:
+        """paths[f][b][t] -> (F, B, T, H, W) tensor of the files' dtype on ``device`` (a view of the host buffer when it is None)"""
+        F, B, T = self.dims
+        if len(paths) != F or any(len(pb) != B or any(len(pt) != T for pt in pb) for pb in paths):
+            raise ValueError(f"expected paths[{F}][{B}][{T}]")
+        if self._copied is not None:
+            self._copied.synchronize()          # the last call's copy has left the buffer
+            self._copied = None
+        for fi in range(F):
+            for b in range(B):
+                for t in range(T):
+                    dst = self._np[fi, b, t]
+                    with open(paths[fi][b][t], "rb") as f:
+                        shape, fortran, dtype = _read_header(f)
+                        if tuple(shape) != self.shape or fortran or np.dtype(dtype) != self.dtype:
+                            raise ValueError(f"{paths[fi][b][t]}: holds {tuple(shape)} {dtype}{' (Fortran order)' if fortran else ''}, "
+                                             f"expected {self.shape} {self.dtype}")
+                        n = f.readinto(memoryview(dst).cast("B"))
+                        if n != dst.nbytes:
+                            raise ValueError(f"{paths[fi][b][t]}: truncated file ({n} of {dst.nbytes} bytes)")
+        if self.device is None or self.copy_stream is None:
+            return self._typed(self.host if self.device is None else self.host.to(self.device))
+        current = torch.cuda.current_stream(self.device)
+        self.copy_stream.wait_stream(current)
+        with torch.cuda.stream(self.copy_stream):
+            dev = self.host.to(self.device, non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record(self.copy_stream)
+        current.wait_stream(self.copy_stream)
+        dev.record_stream(current)
+        return self._typed(dev)
+
+
+def load_titan_typed_batch(dataset_path, params: List[Tuple[str, int, str]], dates: List[List[dt.datetime]], stats: Stats,
+                           num_input_steps: int, forcing, reader: Optional[TypedNpyPlaneReader] = None, device=None,
+                           standardize: bool = True, transforms=None, host: bool = False):
+    """``load_titan_batch`` for ``.npy`` planes of any dtype ``p4c_pack_convert`` reads, all of one dtype: no conversion on the host.
+    transforms: as ``datapipe.load_typed_batch`` takes them (None: the planes are standardised as they are).  Without a CUDA
+    ``device`` (or a reader on one) the call is refused -- no CPU fallback -- unless ``host=True`` asks for the numpy statement."""
+    from . import datapipe
+
+    B, T = len(dates), len(dates[0])
+    paths = [[[titan_plane_path(dataset_path, n, lv, lt, dates[b][t]) for t in range(T)] for b in range(B)] for (n, lv, lt) in params]
+    if reader is None:
+        with open(paths[0][0][0], "rb") as f:
+            shape, _, dtype = _read_header(f)
+        reader = TypedNpyPlaneReader(shape, dtype, len(params), B, T, device=device)
+    raw = reader.read(paths)
+    names = [f"{n}_{lv}{'m' if lt in ('surface', 'heightAboveGround') else 'hpa'}" for (n, lv, lt) in params]
+    return datapipe.load_typed_batch(raw, names, transforms, forcing, stats, num_input_steps, standardize, host)
 
 
 # ------------------------------------------------------------------------------------------ GRIB2 files

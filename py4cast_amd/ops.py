@@ -599,6 +599,88 @@ def regrid_pack(sources, feats, taps: torch.Tensor, table_dims, B: int, T: int, 
     return out
 
 
+# host mirror of p4c_convert_feature (include/py4cast_hip.h)
+CONVERT_FEATURE = np.dtype([("src", "<u8"), ("b_stride", "<i8"), ("t_stride", "<i8"), ("floor", "<f4"), ("div", "<f4"), ("mul", "<f4"),
+                            ("mean", "<f4"), ("std", "<f4"), ("flags", "<i4"), ("channel", "<i4"), ("pad", "<i4")])
+CONVERT_FLIP_ROWS, CONVERT_HAS_FLOOR = 1, 2
+CONVERT_MAX_FEATURES = 144
+
+
+def convert_dtype_code(dt: torch.dtype) -> int:
+    """the P4C_SRC_* code of a source dtype (``p4c_pack_convert`` reads u8, i16, u16, i32, f16, f32 and f64 planes)"""
+    codes = {torch.uint8: 0, torch.int16: 1, torch.uint16: 2, torch.int32: 3, torch.float16: 4, torch.float32: 5, torch.float64: 6}
+    if dt not in codes:
+        raise L.P4CError(f"pack_convert: source dtype {dt} is none of {', '.join(str(k) for k in codes)}")
+    return codes[dt]
+
+
+def convert_features(sources, feats, B: int, T: int, H: int, W: int):
+    """The device descriptors (p4c_convert_feature) of ``pack_convert``, checked on the host -> (descriptors, vec).
+
+    sources: device tensors (Fg, B, T, H, W), all of ONE dtype of ``convert_dtype_code``, every plane dense (``planes_dense``: the
+    strides of the three leading dimensions are free, so planes may lie at a pitch).  feats: one tuple per output feature,
+    (index into sources, plane of that source, floor or None, div, mul, flip_rows, mean, std, output channel).  A feature's first
+    plane must start on a 16-byte boundary (a torch allocation or a padded slot of a pinned buffer does).  vec: whether every
+    16 bytes of a source row can be one load -- W and all batch / step strides are multiples of 16 / itemsize.  The result
+    holds raw pointers into ``sources``: keep them alive."""
+    L.require_cuda(*sources)
+    F = len(feats)
+    if not 1 <= F <= CONVERT_MAX_FEATURES:
+        raise L.P4CError(f"pack_convert: {F} features: 1 .. at most {CONVERT_MAX_FEATURES} per call (LDS tile)")
+    if int(B) * int(T) * int(H) * int(W) >= 1 << 31:
+        raise L.P4CError(f"pack_convert: {int(B) * int(T) * int(H) * int(W)} rows: at most 2^31 - 1 per call")
+    if not sources:
+        raise L.P4CError("pack_convert: no sources")
+    dev, dt = sources[0].device, sources[0].dtype
+    convert_dtype_code(dt)
+    size = sources[0].element_size()
+    per = 16 // size
+    for s in sources:
+        if s.dim() != 5 or tuple(s.shape[1:]) != (B, T, H, W) or s.dtype != dt or not planes_dense(s) or s.device != dev:
+            raise L.P4CError(f"pack_convert: source {tuple(s.shape)} {s.dtype} is not a dense {dt} (Fg, {B}, {T}, {H}, {W}) on {dev}")
+        if min(s.stride()[:3]) < 0:
+            raise L.P4CError(f"pack_convert: source strides {s.stride()} are negative")
+    if sorted(f[8] for f in feats) != list(range(F)):
+        raise L.P4CError(f"pack_convert: the output channels {sorted(f[8] for f in feats)} are not 0 .. {F - 1}, each once")
+    desc = np.zeros(F, dtype=CONVERT_FEATURE)
+    vec = W % per == 0
+    for i, (si, plane, floor, div, mul, flip, mean, std, channel) in enumerate(feats):
+        if not 0 <= si < len(sources):
+            raise L.P4CError(f"pack_convert: feature {i}: source {si} of {len(sources)}")
+        s = sources[si]
+        if not 0 <= plane < s.shape[0]:
+            raise L.P4CError(f"pack_convert: feature {i}: plane {plane} of {s.shape[0]}")
+        base = s.data_ptr() + size * plane * s.stride(0)
+        if base % 16:
+            raise L.P4CError(f"pack_convert: feature {i}: its first plane starts at address {base:#x}, not on a 16-byte boundary")
+        bs, ts = (s.stride(1) if B > 1 else 0), (s.stride(2) if T > 1 else 0)
+        vec = vec and bs % per == 0 and ts % per == 0
+        flags = (CONVERT_FLIP_ROWS if flip else 0) | (CONVERT_HAS_FLOOR if floor is not None else 0)
+        desc[i] = (base, bs, ts, 0.0 if floor is None else floor, div, mul, mean, std, flags, channel, 0)
+    return torch.from_numpy(desc.view(np.uint8)).to(dev), bool(vec)
+
+
+def pack_convert(sources, feats, B: int, T: int, H: int, W: int) -> torch.Tensor:
+    """Planes in the files' own dtype -> (B, T, H, W, F) fp32 standardised features-last, one pass of ``p4c_pack_convert``:
+    ``(float)raw``, the floor, ``/ div``, ``* mul`` (each a rounded fp32 step, a factor of exactly 1 skipped), the row flip, then
+    ``(v - mean) / std`` as ``pack_standardize`` does.  sources, feats: as ``convert_features`` takes them (and checks them)."""
+    B, T, H, W = int(B), int(T), int(H), int(W)
+    feats_dev, vec = convert_features(sources, feats, B, T, H, W)
+    return pack_convert_launch(sources, feats_dev, vec, B, T, H, W)
+
+
+def pack_convert_launch(sources, feats_dev: torch.Tensor, vec: bool, B: int, T: int, H: int, W: int) -> torch.Tensor:
+    """the launch of ``pack_convert`` on descriptors ``convert_features`` made for these very sources and dimensions"""
+    F = feats_dev.numel() // CONVERT_FEATURE.itemsize
+    dev, dt = sources[0].device, sources[0].dtype
+    if feats_dev.device != dev or feats_dev.dtype != torch.uint8 or feats_dev.numel() != F * CONVERT_FEATURE.itemsize or F < 1:
+        raise L.P4CError(f"pack_convert: descriptors {tuple(feats_dev.shape)} {feats_dev.dtype} on {feats_dev.device}: not convert_features' on {dev}")
+    out = torch.empty(B, T, H, W, F, dtype=torch.float32, device=dev)
+    L.call("p4c_pack_convert", L.ptr(feats_dev), L.ptr(out), convert_dtype_code(dt), int(vec), B, T, H, W, F, L.stream(dev),
+           alg_bytes=(sources[0].element_size() + 4) * out.numel())
+    return out
+
+
 def regrid_blur(src: torch.Tensor, window, row_index: torch.Tensor, col_index: torch.Tensor, row_w: torch.Tensor,
                 col_w: torch.Tensor) -> torch.Tensor:
     """The Gaussian of ``resize(anti_aliasing=True)`` over the window (r0, r1, c0, c1) of every plane of ``src`` (..., Hs, Ws) ->

@@ -991,6 +991,31 @@ class Trainer:
             self.callback_metrics["val_mean_loss"] = mean
         return self.callback_metrics
 
+    def test(self, module, dataloader: Iterable):
+        """``on_test_start`` / ``test_step`` / ``on_test_epoch_end`` over the batches, in eval mode (``trainer.test`` of Lightning): the
+        module's test observers (score cards, spatial error maps) write their files at the end."""
+        module.trainer = self
+        module.to(self.device)
+        module.eval()
+        if hasattr(module, "setup"):
+            module.setup("test")        # the metrics and the observers' save path (Lightning calls it before on_test_start)
+        if hasattr(module, "on_test_start"):
+            module.on_test_start()
+        losses = []
+        for i, batch in enumerate(dataloader):
+            if self.limit_val_batches and i >= self.limit_val_batches:
+                break
+            losses.append(module.test_step(self._to_device(batch, self.device), i))
+        if losses:
+            mean = torch.stack([torch.as_tensor(l) for l in losses]).mean()
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(mean, op=dist.ReduceOp.SUM)
+                mean /= dist.get_world_size()
+            self.callback_metrics["test_mean_loss"] = mean
+        if hasattr(module, "on_test_epoch_end"):
+            module.on_test_epoch_end()
+        return self.callback_metrics
+
     def predict(self, module, dataloader: Iterable):
         """``predict_step`` over the batches, in eval mode under no_grad; the module's forecast writers (``io_conf``: the GIFs and GRIBs
         of batch i are written while batch i+1 is on the device) are drained at the end.  Returns the list of un-normalised predictions."""
