@@ -604,6 +604,43 @@ int p4c_grib_unpack_complex(const unsigned char* bytes, int64_t nbytes, const p4
                             const p4c_grib_cfield* fields_host, int nfields, float* planes, int32_t* status, void* workspace,
                             p4c_stream_t stream);
 
+/* The training sub-domain straight out of simple-packed fields that are already on the target grid (csrc/grib_window.hip):
+ * p4c_grib_unpack followed by p4c_regrid_pack with an identity plan, in one launch and with the same bits.  Simple packing without
+ * a bitmap is random access, so only the byte range of a stream that holds the window's rows (the "slice",
+ * py4cast_amd/grib2.py: window_slice) has to lie in `bytes`.
+ *
+ * p4c_grib_window_pack: out (B,T,H,W,F) fp32 features-last; element (b,t,y,x,f) comes from fields[(b*T + t)*F + f]:
+ *   p = (row0 + y*row_step)*ni + col0 + x is its stream point (latitude flip, scanning direction and sub-domain origin folded in);
+ *   X = the unsigned nbits-bit integer at bit p*nbits - bit0 of the slice, most significant bit first (nbits == 0: X = 0, no read);
+ *   in float64, one rounded operation each: t = R + ldexp(X, E); y = t / 10^D (D >= 0) or t * 10^-D; v = (float)y;
+ *   in fp32, two rounded operations: c = v - mean; out = c / std  (mean 0, std 1: v unchanged).
+ * No byte outside [slice_off, slice_off + slice_len) is read; the last, partial word of a slice is put together from its bytes.
+ * One launch, no atomics: two calls give the same bits.  `fields` is the table in DEVICE memory, `fields_host` the same table in
+ * host memory, which the checks read.
+ * Errors (nothing is launched): a null pointer; `bytes` not 4-byte aligned; F < 1 or F > p4c_grib_window_max_features() (144: the
+ * LDS tile); B*T*H*W >= 2^31; bitmap_off other than -1 (a field with a bitmap goes through p4c_grib_unpack); nbits outside
+ * 0 .. 32; |D| > 15; slice_off or bit0 negative or no multiple of 4 bytes; a slice that does not lie inside [0, nbytes); row_step
+ * other than 1 and -1; a window that leaves the rows of ni points or the rows from 0 on; a value of the window with a bit outside
+ * the slice. */
+typedef struct p4c_grib_wfield {
+    int64_t slice_off;  /* byte offset of the shipped slice in `bytes`, a multiple of 4 */
+    int64_t slice_len;  /* its length in bytes */
+    int64_t bit0;       /* bit offset of the slice's first byte within the field's stream, a multiple of 32 */
+    int64_t bitmap_off; /* -1: every point present; anything else is refused */
+    int32_t ni;         /* stream row length */
+    int32_t row0;       /* stream row of output row 0 */
+    int32_t row_step;   /* 1 or -1: output row y is stream row row0 + y*row_step */
+    int32_t col0;       /* stream column of output column 0 */
+    int32_t nbits;      /* 0 .. 32 */
+    int32_t E, D;       /* binary and decimal scale factors */
+    float R;            /* reference value */
+    float mean, std;    /* the standardisation of the field's feature */
+} p4c_grib_wfield;
+
+int p4c_grib_window_max_features(void);
+int p4c_grib_window_pack(const unsigned char* bytes, int64_t nbytes, const p4c_grib_wfield* fields, const p4c_grib_wfield* fields_host,
+                         float* out, int B, int T, int H, int W, int F, p4c_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * K2+K3 fused (training path): one AR step's state update AND its contribution to the
  * training loss in a single pass over (B,N,F) -- the target of step i is also the border

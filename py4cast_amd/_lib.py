@@ -73,6 +73,8 @@ SIGNATURES = {
     "p4c_grib_unpack": [P, L, P, P, I, P, P, P],
     # bytes, nbytes, fields (device), fields (host), nfields, planes, status, ws, stream
     "p4c_grib_unpack_complex": [P, L, P, P, I, P, P, P, P],
+    # bytes, nbytes, fields (device), fields (host), out, B, T, H, W, F, stream
+    "p4c_grib_window_pack": [P, L, P, P, P, I, I, I, I, I, P],
     "p4c_ar_update_loss_fwd": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F, P],
     "p4c_ar_update_loss_fwd_next": [P, L, P, I, I, P, L, P, P, P, P, P, L, P, F, P, I, I, P, L, P, I, L, I, F,
                                     P, I, P, L, I, P, L, I, P],
@@ -141,6 +143,7 @@ OTHER = {
     "p4c_grib_complex_chunk": ([], c_int),
     "p4c_grib_complex_max_blocks": ([], c_int),
     "p4c_grib_unpack_complex_workspace_bytes": ([L, L, I], c_size_t),
+    "p4c_grib_window_max_features": ([], c_int),
     "p4c_set_side_stream": ([P, P, I], c_int),
     "p4c_ghost_dw_fwd": ([P, P, P, I, I, I, I, P], c_int),
     "p4c_ghost_dw_bwd_data": ([P, P, P, I, I, I, I, P], c_int),

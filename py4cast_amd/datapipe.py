@@ -195,6 +195,86 @@ def load_native_batch(groups, io_names: List[str], forcing: NamedTensor, stats, 
     return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
 
 
+class WindowTable(NamedTuple):
+    """What ``load_window_batch`` launches with: ``fields`` (B, T, F) ``ops.GRIB_WFIELD`` records (mean 0, std 1: the batch call fills
+    them in), the F feature ``names`` of its last axis and the sub-domain's ``shape`` (H, W)."""
+    fields: np.ndarray
+    names: tuple
+    shape: tuple
+
+
+def window_rows(plan) -> tuple:
+    """(first, end) of the NORTH-FIRST native plane rows an identity ``plan`` reads: the rows ``grib2.window_slice`` has to ship"""
+    if not plan.identity:
+        raise ValueError("window_rows: the plan resizes; only a plane already on the target grid is read through a window")
+    rows = plan.window[0] + plan.row_taps["i0"].astype(np.int64)
+    return int(rows.min()), int(rows.max()) + 1
+
+
+def window_qualifies(field, plan) -> bool:
+    """a field ``p4c_grib_window_pack`` decodes: simple-packed, no bitmap, already on the target grid (an identity plan of its size)"""
+    from . import grib2
+
+    return bool(grib2.window_qualifies(field) and plan.identity and (field.nj, field.ni) == plan.src_shape)
+
+
+def window_table(fields, places, names: Sequence[str], plan) -> WindowTable:
+    """fields[f][b][t]: ``grib2.PackedField``s that ``window_qualifies``; places[f][b][t] = (slice_off, slice_len, bit0): where the
+    field's slice (``grib2.window_slice`` over ``window_rows(plan)``) lies in the byte buffer and the bit of the stream it starts at;
+    plan: the identity ``RegridPlan`` they share.  The plan's flip, window and sub-domain and each file's scanning direction are folded
+    into ``row0`` / ``row_step`` / ``col0``."""
+    F, B, T = len(fields), len(fields[0]), len(fields[0][0])
+    if len(names) != F:
+        raise ValueError(f"window_table: {len(names)} names for {F} features")
+    H, W = plan.out_shape
+    prow = plan.window[0] + plan.row_taps["i0"].astype(np.int64)       # north-first native row of every output row
+    step = int(prow[1] - prow[0]) if H > 1 else 1
+    if not plan.identity or (H > 1 and (abs(step) != 1 or not np.array_equal(np.diff(prow), np.full(H - 1, step)))):
+        raise ValueError("window_table: the plan is no identity: its rows are not consecutive plane rows")
+    col0 = int(plan.window[2] + plan.col_taps["i0"][0])
+    table = np.zeros((B, T, F), dtype=ops.GRIB_WFIELD)
+    table["bitmap_off"], table["std"] = -1, 1.0
+    for fi in range(F):
+        for b in range(B):
+            for t in range(T):
+                f = fields[fi][b][t]
+                if not window_qualifies(f, plan):
+                    raise ValueError(f"window_table: feature {names[fi]!r}, sample {b}, step {t}: not a simple-packed field without bitmap "
+                                     f"on the plan's {plan.src_shape} grid")
+                rec = table[b, t, fi]
+                rec["slice_off"], rec["slice_len"], rec["bit0"] = places[fi][b][t]
+                rec["ni"], rec["nbits"], rec["E"], rec["D"], rec["R"], rec["col0"] = f.ni, f.nbits, f.E, f.D, f.R, col0
+                rec["row0"] = f.nj - 1 - int(prow[0]) if f.south_to_north else int(prow[0])
+                rec["row_step"] = -step if f.south_to_north else step
+    return WindowTable(table, tuple(names), (H, W))
+
+
+def load_window_batch(bytes_dev: torch.Tensor, table: WindowTable, io_names: List[str], forcing: NamedTensor, stats,
+                      num_input_steps: int, standardize: bool = True) -> ItemBatch:
+    """``load_native_batch`` for fields that need no native plane at all: simple-packed, without bitmap, already on the target grid
+    (``window_qualifies``).  The slices of their bit streams that hold the sub-domain's rows lie in ``bytes_dev``
+    (``grib2.window_slice``), and ONE ``p4c_grib_window_pack`` launch decodes the window's values, standardises them and packs them
+    features-last: the bits of ``ops.grib_unpack`` followed by ``load_native_batch`` with the identity plan.  table: ``window_table``'s;
+    io_names: the output feature order, a permutation of the table's names.  -> the ItemBatch of ``load_batch``."""
+    io_names = list(io_names)
+    if sorted(io_names) != sorted(table.names) or len(set(io_names)) != len(io_names):
+        raise ValueError(f"load_window_batch: io_names and the table's names differ: {sorted(set(table.names) ^ set(io_names))}")
+    B, T, F = table.fields.shape
+    if not 0 < num_input_steps <= T:
+        raise ValueError(f"load_window_batch: {num_input_steps} input steps of {T}")
+    order = [table.names.index(n) for n in io_names]
+    fields = np.ascontiguousarray(table.fields[:, :, order])
+    if standardize:
+        fields["mean"] = np.asarray(stats.to_list("mean", io_names).tolist(), dtype=np.float32)
+        fields["std"] = np.asarray(stats.to_list("std", io_names).tolist(), dtype=np.float32)
+    else:
+        fields["mean"], fields["std"] = 0.0, 1.0
+    full = ops.grib_window_pack(bytes_dev, fields, B, T, *table.shape, F)
+    inputs = NamedTensor(full[:, :num_input_steps], DIMS.copy(), io_names)
+    outputs = NamedTensor(full[:, num_input_steps:], DIMS.copy(), list(io_names))
+    return ItemBatch(inputs=inputs, forcing=forcing, outputs=outputs)
+
+
 def build_forcing(raw: Optional[torch.Tensor], ext_names: Sequence[str], stats, dates: Sequence[datetime],
                   timedeltas: Sequence[timedelta], lat, lon, standardize: bool = True, device=None) -> NamedTensor:
     """Device-side forcing of ``Sample.load`` (base.py:455-527): the ``kind == "input"`` parameters standardised, then the five

@@ -12,6 +12,8 @@ From a dataset configuration to batches on the device: the 
   copy stream ships a finished buffer, and on the consumer's stream one pack kernel (``p4c_pack_standardize`` /
   ``p4c_pack_convert``) and ``p4c_build_forcing`` make the ``ItemBatch`` (``Sample.load`` + ``collate_fn``, base.py:455-527,173-195).
   DESIGN.md 4.9 has the layout and the buffer lifetime.
+* ``GribRoutes``: Titan's ``file_format: grib`` in the loader -- packed bit streams in the ring slots, decoded on the device by the
+  window kernel or by unpack + regrid.
 """
 
 import datetime as dt
@@ -250,6 +252,14 @@ class PlaneReadError(RuntimeError):
     """a plane could not be read; the message starts with the file's path"""
 
 
+class GribReadError(PlaneReadError):
+    """a message of a GRIB dataset could not be found, parsed or laid out; ``param`` is the parameter it belongs to"""
+
+    def __init__(self, path, param, why):
+        super().__init__(f"{path}: {why}")
+        self.path, self.param = path, param
+
+
 def _fill(f, dst: np.ndarray) -> None:
     view = memoryview(dst).cast("B")
     got = 0
@@ -363,7 +373,9 @@ class TitanAccessor(DataAccessor):
     """datasets/titan/__init__.py, ``file_format: npy``: one 2-D ``.npy`` per (date, parameter) under
     ``<root>/subdatasets/<name>_<grid>_<subdomain>/data`` (``diskio.titan_plane_path``), already on the sub-domain.  The grid comes
     from ``<root>/conf_<grid>.grib`` through this package's ``grib2``: latitude / longitude from section 3 (template 3.0), the
-    ``h`` field decoded by ``grib2.decode``.  ``file_format: grib`` batches go through ``diskio.load_titan_grib_batch``."""
+    ``h`` field decoded by ``grib2.decode``.  ``file_format: grib`` (the reference's default): ``<root>/grib/<date>/<grib_name>``
+    (``diskio.titan_grib_path``), messages found by numeric keys (``grib_fid``), decoded, regridded and cut on the device by
+    ``DeviceLoader`` (``GribRoutes``); ``diskio.convert_titan_grib_to_npy`` writes the ``.npy`` sub-dataset from them."""
 
     registry_key = "titan"
     GRIDS = ("PAAROME_1S100", "PAAROME_1S40")
@@ -403,10 +415,50 @@ class TitanAccessor(DataAccessor):
         return f"{param.name}_{param.level}{'m' if param.level_type in ('surface', 'heightAboveGround') else 'hpa'}"
 
     def paths(self, ds_name, param, timestamps, file_format):
+        if file_format == "grib":   # :103-105
+            return [diskio.titan_grib_path(self.root, param.grib_name, date) for date in timestamps.validity_times]
         if file_format != "npy":
-            raise NotImplementedError("TitanAccessor reads file_format 'npy'; GRIB batches go through diskio.load_titan_grib_batch")
+            raise NotImplementedError(f"TitanAccessor reads file_format 'npy' and 'grib', not {file_format!r}")
         folder = self.get_dataset_path(ds_name, param.grid)
         return [diskio.titan_plane_path(folder, param.name, param.level, param.level_type, date) for date in timestamps.validity_times]
+
+    def grib_fid(self, param: WeatherParam) -> dict:
+        """The numeric keys (``grib2.MATCHED_KEYS``) a parameter's message is found by: ``metadata["WEATHER_PARAMS"][name]["grib_keys"]``
+        with ``level`` filled from the parameter's level when it is absent, else ``outputs.grib_fid`` of the feature name.  The
+        reference selects by ``shortName`` (``param``), which lives in eccodes' tables and not in a message: a parameter with neither
+        is refused by name."""
+        from . import grib2, outputs
+
+        keys = self.metadata["WEATHER_PARAMS"][param.name].get("grib_keys")
+        if keys is not None:
+            unknown = sorted(set(keys) - set(grib2.MATCHED_KEYS))
+            if unknown or not keys:
+                raise ValueError(f"parameter {param.name}: grib_keys {unknown or dict(keys)} are none of {grib2.MATCHED_KEYS}")
+            fid = dict(keys)
+            fid.setdefault("level", param.level)
+            return fid
+        fid, _ = outputs.grib_fid(self.parameter_namer(param), 3600)
+        if fid is None:
+            raise ValueError(f"parameter {param.name} (feature {self.parameter_namer(param)}): file_format 'grib' needs the numeric keys of "
+                             f"its message: add 'grib_keys' (a mapping over {grib2.MATCHED_KEYS}) to its metadata entry; matching by "
+                             f"shortName {param.grib_param!r} is out of scope (eccodes' tables)")
+        return fid
+
+    def regrid_plan(self, param: WeatherParam, src_shape, lat, lon):
+        """``fit_to_grid`` (:184-208) for planes of ``src_shape`` with north-first ``lat`` and ``lon`` vectors, the latitude flip of
+        ``load_data_for_date`` and the sub-domain of titan_cli.py:36 as a ``regrid.RegridPlan``: an identity for a parameter already
+        on the target grid, the crop to the target grid's extent for ``PA_01D``, anti-aliasing towards ``PAAROME_1S40`` only."""
+        from . import regrid
+
+        grid = param.grid
+        if param.native_grid == grid.name:
+            if tuple(src_shape) != tuple(grid.full_size):
+                raise ValueError(f"parameter {param.name}: a plane of {tuple(src_shape)} on its own grid {grid.name} of {tuple(grid.full_size)}")
+            return regrid.RegridPlan(src_shape, grid.full_size, subdomain=grid.subdomain)
+        window = None
+        if param.native_grid == "PA_01D":
+            window = regrid.titan_window(lat, lon, self.metadata["GRIDS"][grid.name]["extent"])
+        return regrid.RegridPlan(src_shape, grid.full_size, window=window, subdomain=grid.subdomain, anti_aliasing=grid.name == "PAAROME_1S40")
 
     def read_plane(self, ds_name, param, timestamps, step, member, file_format, dst):
         path = self.paths(ds_name, param, Timestamps(timestamps.datetime, [list(timestamps.timedeltas)[step]]), file_format)[0]
@@ -669,6 +721,9 @@ class NativeDataset:
         self.name, self.grid, self.period, self.params, self.settings, self.accessor = name, grid, period, params, settings, accessor
         self.shuffle = period.name == "train"
         self.cache_dir = accessor.cache_dir(name, grid)
+        if settings.file_format == "grib" and hasattr(accessor, "grib_fid"):
+            for p in params:                 # a parameter whose messages cannot be found is refused here, by name
+                accessor.grib_fid(p)
 
     def __str__(self) -> str:
         return f"{self.name}_{self.grid.name}"
@@ -831,6 +886,163 @@ def _layout(groups, B: int, H: int, W: int):
     return places, at
 
 
+class _GribPending:
+    """a GRIB batch between its submission and its turn: the index futures of the files that were not in the cache, then -- laid out --
+    its copy futures, its bytes and its layouts.  Unpacks like the (futures, bytes, places) of the other formats."""
+
+    def __init__(self, slot, dates):
+        self.slot, self.dates, self.held, self.index = slot, dates, {}, {}
+        self.futures, self.nbytes, self.layouts, self.error = None, 0, [], None
+
+    def __iter__(self):
+        return iter((list(self.index.values()) + (self.futures or []), self.nbytes, self))
+
+
+class _GribLayout:
+    """where the fields of one group of one batch lie in a byte buffer, and which route decodes them"""
+
+    def __init__(self, window, entries, plans, names, where, copies, start, end):
+        self.window, self.entries, self.plans, self.names, self.where = window, entries, plans, names, where
+        self.copies, self.start, self.end = copies, start, end
+
+
+class GribRoutes:
+    """From (parameters, validity dates) of a Titan GRIB dataset to the features-last tensor on the sub-domain, in the three steps a
+    ``DeviceLoader`` spreads over its threads and streams: ``files.get`` indexes a file (a shared LRU),
+    ``layout`` decides the route of a group and where every message's bytes go in a byte buffer, ``copy`` is one ``memcpy`` of one
+    message's bytes, ``decode`` launches on the device copy of the buffer.
+
+    * window route (``p4c_grib_window_pack``, one launch): every field of the group is simple-packed, without bitmap and already on
+      the target grid; only the byte range of each stream that holds the sub-domain's rows is copied (``grib2.window_slice``).
+    * regrid route (``p4c_grib_unpack`` / ``p4c_grib_unpack_complex``, then ``p4c_regrid_pack``): any other group, as a whole; the
+      whole streams and bitmaps are copied.  This is ``diskio.load_titan_grib_batch``.
+    ``counts`` says how many groups went each way.  ``use_window = False`` sends every group the second way."""
+
+    def __init__(self, dataset: "NativeDataset", cache: int = 50, check: bool = True):
+        acc = dataset.accessor
+        if not (hasattr(acc, "grib_fid") and hasattr(acc, "regrid_plan")):
+            raise NotImplementedError(f"{type(acc).__name__} has no GRIB layout: file_format 'grib' is read for Titan")
+        self.dataset, self.files, self.check = dataset, diskio.GribFileCache(cache), bool(check)
+        self.use_window = True
+        self.counts = {"window": 0, "regrid": 0}
+        self._plans: Dict[tuple, Any] = {}
+        self._fids: Dict[int, dict] = {}
+        self._host: Optional[torch.Tensor] = None
+
+    def path(self, param: WeatherParam, date: dt.datetime) -> Path:
+        return diskio.titan_grib_path(self.dataset.accessor.root, param.grib_name, date)
+
+    def plan_of(self, param: WeatherParam, message, field):
+        from . import grib2
+
+        ni, nj, lat, lon, _ = grib2.grid_of(message)
+        lat = lat[::-1] if field.south_to_north else lat          # north first, as the decoded planes are
+        key = (param.native_grid, nj, ni, round(float(lat[0]), 5), round(float(lat[-1]), 5), round(float(lon[0]), 5), round(float(lon[-1]), 5))
+        if key not in self._plans:
+            self._plans[key] = self.dataset.accessor.regrid_plan(param, (nj, ni), lat, lon)
+        return self._plans[key]
+
+    def layout(self, params: Sequence[WeatherParam], names: Sequence[str], dates: Sequence[Sequence[dt.datetime]], at: int = 0,
+               files: Optional[Dict[str, Any]] = None) -> _GribLayout:
+        """dates[b][t]: the validity times of the group's planes; at: the first free byte of the buffer, a multiple of 4; files: parsed
+        files by path that the caller holds for the batch (whatever the LRU has evicted since; others come from ``self.files``).
+        Every field of a parameter must lie on ONE grid -- size, latitudes and longitudes, as ``GribPlaneReader`` asks of a call --:
+        the parameter's plan, the pitch of its planes and its crop come from it.  A file that cannot be read, a message that is not
+        found and a field on another grid raise ``GribReadError`` naming the file."""
+        from . import datapipe, grib2
+
+        files = files if files is not None else {}
+        entries, plans = [], []
+        for p in params:
+            if id(p) not in self._fids:
+                self._fids[id(p)] = self.dataset.accessor.grib_fid(p)
+            per_f, plan, first = [], None, None
+            for sample in dates:
+                per_f.append([])
+                for d in sample:
+                    path = str(self.path(p, d))
+                    try:
+                        m, f = (files.get(path) or self.files.get(path)).field(self._fids[id(p)])
+                        mine = self.plan_of(p, m, f)
+                    except (OSError, KeyError, ValueError) as e:          # grib2.GribError is a ValueError
+                        raise GribReadError(path, p, f"{type(e).__name__}: {e}") from e
+                    if plan is None:
+                        plan, first = mine, path
+                    elif mine is not plan:
+                        raise GribReadError(path, p, f"{self.dataset.accessor.parameter_namer(p)} is on a grid of {f.nj} x {f.ni} whose latitudes or "
+                                                     f"longitudes differ from those of {first} ({plan.src_shape[0]} x {plan.src_shape[1]}): one "
+                                                     f"parameter reads one grid")
+                    per_f[-1].append((path, m, f))
+            entries.append(per_f)
+            plans.append(plan)
+        window = self.use_window and all(pl is plans[0] for pl in plans) and all(
+            datapipe.window_qualifies(f, plans[0]) for per_f in entries for per_b in per_f for _, _, f in per_b)
+        rows = datapipe.window_rows(plans[0]) if window else None
+        start, place, copies = at, {}, []
+        for per_f in entries:
+            for per_b in per_f:
+                for path, m, f in per_b:
+                    if (path, id(m)) in place:        # a message selected twice (samples that overlap in a date) is copied once
+                        continue
+                    if window:
+                        first, end, bit0 = grib2.window_slice(f, *rows)
+                        place[path, id(m)] = (at, end - first, bit0)
+                        copies.append((at, f.stream, first, end))
+                        at += (end - first + 3) // 4 * 4
+                    else:
+                        s_off, b_off = at, -1
+                        copies.append((at, f.stream, 0, len(f.stream)))
+                        at += (len(f.stream) + 3) // 4 * 4
+                        if f.bitmap is not None:
+                            b_off = at
+                            copies.append((at, f.bitmap, 0, len(f.bitmap)))
+                            at += (len(f.bitmap) + 3) // 4 * 4
+                        place[path, id(m)] = (s_off, b_off)
+        where = [[[place[path, id(m)] for path, m, _ in per_b] for per_b in per_f] for per_f in entries]
+        return _GribLayout(window, entries, plans, list(names), where, copies, start, at)
+
+    @staticmethod
+    def copy(buf: np.ndarray, at: int, source, first: int, end: int) -> None:
+        """one message's bytes ``source[first:end]`` as they lie in the file into the buffer: no crop, no value touched"""
+        buf[at:at + end - first] = np.frombuffer(source, dtype=np.uint8)[first:end]
+
+    def decode(self, dev: torch.Tensor, lay: _GribLayout, stats, standardize: bool) -> torch.Tensor:
+        """the group's (B, T, H, W, F) fp32 features-last tensor from the device copy ``dev`` of the buffer"""
+        from . import datapipe
+
+        B, T = len(lay.entries[0]), len(lay.entries[0][0])
+        if lay.window:
+            fields = [[[f for _, _, f in per_b] for per_b in per_f] for per_f in lay.entries]
+            table = datapipe.window_table(fields, lay.where, lay.names, lay.plans[0])
+            self.counts["window"] += 1
+            return datapipe.load_window_batch(dev, table, lay.names, None, stats, T, standardize).inputs.tensor
+        groups = []
+        for plan in dict.fromkeys(lay.plans):                     # one unpack call per native grid, in the order of its first parameter
+            mine = [i for i, pl in enumerate(lay.plans) if pl is plan]
+            chosen = [e for i in mine for per_b in lay.entries[i] for e in per_b]
+            where = [w for i in mine for per_b in lay.where[i] for w in per_b]
+            nj, ni = plan.src_shape
+            pitch = (nj * ni + 3) // 4 * 4
+            flat, _ = diskio.decode_placed(dev, chosen, where, pitch, self.check)
+            groups.append((flat.as_strided((len(mine), B, T, nj, ni), (B * T * pitch, T * pitch, pitch, ni, 1)), [lay.names[i] for i in mine], plan))
+        self.counts["regrid"] += 1
+        return datapipe.load_native_batch(groups, lay.names, None, stats, T, standardize).inputs.tensor
+
+    def planes(self, params: Sequence[WeatherParam], dates: Sequence[dt.datetime], device) -> torch.Tensor:
+        """(len(dates), H, W, len(params)) fp32 on ``device``: the un-standardised sub-domain planes of ``params`` at ``dates``, through
+        the same two routes (a blocking call on the current stream: the conversion's, not the loader's)"""
+        acc = self.dataset.accessor
+        lay = self.layout(params, [acc.parameter_namer(p) for p in params], [[d] for d in dates])
+        if self._host is None or self._host.numel() < lay.end:
+            self._host = torch.empty(max(lay.end, 16), dtype=torch.uint8, pin_memory=torch.device(device).type == "cuda")
+        buf = self._host.numpy()
+        for c in lay.copies:
+            self.copy(buf, *c)
+        dev = self._host[:max(lay.end, 16)].to(device)
+        with torch.cuda.device(dev.device):
+            return self.decode(dev, lay, None, False)[:, 0]
+
+
 class DeviceLoader:
     """An iterable of ``ItemBatch``es on ``device`` over a ``NativeDataset`` (``Sample.load`` + ``collate_fn``, base.py:455-527,173-195).
 
@@ -843,6 +1055,10 @@ class DeviceLoader:
     only.  Inputs and outputs are the ``input_output`` parameters and ``input`` parameters are forcing planes at the prediction
     steps, each group in the order of the configuration; a configuration with ``output``-only parameters is refused with the
     error the reference's ``Item`` raises for it (base.py:98-113).
+
+    A dataset whose ``file_format`` is ``grib`` (Titan) goes through ``GribRoutes`` instead: the threads index the batch's files and
+    copy each message's packed bytes, the slot grows when a batch needs more, and every group is decoded by
+    ``p4c_grib_window_pack`` or by unpack + regrid (``routes.counts``); CUDA only.
 
     Shuffling draws ``torch.randperm`` from ``torch.Generator().manual_seed(seed + epoch)``; the epoch counts the iterations
     started.  A reader's exception surfaces at ``__next__`` as ``PlaneReadError`` naming the file.  ``close()`` (or leaving the
@@ -871,6 +1087,8 @@ class DeviceLoader:
         self.copied: List[Optional[torch.cuda.Event]] = []
         self.copy_stream = torch.cuda.Stream(self.device) if self.cuda else None
         self.waited_s = 0.0     # host seconds __next__ spent waiting for reads (the consumer arriving before its batch)
+        self._indexing: Dict[str, Any] = {}           # file_format "grib": path -> the future of a parse that a batch still waits for
+        self.routes: Optional["GribRoutes"] = None    # file_format "grib": the decode routes; routes.counts says which way the groups went
 
     # -- sizes
     def __len__(self) -> int:
@@ -899,10 +1117,17 @@ class DeviceLoader:
             # base.py:455-527 would append an ``output`` parameter to the targets, but the Item it then builds refuses targets that
             # are not the inputs' features (base.py:98-113): such a configuration yields no batch in the reference either
             raise ValueError(f"Inputs and outputs must have the same feature names, got {io_names} and {out_names}")
+        if s.file_format == "grib" and self.routes is None:      # kept over the epochs: its file index and its counters
+            if not self.cuda:
+                raise ValueError("DeviceLoader: file_format 'grib' needs a CUDA device: the decode and the regrid have no host path")
+            self.routes = GribRoutes(ds)
         for kind, steps in (("input_output", list(range(T_all))), ("input", list(range(T_in, T_all)))):
             params = [p for p in ds.params if p.kind == kind]
             if not params:
                 self.groups.append(None)
+                continue
+            if self.routes is not None:      # packed bit streams: no plane dtype, the layout is decided batch by batch
+                self.groups.append(_Group(params, [ds.accessor.parameter_namer(p) for p in params], steps, None, None))
                 continue
             dtypes = {np.dtype(ds.accessor.plane_dtype(s.dataset_name, p, first.timestamps, s.file_format)) for p in params}
             if len(dtypes) != 1:
@@ -911,7 +1136,7 @@ class DeviceLoader:
             self.groups.append(_Group(params, [ds.accessor.parameter_namer(p) for p in params], steps, dtypes.pop(),
                                       [ds.accessor.transform(p, s.file_format) for p in params]))
         H, W = ds.grid.x, ds.grid.y
-        _, at = _layout(self.groups, self.batch_size, H, W)
+        _, at = (None, 16) if self.routes is not None else _layout(self.groups, self.batch_size, H, W)    # GRIB: grown by the first batches
         pin = self.cuda
         self.buffers = [torch.empty(max(at, 16), dtype=torch.uint8, pin_memory=pin) for _ in range(self.prefetch + 1)]
         self.copied = [None] * (self.prefetch + 1)
@@ -950,6 +1175,8 @@ class DeviceLoader:
         if self.copied[slot] is not None:
             self.copied[slot].synchronize()      # the copy that last read this buffer has left it
             self.copied[slot] = None
+        if self.routes is not None:
+            return self._submit_grib(slot, samples)
         H, W = self.dataset.grid.x, self.dataset.grid.y
         B = len(samples)
         places, at = _layout(self.groups, B, H, W)
@@ -963,6 +1190,53 @@ class DeviceLoader:
                     for t in range(len(g.steps)):
                         futures.append(self.pool.submit(self._read, sample, g, fi, t, view[fi, b, t]))
         return futures, at, places
+
+    def _submit_grib(self, slot: int, samples: List[Sample]) -> "_GribPending":
+        """Hand the batch's files that are not in the index to the reader threads and do not wait for them.  The headers decide each
+        group's route and where every message goes, so the batch is laid out -- and its copies handed to the threads -- once they
+        are there (``_lay_out``): at once when the index already holds every file, else when the iteration next comes by, at the
+        latest when the batch is asked for.  A parse is so hidden behind the consumer's work from prefetch 1 on, the copies from
+        prefetch 1 on with a warm index and from prefetch 2 on without."""
+        dates = [None if g is None else [(smp.timestamps if g.steps[0] == 0 else smp.output_timestamps).validity_times for smp in samples]
+                 for g in self.groups]
+        rec = _GribPending(slot, dates)
+        for path in dict.fromkeys(self.routes.path(p, d) for g, ds in zip(self.groups, dates) if g is not None for p in g.params for smp in ds for d in smp):
+            f = self.routes.files.peek(path)
+            if f is not None:
+                rec.held[str(path)] = f
+            else:            # a file an earlier batch is still waiting for is parsed once
+                if str(path) not in self._indexing:
+                    self._indexing[str(path)] = self.pool.submit(self.routes.files.get, path)
+                rec.index[str(path)] = self._indexing[str(path)]
+        self._lay_out(rec, block=False)
+        return rec
+
+    def _lay_out(self, rec: "_GribPending", block: bool) -> None:
+        """Once the batch's files are indexed (``block``: wait for them): lay the groups out one after the other in the slot, grown
+        when the batch needs more, and hand one copy per message to the threads.  An error waits in ``rec.error`` for the batch's turn."""
+        if rec.futures is not None or (not block and not all(f.done() for f in rec.index.values())):
+            return
+        rec.futures = []
+        try:
+            for path, f in rec.index.items():
+                try:
+                    if self._indexing.get(path) is f:
+                        del self._indexing[path]     # from here on the cache answers (or parses again what it has evicted)
+                    rec.held[path] = f.result()      # alive until the batch is laid out, whatever the LRU evicts meanwhile
+                except Exception as e:
+                    raise PlaneReadError(f"{path}: {type(e).__name__}: {e}") from e
+            at = 0
+            for g, ds in zip(self.groups, rec.dates):
+                rec.layouts.append(None if g is None else self.routes.layout(g.params, g.names, ds, at, files=rec.held))   # GribReadError names the file
+                at = at if g is None else rec.layouts[-1].end
+            if self.buffers[rec.slot].numel() < at:          # the slot is quiet: its last copy was waited for when the batch was submitted
+                self.buffers[rec.slot] = torch.empty(at + at // 8, dtype=torch.uint8, pin_memory=self.cuda)
+            buf = self.buffers[rec.slot].numpy()
+            rec.nbytes = at
+            rec.futures = [self.pool.submit(GribRoutes.copy, buf, *c) for lay in rec.layouts if lay is not None for c in lay.copies]
+        except Exception as e:
+            rec.error = e
+        rec.held = {}
 
     # -- iteration
     def __iter__(self):
@@ -987,9 +1261,13 @@ class DeviceLoader:
                         break
                     pending[submitted] = self._submit(submitted % ring, batches[submitted])
                     submitted += 1
-                futures, nbytes, places = pending.pop(k)
                 t0 = time.perf_counter()
-                error = None
+                if self.routes is not None:
+                    for later in pending.values():       # batches whose files have been indexed meanwhile: their copies start now
+                        self._lay_out(later, block=False)
+                    self._lay_out(pending[k], block=True)
+                futures, nbytes, places = pending.pop(k)
+                error = getattr(places, "error", None)
                 for f in futures:
                     try:
                         f.result()
@@ -1001,6 +1279,7 @@ class DeviceLoader:
                 yield self._make(k % ring, samples, nbytes, places)
         finally:
             self._drain(pending)
+            self._indexing.clear()
             if self.close_after_epoch:
                 self.close()
 
@@ -1031,8 +1310,11 @@ class DeviceLoader:
             current.wait_event(self.copied[slot])
             dev.record_stream(current)
             with torch.cuda.device(self.device):
-                packed = [None if g is None else pack_typed(self._slot_view(slot, g, place, B, H, W, base=dev), g.names, g.transforms, stats, standardize)
-                          for g, place in zip(self.groups, places)]
+                if self.routes is not None:
+                    packed = [None if g is None else self.routes.decode(dev, lay, stats, standardize) for g, lay in zip(self.groups, places.layouts)]
+                else:
+                    packed = [None if g is None else pack_typed(self._slot_view(slot, g, place, B, H, W, base=dev), g.names, g.transforms, stats, standardize)
+                              for g, place in zip(self.groups, places)]
         else:
             packed = [None if g is None else pack_typed(self._slot_view(slot, g, place, B, H, W).copy(), g.names, g.transforms, stats, standardize, host=True)
                       for g, place in zip(self.groups, places)]

@@ -12,6 +12,8 @@ On-disk formats either side of the hot path, host side.
   dataset at datasets/dummy.py:24-42).
 * Titan's GRIB layout (``file_format="grib"``, the reference's default: datasets/titan/__init__.py:112-152): ``GribPlaneReader``
   ships the packed bit streams of a batch as they lie in the files and ``ops.grib_unpack`` decodes them on the device.
+  ``decode_placed`` is its device half, ``GribFileCache`` the parsed files shared by the loader's threads (``datasets.GribRoutes``),
+  ``convert_titan_grib_to_npy`` the conversion to the ``.npy`` layout above.
 """
 
 import datetime as dt
@@ -227,6 +229,84 @@ def titan_grib_path(dataset_path, grib_name: str, date: dt.datetime) -> Path:
     return Path(dataset_path) / "grib" / date.strftime(TITAN_FORMATSTR) / grib_name
 
 
+def decode_placed(dev: torch.Tensor, chosen, where, pitch: int, check: bool = True):
+    """The device half of ``GribPlaneReader.read``: ``chosen[i]`` = (path, message, field) whose stream and bitmap lie in the device
+    byte buffer ``dev`` at ``where[i]`` = (stream_off, bitmap_off; -1 without a bitmap) -> (flat fp32 tensor with plane i at
+    ``i * pitch`` floats, the status words of the complex-packed fields or None).  ``ops.grib_unpack`` decodes the simple-packed
+    fields, ``ops.grib_unpack_complex`` the others; ``check`` copies the status words back and raises ``grib2.GribError`` naming the
+    file and the condition."""
+    from . import grib2, ops
+
+    # plane i of the output belongs to chosen[i], whichever of the two tables it is decoded from
+    simple = [i for i, (_, _, f) in enumerate(chosen) if not isinstance(f, grib2.ComplexField)]
+    packed = [i for i, (_, _, f) in enumerate(chosen) if isinstance(f, grib2.ComplexField)]
+    table = np.zeros(len(simple), dtype=ops.GRIB_FIELD)
+    for j, i in enumerate(simple):
+        _, _, f = chosen[i]
+        s_off, b_off = where[i]
+        table[j] = (s_off, len(f.stream), b_off, i * pitch, f.ni, f.nj, f.count, f.nbits, f.E, f.D, f.R, int(f.south_to_north), 0, 0)
+    ctable = np.zeros(len(packed), dtype=ops.GRIB_CFIELD)
+    for j, i in enumerate(packed):
+        _, _, f = chosen[i]
+        rec = ctable[j]
+        rec["stream_off"], rec["bitmap_off"] = where[i]
+        rec["stream_len"], rec["dst_off"], rec["flip_rows"] = len(f.stream), i * pitch, int(f.south_to_north)
+        for name in ("ni", "nj", "count", "ng", "ref_bits", "w_ref", "w_bits", "l_ref", "l_inc", "l_last", "l_bits", "order", "nbytes",
+                     "ival1", "ival2", "gmin", "E", "D", "R"):
+            rec[name] = getattr(f, name)
+    status = None
+    with torch.cuda.device(dev.device):
+        flat = torch.empty(len(chosen) * pitch, dtype=torch.float32, device=dev.device)
+        if simple:
+            ops.grib_unpack(dev, table, out=flat)
+        if packed:
+            _, status = ops.grib_unpack_complex(dev, ctable, out=flat)
+    if packed and check:
+        # one blocking copy of len(packed) ints: the price of naming a malformed file here instead of handing on a NaN plane
+        for j, st in enumerate(status.cpu().tolist()):
+            if st:
+                what = [text for bit, text in ((ops.GRIB_STATUS_LENGTHS, "the group lengths do not sum to the number of values"),
+                                               (ops.GRIB_STATUS_WIDTH, "a group width above 32 bits"),
+                                               (ops.GRIB_STATUS_STREAM, "the values need more bits than section 7 holds")) if st & bit]
+                raise grib2.GribError(f"{chosen[packed[j]][0]}: complex-packed message {chosen[packed[j]][1]!r}: {'; '.join(what)}")
+    return flat, status
+
+
+class GribFileCache:
+    """Parsed ``grib2.GribFile``s shared by reader threads: an LRU of ``cache`` files behind a lock (the reference's ``read_grib``
+    keeps 50).  Two threads that ask for one new file at once may both parse it; one result is kept."""
+
+    def __init__(self, cache: int = 50):
+        import threading
+
+        self.cache, self.files, self.lock, self.parsed = max(int(cache), 1), OrderedDict(), threading.Lock(), 0
+
+    def peek(self, path):
+        """the parsed file when the cache holds it (now its most recent one), else None: nothing is read"""
+        with self.lock:
+            f = self.files.get(str(path))
+            if f is not None:
+                self.files.move_to_end(str(path))
+            return f
+
+    def get(self, path):
+        from . import grib2
+
+        key = str(path)
+        with self.lock:
+            if key in self.files:
+                self.files.move_to_end(key)
+                return self.files[key]
+        parsed = grib2.GribFile(path)
+        with self.lock:
+            self.parsed += 1
+            f = self.files.setdefault(key, parsed)
+            self.files.move_to_end(key)
+            while len(self.files) > self.cache:
+                self.files.popitem(last=False)
+        return f
+
+
 class GribPlaneReader:
     """Reads (F, B, T) fields out of GRIB2 files and returns ``(planes (F, B, T, Nj, Ni) fp32, lat (Nj,), lon (Ni,))``.
 
@@ -305,7 +385,7 @@ class GribPlaneReader:
         """selections[f][b][t] = (path, fid) -> (planes (F, B, T, Nj, Ni), lat (Nj,) descending, lon (Ni,)): planes on ``device``, or a
         host tensor when it is None.  On a device every plane is dense and starts at a multiple of 4 floats (16-byte stores): where
         Nj * Ni is no multiple of 4 the tensor is a view with that pitch between planes, not contiguous."""
-        from . import grib2, ops
+        from . import grib2
 
         (F, B, T), chosen, (ni, nj, lat, lon) = self._select(selections)
         if not self.cuda:
@@ -335,25 +415,7 @@ class GribPlaneReader:
             buf[s_off:s_off + len(f.stream)] = np.frombuffer(f.stream, dtype=np.uint8)
             if b_off >= 0:
                 buf[b_off:b_off + len(f.bitmap)] = np.frombuffer(f.bitmap, dtype=np.uint8)
-        N = ni * nj
-        pitch = (N + 3) // 4 * 4
-        # plane i of the output belongs to chosen[i], whichever of the two tables it is decoded from
-        simple = [i for i, (_, _, f) in enumerate(chosen) if not isinstance(f, grib2.ComplexField)]
-        packed = [i for i, (_, _, f) in enumerate(chosen) if isinstance(f, grib2.ComplexField)]
-        table = np.zeros(len(simple), dtype=ops.GRIB_FIELD)
-        for j, i in enumerate(simple):
-            path, m, f = chosen[i]
-            s_off, b_off, _ = place[path, id(m)]
-            table[j] = (s_off, len(f.stream), b_off, i * pitch, f.ni, f.nj, f.count, f.nbits, f.E, f.D, f.R, int(f.south_to_north), 0, 0)
-        ctable = np.zeros(len(packed), dtype=ops.GRIB_CFIELD)
-        for j, i in enumerate(packed):
-            path, m, f = chosen[i]
-            rec = ctable[j]
-            rec["stream_off"], rec["bitmap_off"], _ = place[path, id(m)]
-            rec["stream_len"], rec["dst_off"], rec["flip_rows"] = len(f.stream), i * pitch, int(f.south_to_north)
-            for name in ("ni", "nj", "count", "ng", "ref_bits", "w_ref", "w_bits", "l_ref", "l_inc", "l_last", "l_bits", "order", "nbytes",
-                         "ival1", "ival2", "gmin", "E", "D", "R"):
-                rec[name] = getattr(f, name)
+        pitch = (ni * nj + 3) // 4 * 4
         current = torch.cuda.current_stream(self.device)
         self.copy_stream.wait_stream(current)
         with torch.cuda.stream(self.copy_stream):
@@ -362,24 +424,74 @@ class GribPlaneReader:
             self._copied.record(self.copy_stream)
         current.wait_stream(self.copy_stream)      # the unpack launches run after the transfer
         dev.record_stream(current)
-        self.last_status = None
-        with torch.cuda.device(dev.device):
-            flat = torch.empty(len(chosen) * pitch, dtype=torch.float32, device=dev.device)
-            if simple:
-                ops.grib_unpack(dev, table, out=flat)
-            if packed:
-                _, self.last_status = ops.grib_unpack_complex(dev, ctable, out=flat)
-        if packed and self.check:
-            # one blocking copy of len(packed) ints: the price of naming a malformed file here instead of handing on a NaN plane
-            for j, st in enumerate(self.last_status.cpu().tolist()):
-                if st:
-                    what = [text for bit, text in ((ops.GRIB_STATUS_LENGTHS, "the group lengths do not sum to the number of values"),
-                                                   (ops.GRIB_STATUS_WIDTH, "a group width above 32 bits"),
-                                                   (ops.GRIB_STATUS_STREAM, "the values need more bits than section 7 holds")) if st & bit]
-                    raise grib2.GribError(f"{chosen[packed[j]][0]}: complex-packed message {chosen[packed[j]][1]!r}: {'; '.join(what)}")
+        flat, self.last_status = decode_placed(dev, chosen, [place[path, id(m)][:2] for path, m, _ in chosen], pitch, self.check)
         # no copy: where Nj * Ni is no multiple of 4 the planes keep their pitch (dense planes, which load_native_batch takes as they are)
         planes = flat.as_strided((F, B, T, nj, ni), (B * T * pitch, T * pitch, pitch, ni, 1))
         return planes, lat.copy(), lon.copy()
+
+
+def convert_titan_grib_to_npy(dataset, device=None, batch: int = 8) -> List[Path]:
+    """``convert_samples_grib2_numpy`` of the reference's ``prepare --convert-grib2npy`` (datasets/titan/titan_cli.py:17-44) on the
+    device: for every validity date of every sample of ``dataset`` -- the samples whose GRIB files exist -- and every parameter whose
+    ``.npy`` is not there yet, the float32 sub-domain plane, un-standardised, goes to ``titan_plane_path``.  The planes of up to
+    ``batch`` dates come from one pass of ``datasets.GribRoutes``: the window kernel with mean 0 and std 1 for parameters already on
+    the target grid, unpack + regrid for the others.  A date whose GRIB cannot be read (missing, malformed, a message not found or on another grid) prints the reference's
+    warning and is skipped; any other error, a device error among them, propagates.
+    ``file_format`` and ``standardize`` are put back afterwards.  -> the files written, in order."""
+    from . import datasets as D
+
+    s, acc = dataset.settings, dataset.accessor
+    if device is None:
+        if not torch.cuda.is_available():
+            raise ValueError("convert_titan_grib_to_npy: a CUDA device is needed: the decode and the regrid have no host path")
+        device = torch.device("cuda", torch.cuda.current_device())
+    keep = (s.file_format, s.standardize)
+    written: List[Path] = []
+    # what "cannot be read" means: a file or message that is missing or malformed (GribError is a ValueError; a complex-packed stream
+    # that contradicts its header raises it after the decode).  An error of the device or of this code is not among them and ends the run.
+    unreadable = (D.PlaneReadError, OSError, KeyError, ValueError)
+
+    def target(p, date):
+        return titan_plane_path(acc.get_dataset_path(s.dataset_name, dataset.grid), p.name, p.level, p.level_type, date)
+
+    def convert(params, dates):
+        planes = routes.planes(params, dates, device).cpu().numpy()
+        for b, date in enumerate(dates):
+            for f, p in enumerate(params):
+                path = target(p, date)
+                path.parent.mkdir(parents=True, exist_ok=True)
+                np.save(path, np.ascontiguousarray(planes[b, :, :, f], dtype=np.float32))
+                written.append(path)
+
+    try:
+        s.file_format, s.standardize = "grib", False      # the GRIB files define the valid samples
+        dataset.__dict__.pop("sample_list", None)
+        routes = D.GribRoutes(dataset)
+        todo: "OrderedDict[dt.datetime, tuple]" = OrderedDict()
+        for sample in dataset.sample_list:
+            for date in sample.timestamps.validity_times:
+                if date not in todo:          # the parameters it misses, as indices (a WeatherParam is not hashable)
+                    todo[date] = tuple(i for i, p in enumerate(sample.params) if not target(p, date).exists())
+        for missing in dict.fromkeys(todo.values()):      # dates that miss the same parameters go together
+            params = [dataset.params[i] for i in missing]
+            dates = [d for d, m in todo.items() if m == missing]
+            for k in range(0, len(dates) if params else 0, max(int(batch), 1)):
+                chunk = dates[k:k + max(int(batch), 1)]
+                try:
+                    convert(list(params), chunk)
+                except unreadable:
+                    for date in chunk:                    # one of them cannot be read: date by date, as the reference goes
+                        try:
+                            if not all(target(p, date).exists() for p in params):
+                                convert([p for p in params if not target(p, date).exists()], [date])
+                        except unreadable as e:
+                            p = getattr(e, "param", params[0])
+                            print(e)
+                            print(f"WARNING: Could not load grib {acc.parameter_namer(p)} {p.level} {date}. Skipping.")
+    finally:
+        s.file_format, s.standardize = keep
+        dataset.__dict__.pop("sample_list", None)
+    return written
 
 
 def load_titan_grib_batch(dataset_path, params: List[Tuple[str, str, dict, str]], dates: List[List[dt.datetime]], stats: Stats,

@@ -760,6 +760,57 @@ def unpack_fields(fields: Sequence, flip=False) -> List[np.ndarray]:
     return out
 
 
+def window_qualifies(field) -> bool:
+    """a simple-packed field without a bitmap: value p lies at bit p * nbits, so a window of it can be decoded on its own"""
+    return isinstance(field, PackedField) and field.bitmap is None
+
+
+def window_slice(field: PackedField, row0: int, row1: int) -> Tuple[int, int, int]:
+    """The smallest byte range of ``field.stream`` that holds the NORTH-FIRST plane rows row0 .. row1 - 1 in file order, its start
+    rounded down to a multiple of 4 bytes -> (byte_start, byte_end, bit0), ``bit0 = 8 * byte_start`` the bit offset of the slice's
+    first byte within the stream.  A file that scans south to north holds plane row r as stream row nj - 1 - r.  Only a field
+    ``window_qualifies`` accepts has such a slice; 0 bits per value: the empty slice."""
+    if not window_qualifies(field):
+        raise GribError("window_slice: only a simple-packed field without a bitmap is random access")
+    if not 0 <= row0 < row1 <= field.nj:
+        raise GribError(f"window_slice: rows {row0} .. {row1} of a grid of {field.nj} rows")
+    first, end = (field.nj - row1, field.nj - row0) if field.south_to_north else (row0, row1)
+    if field.nbits == 0:
+        return 0, 0, 0
+    start = (first * field.ni * field.nbits) // 8 // 4 * 4
+    stop = min((end * field.ni * field.nbits + 7) // 8, len(field.stream))
+    return start, stop, 8 * start
+
+
+def unpack_window(field: PackedField, window: Sequence[int], mean: float = 0.0, std: float = 1.0, data=None, bit0: int = 0) -> np.ndarray:
+    """The contract of csrc/grib_window.hip for one field in numpy -> (r1 - r0, c1 - c0) float32.  ``window`` = (r0, r1, c0, c1), ends
+    exclusive, in NORTH-FIRST plane coordinates (a south-to-north file holds plane row r as stream row nj - 1 - r).  X is the
+    nbits-bit big-endian integer at bit (row * ni + col) * nbits - bit0 of ``data``, the shipped slice (default: the whole stream,
+    bit0 = 0); v = float32((R + ldexp(X, E)) / 10^D) in float64 (``* 10^-D`` for D < 0); then c = v - mean, c / std in float32."""
+    if not window_qualifies(field):
+        raise GribError("unpack_window: only a simple-packed field without a bitmap is random access")
+    r0, r1, c0, c1 = (int(v) for v in window)
+    if not (0 <= r0 < r1 <= field.nj and 0 <= c0 < c1 <= field.ni):
+        raise GribError(f"unpack_window: window {tuple(window)} on a grid of {field.nj} x {field.ni}")
+    rows = np.arange(r0, r1, dtype=np.int64)
+    rows = field.nj - 1 - rows if field.south_to_north else rows
+    starts = ((rows[:, None] * field.ni + np.arange(c0, c1, dtype=np.int64)[None, :]) * field.nbits - int(bit0)).reshape(-1)
+    if field.nbits:
+        bits = np.unpackbits(np.frombuffer(field.stream if data is None else data, dtype=np.uint8))
+        if starts.min() < 0 or starts.max() + field.nbits > bits.size:
+            raise GribError(f"unpack_window: the window's bits {int(starts.min())} .. {int(starts.max()) + field.nbits} leave the "
+                            f"{bits.size // 8} octets given")
+        X = _integers_at(bits, starts, field.nbits).astype(np.float64)
+    else:
+        X = np.zeros(starts.size)
+    f4 = np.float32
+    with np.errstate(all="ignore"):
+        scaled = float(field.R) + np.ldexp(X, field.E)
+        v = (scaled / float(10 ** field.D) if field.D >= 0 else scaled * float(10 ** -field.D)).astype(f4)
+        c = v - f4(mean)
+        return (c / f4(std)).reshape(r1 - r0, c1 - c0)
+
+
 class GribFile:
     """An index over the messages of one GRIB2 file for reading: ``find(fid)`` matches as ``Template.find`` does (numeric
     MATCHED_KEYS only, no ``shortName``), ``field(fid)`` is ``field_of`` of that message -- ``complex_field_of`` for templates 5.2 and

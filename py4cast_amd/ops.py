@@ -1128,6 +1128,55 @@ def grib_unpack(bytes_dev: torch.Tensor, fields, out: Optional[torch.Tensor] = N
     return out
 
 
+# ------------------------------------------------------------------------------------------------ GRIB2 simple packing, windowed
+GRIB_WINDOW_MAX_FEATURES = 144   # p4c_grib_window_max_features(): the LDS tile
+# host mirror of p4c_grib_wfield (include/py4cast_hip.h)
+GRIB_WFIELD = np.dtype([("slice_off", "<i8"), ("slice_len", "<i8"), ("bit0", "<i8"), ("bitmap_off", "<i8"), ("ni", "<i4"), ("row0", "<i4"),
+                        ("row_step", "<i4"), ("col0", "<i4"), ("nbits", "<i4"), ("E", "<i4"), ("D", "<i4"), ("R", "<f4"), ("mean", "<f4"),
+                        ("std", "<f4")])
+
+
+def grib_wfields(records, shape=None) -> np.ndarray:
+    """A GRIB_WFIELD table from a sequence of mappings with its column names; ``bitmap_off`` defaults to -1 (no bitmap), ``row_step``
+    and ``std`` to 1, the rest to 0.  A GRIB_WFIELD array is copied."""
+    if isinstance(records, np.ndarray):
+        if records.dtype != GRIB_WFIELD:
+            raise L.P4CError(f"grib_window_pack: a table of dtype {records.dtype}, GRIB_WFIELD expected")
+        return np.ascontiguousarray(records).copy()
+    table = np.zeros(len(records), dtype=GRIB_WFIELD)
+    table["bitmap_off"], table["row_step"], table["std"] = -1, 1, 1.0
+    for i, rec in enumerate(records):
+        for name, value in rec.items():
+            if name not in GRIB_WFIELD.names:
+                raise L.P4CError(f"grib_window_pack: field {i}: {name!r} is no column of GRIB_WFIELD")
+            table[i][name] = value
+    return table
+
+
+def grib_window_pack(bytes_dev: torch.Tensor, fields, B: int, T: int, H: int, W: int, F: int) -> torch.Tensor:
+    """Windows of simple-packed GRIB2 fields without bitmap, whose slices (``grib2.window_slice``) lie in the device byte buffer
+    ``bytes_dev`` (uint8, dense, 4-byte aligned) -> (B, T, H, W, F) fp32 standardised features-last, one launch of
+    ``p4c_grib_window_pack`` (the contract is in include/py4cast_hip.h and, in numpy, ``grib2.unpack_window``).  ``fields``: B*T*F
+    GRIB_WFIELD records (or mappings, ``grib_wfields``), element (b, t, f) at (b*T + t)*F + f.  The records are checked by the
+    library, not here: a refusal raises ``P4CError`` before anything is launched.  Not differentiable."""
+    L.require_cuda(bytes_dev)
+    if bytes_dev.dtype != torch.uint8 or bytes_dev.dim() != 1 or not bytes_dev.is_contiguous() or bytes_dev.data_ptr() % 4:
+        raise L.P4CError(f"grib_window_pack: bytes {tuple(bytes_dev.shape)} {bytes_dev.dtype}: a dense, 4-byte aligned 1-D uint8 tensor expected")
+    B, T, H, W, F = int(B), int(T), int(H), int(W), int(F)
+    table = grib_wfields(fields).reshape(-1)
+    if min(B, T, H, W, F) < 1 or table.size != B * T * F:
+        raise L.P4CError(f"grib_window_pack: {table.size} fields for B x T x F = {B} x {T} x {F} (H = {H}, W = {W})")
+    if B * T * H * W >= 2 ** 31:      # the library refuses it too; here before the output is allocated
+        raise L.P4CError(f"grib_window_pack: {B * T * H * W} rows: at most 2^31 - 1 per call")
+    dev = bytes_dev.device
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+    out = torch.empty(B, T, H, W, F, dtype=torch.float32, device=dev)
+    read = int((H * W * table["nbits"].astype(np.int64) + 7).sum() // 8)
+    L.call("p4c_grib_window_pack", L.ptr(bytes_dev), bytes_dev.numel(), L.ptr(table_dev), ctypes.c_void_p(table.ctypes.data), L.ptr(out),
+           B, T, H, W, F, L.stream(dev), alg_bytes=read + 4 * out.numel())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ GRIB2 complex packing, decoded
 # launch constants of csrc/grib_complex.hip (p4c_grib_complex_tile() / _chunk() / _max_blocks() report the same)
 GRIB_COMPLEX_TILE = 2048        # values per tile, 8 per lane
